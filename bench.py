@@ -4,7 +4,14 @@ parameter gradients; optimiser step and data loading excluded; inputs resident i
 metric, SURVEY.md 8(d) -- plus the metric's second half, node-match Hits@1 against the oracle on a fixed
 val-style subsample.
 
-  python bench.py [--gpus N --steps K --warmup W --config auto|c2|c3]      (N > 1: launched by torch.distributed.run)
+  python bench.py [--gpus N --steps K --warmup W --config auto|c2|c3|c5] [--full] [--dump-outputs DIR]
+                                                                            (N > 1: launched by torch.distributed.run)
+
+A plain run sets up, warms up, times exactly K steps and prints the line (`value`, `ms_per_step` of one timed step, the `roofline` of
+the kernels those steps launched).  `--full` adds everything else the benchmark measures: Hits@1 against the oracle, the CPU baseline,
+the other arithmetic modes, workloads and module lists below (`extra_*`), the weak-scaling point and the `collectives` object (N > 1);
+the `--no-*` options leave single parts of it out.  `--dump-outputs DIR` writes what the last timed step handed its caller (embedding
+tables -- a fixed, seeded sample of rows --, loss terms, parameter gradients) as DIR/<name>.npy, right after the timed steps.
 
 Workloads (config.workload):
   c3 = BASELINE.json configs[2] = the configuration north_star quotes its target on ("4096-pair / 128-object / 512-pt synthetic
@@ -53,6 +60,9 @@ NOISE_FLOOR = 2e-5               # floor of the rerun-noise unit in default_vs_e
 
 COMPACT_LIMIT = 4096             # bytes: the driver keeps only the tail of stdout; the final line must fit and parse (tests/test_bench_line_cpu.py)
 EXTRAS_FILE = 'bench_extras.json'
+DUMP_LIMIT = 64 << 20            # bytes: every file of --dump-outputs together
+DUMP_TABLE_BYTES = 40 << 20      # bytes: the sampled rows of all embedding tables together
+DUMP_TABLE_ROWS = 4096           # rows per embedding table at most (one seeded sample, the same rows of every table)
 
 
 def _clip(text, n):
@@ -485,12 +495,55 @@ def roofline_objects(events, world, workload=None):
     return roofs
 
 
+def _np_out(t):
+    """float64 stays float64, every other floating type is written as float32."""
+    t = t.detach()
+    return t.double().cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+
+
+def dump_outputs(path, out_dict, loss_dict, steps):
+    """--dump-outputs: what the last timed step handed its caller, as <path>/<name>.npy -- emb_<table> (the encoder's embedding tables;
+    the same fixed, seeded sample of rows from each when they are larger than DUMP_TABLE_ROWS / DUMP_TABLE_BYTES allow), loss_<term>
+    (every loss term) and grad_<parameter> (every parameter gradient, whole).  The inputs and weights are seeded, so two builds run with
+    the same arguments can be compared file for file."""
+    arrays = {}
+    tables = {k: v for k, v in out_dict.items() if torch.is_tensor(v) and v.is_floating_point()}
+    if tables:
+        n = min(int(v.shape[0]) for v in tables.values())
+        width = sum(int(np.prod(v.shape[1:])) for v in tables.values())
+        k = max(1, min(n, DUMP_TABLE_ROWS, DUMP_TABLE_BYTES // (4 * max(1, width))))
+        rows = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        for name, v in tables.items():
+            arrays[f'emb_{name}'] = _np_out(v.index_select(0, torch.from_numpy(rows).to(v.device)))
+    for name, v in loss_dict.items():
+        if torch.is_tensor(v) and v.is_floating_point():
+            arrays[f'loss_{name}'] = _np_out(v)
+    named = list(steps.model.named_parameters())
+    if len(steps.modules) > 1:
+        named += [(f'multi_loss_layer_ial.{n}', p) for n, p in steps.multi_loss_layer_ial.named_parameters()]
+        named += [(f'multi_loss_layer_icl.{n}', p) for n, p in steps.multi_loss_layer_icl.named_parameters()]
+    for name, p in named:
+        if p.grad is not None:
+            arrays[f'grad_{name}'] = _np_out(p.grad)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f'--dump-outputs: {total} bytes > {DUMP_LIMIT}')
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    return {'dir': path, 'files': len(arrays), 'bytes': total}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--config', choices=['auto', 'c2', 'c3', 'c5'], default=os.environ.get('SGA_BENCH_CONFIG', 'auto'))
+    ap.add_argument('--full', action='store_true', help='also run everything beyond the headline figure (Hits@1, CPU baseline, extra_*, '
+                                                       'weak-scaling point, collectives); the --no-* options below refine it')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step (embedding tables sampled, loss terms, gradients) as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-hits', action='store_true')
     ap.add_argument('--no-attr', action='store_true', help='skip the extra point+gat+rel+attr (M = 4) measurement (N = 1)')
@@ -500,6 +553,8 @@ def main():
     ap.add_argument('--no-c2', action='store_true', help='skip the extra BASELINE configs[1] measurement (N = 1)')
     ap.add_argument('--no-exact', action='store_true', help='skip the extra measurement of the same step with fp32-MFMA sweeps (extra_exact_f32)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # Launched bare (`python bench.py --gpus N`): create the N ranks ourselves -- one process per GPU under torch.distributed.run,
@@ -556,8 +611,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(st, batch, warm, n):
-        """`warm` untimed steps, then exactly `n` steps between barrier + synchronize on both sides; MAX over ranks."""
+    def timed(st, batch, warm, n, keep=None):
+        """`warm` untimed steps, then exactly `n` steps between barrier + synchronize on both sides; MAX over ranks.  `keep` (a dict):
+        receives the last step's embedding tables as keep['out']."""
         for _ in range(warm):
             st.forward_backward(batch)
         barrier()
@@ -566,11 +622,13 @@ def main():
         for _ in range(n):
             e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
             e0.record()
-            _, ld = st.forward_backward(batch)
+            out, ld = st.forward_backward(batch)
             e1.record()
             evs.append((e0, e1))
         barrier()
         el = time.perf_counter() - t0
+        if keep is not None:
+            keep['out'] = out
         med = float(np.median([x.elapsed_time(y) for x, y in evs]))
         if world > 1:
             t = torch.tensor([el, med], device=dev, dtype=torch.float64)
@@ -583,7 +641,8 @@ def main():
     barrier()
     ops.KERNEL_EVENTS = {}
     sdist.COLLECTIVE_EVENTS = [] if world > 1 else None
-    elapsed, med_ms, loss_dict = timed(steps, dd, 0, args.steps)
+    head = {}
+    elapsed, med_ms, loss_dict = timed(steps, dd, 0, args.steps, keep=head)
     ops.KERNEL_EVENTS['_steps'] = args.steps
     events = ops.KERNEL_EVENTS
     ops.KERNEL_EVENTS = None
@@ -591,6 +650,10 @@ def main():
     loss_val = _finite(loss_dict, 'headline step')
     peak_gib = torch.cuda.max_memory_allocated() / 2 ** 30
     roofs = roofline_objects(events, world, workload=f'{cname}:{my_pairs}x{cfg["n_obj"]}x{cfg["n_pts"]}')
+    dumped = dump_outputs(args.dump_outputs, head['out'], loss_dict, steps) if args.dump_outputs and rank == 0 else None
+    del head
+
+    # ---- everything below up to the line is --full only: what the headline figure does not need
 
     # ---- extras, NOT the headline: the same steps in the other arithmetic modes (ops.set_mfma_mode), on the same batch and weights.
     #   extra_exact_f32: the sweeps on the fp32 MFMA (v_mfma_f32_16x16x4_f32, sweep16_kernel) -- the arithmetic every earlier round's headline
@@ -599,7 +662,7 @@ def main():
     #          MFMAs per product, fp32 accumulate) is fp32 arithmetic on the same operands; tests/test_fp64_chunked_gpu.py holds it to the
     #          fp64 evaluation at this size.
     extra_exact = default_vs_exact = None
-    want_exact = not args.no_exact and mode0 != 'f32'
+    want_exact = args.full and not args.no_exact and mode0 != 'f32'
     if want_exact:
         n_x = 2 if cname == 'c3' else max(2, min(args.steps, 10))
         head_grads = {n: p.grad.detach().clone() for n, p in steps.model.named_parameters() if p.grad is not None}
@@ -665,7 +728,7 @@ def main():
     # its own full measurement with its own roofline object, and the same batch with the reference's full module list
     # (point+gat+rel+attr, M = 4: what every yaml the reference ships trains; SURVEY.md 8(d) "also report +'attr'").  Exact fp32.
     extra_c2 = extra_attr = None
-    if world == 1 and not args.no_c2 and (cname != 'c2'):
+    if args.full and world == 1 and not args.no_c2 and (cname != 'c2'):
         try:
             del dd
             torch.cuda.empty_cache()
@@ -687,7 +750,7 @@ def main():
         except Exception as e:
             extra_c2 = {'error': f'{type(e).__name__}: {e}'}
             dd2 = None
-    elif world == 1 and cname == 'c2':
+    elif args.full and world == 1 and cname == 'c2':
         dd2 = dd
     else:
         dd2 = None
@@ -736,7 +799,7 @@ def main():
     # 4 pairs per step, ~40 objects per scene, 512 points -- where the 'pct' object encoder is ~95 % of the step.  Exact fp32; the
     # algorithmic rate counts the encoder's FLOPs only (forward x 3 for forward + backward; FLOPs per object stated).
     extra_pct = None
-    if world == 1 and not args.no_pct and cname != 'c5':
+    if args.full and world == 1 and not args.no_pct and cname != 'c5':
         try:
             from sgaligner_amd.synthetic import make_batch, to_device
             modsp = ['pct', 'gat', 'rel', 'attr']
@@ -768,7 +831,7 @@ def main():
     # ---- extra at N > 1 under --config auto: the weak-scaling point (BASELINE configs[1] per GPU: 512 pairs x 64 objects on every
     # rank, batch-global loss over 512 N pairs) next to the strong-scaling headline of the same line.
     weak_ref = None
-    if world > 1 and args.config == 'auto' and not args.no_scale_ref:
+    if args.full and world > 1 and args.config == 'auto' and not args.no_scale_ref:
         try:
             c2 = CONFIGS['c2']
             ddw = make_batch_fast(c2['pairs_per_gpu'], c2['n_obj'], c2['n_pts'], seed=143 + rank, device=dev)
@@ -782,7 +845,7 @@ def main():
         except Exception as e:
             weak_ref = {'error': f'{type(e).__name__}: {e}'}
 
-    collectives = sdist.collective_summary(coll_events, args.steps, dev) if world > 1 else None
+    collectives = sdist.collective_summary(coll_events, args.steps, dev) if args.full and world > 1 else None
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3
@@ -819,9 +882,11 @@ def main():
             line['extra_pct'] = extra_pct
         if weak_ref is not None:
             line['weak_scaling_point'] = weak_ref
-        if not args.no_hits:
+        if dumped is not None:
+            line['dump_outputs'] = dumped
+        if args.full and not args.no_hits:
             line['hits_at_1'] = hits_at_k(steps, n_obj, n_pts, dev)
-        if not args.no_cpu_baseline and world == 1:         # the CPU leg runs on rank 0 of a one-GPU run only
+        if args.full and not args.no_cpu_baseline and world == 1:         # the CPU leg runs on rank 0 of a one-GPU run only
             line['cpu_baseline'] = cpu_baseline(n_obj, n_pts, emb_dim=cfg.get('emb_dim', 100))
             line['speedup_vs_cpu_baseline'] = round(line['value'] / line['cpu_baseline']['value'], 1)
         emit(line)

@@ -111,3 +111,34 @@ def test_no_fraction_of_peak_above_one_by_construction():
     roofs = bench.roofline_objects(events, world=2)          # world 2: no traffic lookup
     assert len(roofs) == 1 and roofs[0]['frac'] <= 1.0 + 1e-9, roofs[0]
     assert roofs[0]['frac_of_bf16_peak_executed'] <= 1.0 + 1e-3
+
+
+def test_dump_outputs_is_a_fixed_sample_within_the_limit(tmp_path):
+    """--dump-outputs: the same rows of every embedding table (one seeded sample), every loss term and every gradient, float32 /
+    float64 only, under DUMP_LIMIT; two calls on the same tensors write identical files."""
+    import numpy as np
+    import torch
+
+    class FakeSteps:
+        modules = ['point']
+        model = torch.nn.Linear(8, 3)
+
+    steps = FakeSteps()
+    steps.model.weight.grad = torch.ones(3, 8)
+    steps.model.bias.grad = torch.zeros(3, dtype=torch.float32)
+    n = bench.DUMP_TABLE_ROWS * 3
+    out = {'point': torch.arange(n * 4, dtype=torch.float32).view(n, 4), 'joint': torch.arange(n * 2, dtype=torch.float64).view(n, 2),
+           'ids': torch.arange(n)}
+    loss = {'loss': torch.tensor(1.5, dtype=torch.float64), 'ial_loss': torch.tensor(0.25, dtype=torch.bfloat16), 'count': 3}
+    for d in ('a', 'b'):
+        info = bench.dump_outputs(str(tmp_path / d), out, loss, steps)
+        assert info['bytes'] <= bench.DUMP_LIMIT
+    names = sorted(p.name for p in (tmp_path / 'a').iterdir())
+    assert names == ['emb_joint.npy', 'emb_point.npy', 'grad_bias.npy', 'grad_weight.npy', 'loss_ial_loss.npy', 'loss_loss.npy']
+    for name in names:
+        a, b = np.load(tmp_path / 'a' / name), np.load(tmp_path / 'b' / name)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+    pt, jt = np.load(tmp_path / 'a' / 'emb_point.npy'), np.load(tmp_path / 'a' / 'emb_joint.npy')
+    assert pt.shape == (bench.DUMP_TABLE_ROWS, 4) and jt.shape == (bench.DUMP_TABLE_ROWS, 2)
+    assert np.array_equal(pt[:, 0] / 4, jt[:, 0] / 2)                     # the same rows of both tables
+    assert np.load(tmp_path / 'a' / 'loss_loss.npy').dtype == np.float64

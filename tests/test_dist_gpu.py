@@ -389,7 +389,7 @@ def test_bench_gpus2_creates_its_two_ranks():
         env.pop(k, None)
     env['HSA_ENABLE_IPC_MODE_LEGACY'] = '0'
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '1', '--config', 'c2',
-                        '--no-cpu-baseline', '--no-hits', '--no-scale-ref'], env=env, cwd=ROOT,
+                        '--full', '--no-cpu-baseline', '--no-hits', '--no-scale-ref'], env=env, cwd=ROOT,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 cfg=$1
 out=$2
-EXTRA=${3:-}      # e.g. --no-exact to leave the fp32-MFMA extra out of the pass
+EXTRA="--full ${3:-}"      # the extras run too; a third argument refines them, e.g. --no-exact to leave the fp32-MFMA extra out of the pass
 if [ ! -f "$out" ]; then
   echo "# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-include-regex 'sweep.*_kernel<3, (true|false)|pointnet_fwd_kernel'), bench.py --config <cfg> --steps 2 --warmup 1" > $out
   echo "# unit: KiB per dispatch (average over the profiled launches); gfx950: FETCH_SIZE under-reports wide coalesced reads by 2x (MI355X_MICROARCH.md, HBM) -> bytes = (2*FETCH + WRITE) * 1024" >> $out
