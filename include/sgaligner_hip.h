@@ -139,18 +139,12 @@ int sga_loss_neg_sums_shard(const float* Z, int Dp, int A, int J1, int J2, float
                             void* stream);
 int sga_loss_neg_grad_shard(const float* Z, int Dp, int A, int J1, int J2, float tau0, float tau1, const double* gs8,
                             float* dZ, int a_lo, int a_hi, void* stream);
-/* anchors x anchors terms for NT tables (modalities..., joint): out = [NT icl sums | M iala | M ialb], M = NT-1 */
-/* [a_lo, a_hi) (here and below): the anchor shard this process owns (0, A on one GPU).  Outputs are that shard's partial
- * contribution; the sum over a partition of [0, A) equals the unsharded result (one process per GPU all-reduces it). */
-int sga_loss_anchor_fwd(const float* const* Z, const int* Dp, int NT, int A, const double* sums, float alpha,
-                        float tau_icl, float tau_ial, double* out, int a_lo, int a_hi, void* stream);
-/* given coef = dL/d(out): M1[k][j*A+i] = dL/dS_k[i,j] and gs[k][8] = dL/d(sums) */
-int sga_loss_anchor_bwd(const float* const* Z, const int* Dp, int NT, int A, const double* sums, float alpha,
-                        float tau_icl, float tau_ial, const float* coef, float* const* M1, double* gs, int a_lo, int a_hi,
-                        void* stream);
-
-/* MFMA mode 'f16' (configs[4]: tables wider than 128 columns): the same two launches with fp16 INPUTS for the similarities of every table k
- * whose Zh[k] != NULL -- Zh[k] = the fp16 copy of Z[k]'s rows that sga_wide16_prepare writes (row pitch Dp[k] halfs); fp32 accumulate, the
+/* anchors x anchors terms for NT tables (modalities..., joint): fwd: out = [NT icl sums | M iala | M ialb], M = NT-1;
+ * bwd, given coef = dL/d(out): M1[k][j*A+i] = dL/dS_k[i,j] and gs[k][8] = dL/d(sums).
+ * [a_lo, a_hi) (here and below): the anchor shard this process owns (0, A on one GPU).  Outputs are that shard's partial
+ * contribution; the sum over a partition of [0, A) equals the unsharded result (one process per GPU all-reduces it).
+ * Exact fp32 unless Zh is given: MFMA mode 'f16' (configs[4]: tables wider than 128 columns) takes fp16 INPUTS for the similarities of every
+ * table k whose Zh[k] != NULL -- Zh[k] = the fp16 copy of Z[k]'s rows that sga_wide16_prepare writes (row pitch Dp[k] halfs); fp32 accumulate, the
  * epilogue unchanged.  Zh == NULL or Zh[k] == NULL: exact fp32 for that table.  1e-2 tolerance, like the mode's sweeps.
  * ws / ws_bytes (optional; sga_loss_anchor_f16_ws_bytes(NT, A, a_hi - a_lo) bytes; the caller passes it for WIDE tables): the 2 NT
  * similarity blocks of the shard (X1 X2^T and X2 X1^T, [A][a_hi - a_lo] fp32 each) are formed first -- tables with Zh[k] on the fp16 tile
@@ -164,7 +158,7 @@ int sga_loss_anchor_bwd_f16(const float* const* Z, const void* const* Zh, const 
                             float alpha, float tau_icl, float tau_ial, const float* coef, float* const* M1,
                             double* gs, int a_lo, int a_hi, void* ws, size_t ws_bytes, void* stream);
 
-/* dZ[a_lo:a_hi,:] += M1^T Z[A:2A,:] ; dZ[A:2A,:] += M1 Z[a_lo:a_hi,:]  (M1 [A, a_hi-a_lo] from sga_loss_anchor_bwd; dZ zero-initialised) */
+/* dZ[a_lo:a_hi,:] += M1^T Z[A:2A,:] ; dZ[A:2A,:] += M1 Z[a_lo:a_hi,:]  (M1 [A, a_hi-a_lo] from sga_loss_anchor_bwd_f16; dZ zero-initialised) */
 int sga_loss_stash_grad(const float* M1, const float* Z, int A, int Dp, float* dZ, int a_lo, int a_hi, void* stream);
 /* fused variants for the normal pipeline, where the last table is the fusion of the M others: every joint
  * similarity is S_J = sum_m beta_m S_m (beta_m = w_m^2 / sum w^2, w = softmax(fusion.weight), sg_aligner.py:32-34
@@ -191,7 +185,7 @@ int sga_loss_multi_grad_centred(const float* const* Zc, int M, const float* beta
                                 const double* gs, float* const* dZ, double* gamma, int a_lo, int a_hi, void* stream);
 int sga_loss_scatter_tangent_stat(const float* dZ, const float* Z, const float* nrm, const int32_t* idx, int R, int D,
                                   const void* stat_ws, float* dE, void* stream);
-/* fused anchors x anchors terms (M in {2,3,4}): same outputs as sga_loss_anchor_fwd/bwd for tables (Z_1..Z_M, joint), with the
+/* fused anchors x anchors terms (M in {2,3,4}): same outputs as sga_loss_anchor_fwd_f16/bwd_f16 for tables (Z_1..Z_M, joint), with the
  * joint similarities derived in registers; bwd writes M1[m] = dL/dS_m + beta_m dL/dS_J (no joint stash) and gamma[m] += dL/dbeta_m.
  * bwd with out_terms != NULL ([(M+1) + 2M] doubles + slots, like `out` of the fwd call) ALSO returns the forward term values of the
  * anchor rows [a_lo, a_hi) from the same launch: a training step whose dL/d(terms) (`coef`) is known before the terms are -- the
@@ -224,10 +218,6 @@ int sga_loss_anchor_multi_bwd_symx(const float* const* Z, int M, const float* be
 int sga_loss_stash_grad_symx(const float* M1, const float* M2, const float* Z, int A, int Dp, float* dZ, int a_lo, int a_hi,
                              int j_lo, int j_hi, int mir, void* stream);
 
-/* ZJ[r, m*104+d] = sqrt(beta_m) Z_m[r,d] for the anchor rows (operand of the anchors x anchors kernels), and its adjoint */
-int sga_loss_build_joint(const float* const* Z, int M, const float* beta, int rows, float* ZJ, void* stream);
-int sga_loss_fold_joint(const float* const* Z, int M, const float* beta, const float* dZJ, int rows, float* const* dZ,
-                        double* gamma2, void* stream);
 /* *poison = NaN if any row norm is below F.normalize's eps (the identity above would not hold): fail loudly */
 int sga_loss_check_norms(const float* nrm, int n, float* poison, void* stream);
 

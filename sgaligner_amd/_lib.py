@@ -75,8 +75,6 @@ SIGNATURES = {
     'sga_loss_neg_grad': (I, [P, I, I, I, I, F, F, P, P, P]),
     'sga_loss_neg_sums_shard': (I, [P, I, I, I, I, F, F, P, I, I, P]),
     'sga_loss_neg_grad_shard': (I, [P, I, I, I, I, F, F, P, P, I, I, P]),
-    'sga_loss_anchor_fwd': (I, [P, P, I, I, P, F, F, F, P, I, I, P]),
-    'sga_loss_anchor_bwd': (I, [P, P, I, I, P, F, F, F, P, P, P, I, I, P]),
     'sga_loss_anchor_f16_ws_bytes': (c_size_t, [I, I, I]),
     'sga_loss_anchor_fwd_f16': (I, [P, P, P, I, I, P, F, F, F, P, I, I, P, c_size_t, P]),
     'sga_loss_anchor_bwd_f16': (I, [P, P, P, I, I, P, F, F, F, P, P, P, I, I, P, c_size_t, P]),
@@ -89,8 +87,6 @@ SIGNATURES = {
     'sga_loss_multi_sums_centred': (I, [P, I, P, I, I, I, F, F, P, I, I, P]),
     'sga_loss_multi_grad_centred': (I, [P, I, P, I, I, I, F, F, P, P, P, I, I, P]),
     'sga_loss_scatter_tangent_stat': (I, [P, P, P, P, I, I, P, P, P]),
-    'sga_loss_build_joint': (I, [P, I, P, I, P, P]),
-    'sga_loss_fold_joint': (I, [P, I, P, P, I, P, P, P]),
     'sga_loss_check_norms': (I, [P, I, P, P]),
     'sga_loss_slots': (I, []),
     'sga_loss_anchor_multi_fwd': (I, [P, I, P, I, P, F, F, F, P, I, I, P]),

@@ -1065,38 +1065,6 @@ static void launch_sweep16(const MultiArgs& a, int nwg, hipStream_t s) {
     hipLaunchKernelGGL(k, dim3(nwg), dim3(S16_THREADS), lds, s, a);
 }
 
-// joint operand rows for the anchors x anchors kernels: ZJ[r, m*104 + d] = sqrt(beta_m) Z_m[r, d]
-__global__ void build_joint_kernel(MultiArgs a, float* __restrict__ ZJ, int rows) {
-    const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
-    for (int r = blockIdx.x * wpb + (threadIdx.x >> 6); r < rows; r += gridDim.x * wpb)
-        for (int m = 0; m < a.M; ++m) {
-            const float sb = sqrtf(a.beta[m]);
-            for (int d = lane; d < 104; d += 64) ZJ[(size_t)r * (a.M * 104) + m * 104 + d] = sb * a.Z[m][(size_t)r * 104 + d];
-        }
-}
-
-// fold dL/dZJ back: dZ_m[r,:] += sqrt(beta_m) dZJ[r, block m];  gamma2[m] += <dZJ[r, block m], Z_m[r,:]>
-__global__ void fold_joint_kernel(MultiArgs a, const float* __restrict__ dZJ, int rows, double* __restrict__ gamma2) {
-    const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int r = blockIdx.x * wpb + (threadIdx.x >> 6); r < rows; r += gridDim.x * wpb)
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            if (m >= a.M) break;
-            const float sb = sqrtf(a.beta[m]);
-            for (int d = lane; d < 104; d += 64) {
-                const float gj = dZJ[(size_t)r * (a.M * 104) + m * 104 + d];
-                acc[m] = fmaf(gj, a.Z[m][(size_t)r * 104 + d], acc[m]);
-                a.dZ[m][(size_t)r * 104 + d] += sb * gj;
-            }
-        }
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const float v = wave_sum(acc[m]);
-        if (lane == 0 && m < a.M && v != 0.f) atomicAdd(gamma2 + m, (double)v);
-    }
-}
-
 // poison = NaN if any row of any table took F.normalize's eps branch (then S_J != sum beta_m S_m)
 __global__ void check_norms_kernel(const float* __restrict__ nrm, int n, float* __restrict__ poison) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
@@ -1428,7 +1396,7 @@ struct AnchorMultiArgs {
     int j_hi, mir;                 // symmetric mode: columns [j_lo, j_hi); tiles at j >= mir also produce the mirrored element (one GPU: A, i_hi)
 };
 
-template <int M, bool BWD>
+template <int M>
 __global__ __launch_bounds__(CT_THREADS, M <= 3 ? 2 : 1) void anchor_multi_kernel(AnchorMultiArgs a) {
     constexpr int DP = 104, NQ = 13, NT = M + 1;
     extern __shared__ __attribute__((aligned(16))) float lds[];      // [M][2][32][DP] own rows + inv_s[NT*8]
@@ -1562,7 +1530,7 @@ __global__ void inv_sums_kernel(const double* __restrict__ sums, float* __restri
 
 // RB = anchor rows staged per workgroup: 32 (two wave pairs, each walking its own J tiles) for M <= 3; 16 for M = 4, where 32 rows of
 // four tables are 106 KiB of LDS = one workgroup per CU (all four waves then share the 16 rows and split the J tiles four ways).
-// TERMS: the same launch also accumulates the forward TERM values (what anchor_multi_kernel<M,false> returns): the epilogue already holds
+// TERMS: the same launch also accumulates the forward TERM values (what anchor_multi_kernel<M> returns): the epilogue already holds
 // every q they are made of, so a training step whose dL/d(terms) is known at forward time (ops.FusedContrastiveFn one-pass mode) runs the
 // A x A similarities once instead of twice.
 // SYM (M <= 3, TERMS): every UNORDERED anchor pair is visited once.  The block's rows [i_lo, i_hi) meet the columns j >= i_lo only; in a
@@ -2081,11 +2049,6 @@ static int fill_anchor(AnchorArgs& a, const float* const* Z, const int* Dp, int 
     return SGA_OK;
 }
 
-extern "C" int sga_loss_anchor_fwd(const float* const* Z, const int* Dp, int NT, int A, const double* sums,
-                                   float alpha, float tau_icl, float tau_ial, double* out, int a_lo, int a_hi, void* stream) {
-    return sga_loss_anchor_fwd_f16(Z, nullptr, Dp, NT, A, sums, alpha, tau_icl, tau_ial, out, a_lo, a_hi, nullptr, 0, stream);
-}
-
 // A workspace given (the caller's choice: wide tables): the 2 NT similarity blocks of the anchor shard are formed first -- tables with an
 // fp16 copy Zh[k] on wide16.hip's fp16 tile core (up to 8 blocks per launch), the others by the exact-fp32 NT GEMM of gemm.hip -- and the
 // epilogue-only form of the kernel reads them.
@@ -2133,10 +2096,10 @@ static int anchor_pre_blocks(AnchorArgs& a, const void* const* Zh, void* ws, siz
 extern "C" int sga_loss_anchor_fwd_f16(const float* const* Z, const void* const* Zh, const int* Dp, int NT, int A, const double* sums,
                                        float alpha, float tau_icl, float tau_ial, double* out, int a_lo, int a_hi, void* ws, size_t ws_bytes,
                                        void* stream) {
-    SGA_CHECK_ARG(Z && Dp && sums && out && A >= 0, "sga_loss_anchor_fwd: bad argument");
+    SGA_CHECK_ARG(Z && Dp && sums && out && A >= 0, "sga_loss_anchor_fwd_f16: bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int M = NT > 1 ? NT - 1 : 0;
-    if (int rc0 = zero_slots(out, NT + 2 * M, s, "sga_loss_anchor_fwd")) return rc0;
+    if (int rc0 = zero_slots(out, NT + 2 * M, s, "sga_loss_anchor_fwd_f16")) return rc0;
     if (A == 0 || a_hi <= a_lo) return SGA_OK;
     AnchorArgs a{};
     int rc = fill_anchor(a, Z, Dp, NT, A, sums, alpha, tau_icl, tau_ial, a_lo, a_hi);
@@ -2148,35 +2111,29 @@ extern "C" int sga_loss_anchor_fwd_f16(const float* const* Z, const void* const*
     if (pre) hipLaunchKernelGGL((anchor_kernel<false, true>), dim3((a_hi - a_lo + 127) / 128, (A + 31) / 32), dim3(CT_THREADS), 0, s, a);
     else hipLaunchKernelGGL(anchor_kernel<false>, dim3((a_hi - a_lo + 127) / 128, (A + 63) / 64), dim3(CT_THREADS), 0, s, a);
     fold_slots(out, NT + 2 * M, s);
-    SGA_CHECK_LAUNCH("sga_loss_anchor_fwd");
+    SGA_CHECK_LAUNCH("sga_loss_anchor_fwd_f16");
     return SGA_OK;
-}
-
-extern "C" int sga_loss_anchor_bwd(const float* const* Z, const int* Dp, int NT, int A, const double* sums,
-                                   float alpha, float tau_icl, float tau_ial, const float* coef, float* const* M1,
-                                   double* gs, int a_lo, int a_hi, void* stream) {
-    return sga_loss_anchor_bwd_f16(Z, nullptr, Dp, NT, A, sums, alpha, tau_icl, tau_ial, coef, M1, gs, a_lo, a_hi, nullptr, 0, stream);
 }
 
 extern "C" int sga_loss_anchor_bwd_f16(const float* const* Z, const void* const* Zh, const int* Dp, int NT, int A, const double* sums,
                                        float alpha, float tau_icl, float tau_ial, const float* coef, float* const* M1,
                                        double* gs, int a_lo, int a_hi, void* ws, size_t ws_bytes, void* stream) {
-    SGA_CHECK_ARG(Z && Dp && sums && coef && M1 && gs && A >= 0, "sga_loss_anchor_bwd: bad argument");
+    SGA_CHECK_ARG(Z && Dp && sums && coef && M1 && gs && A >= 0, "sga_loss_anchor_bwd_f16: bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc0 = zero_slots(gs, NT * 8, s, "sga_loss_anchor_bwd")) return rc0;
+    if (int rc0 = zero_slots(gs, NT * 8, s, "sga_loss_anchor_bwd_f16")) return rc0;
     if (A == 0 || a_hi <= a_lo) return SGA_OK;
     AnchorArgs a{};
     int rc = fill_anchor(a, Z, Dp, NT, A, sums, alpha, tau_icl, tau_ial, a_lo, a_hi);
     if (rc) return rc;
     a.coef = coef; a.gs = gs;
-    for (int k = 0; k < NT; ++k) { SGA_CHECK_ARG(M1[k], "sga_loss_anchor_bwd: null stash %d", k); a.M1[k] = M1[k]; }
+    for (int k = 0; k < NT; ++k) { SGA_CHECK_ARG(M1[k], "sga_loss_anchor_bwd_f16: null stash %d", k); a.M1[k] = M1[k]; }
     for (int k = 0; k < NT; ++k) a.Zh[k] = Zh ? static_cast<const _Float16*>(Zh[k]) : nullptr;
     bool pre = false;
     if (int rcp = anchor_pre_blocks(a, Zh, ws, ws_bytes, s, pre)) return rcp;
     if (pre) hipLaunchKernelGGL((anchor_kernel<true, true>), dim3((a_hi - a_lo + 127) / 128, (A + 31) / 32), dim3(CT_THREADS), 0, s, a);
     else hipLaunchKernelGGL(anchor_kernel<true>, dim3((a_hi - a_lo + 127) / 128, (A + 63) / 64), dim3(CT_THREADS), 0, s, a);
     fold_slots(gs, NT * 8, s);
-    SGA_CHECK_LAUNCH("sga_loss_anchor_bwd");
+    SGA_CHECK_LAUNCH("sga_loss_anchor_bwd_f16");
     return SGA_OK;
 }
 
@@ -2276,29 +2233,6 @@ extern "C" int sga_loss_multi_grad_centred(const float* const* Zc, int M, const 
     return multi_grad_impl(Zc, M, 102, true, beta, A, J1, J2, tau0, tau1, gs, dZ, gamma, a_lo, a_hi, stream);
 }
 
-extern "C" int sga_loss_build_joint(const float* const* Z, int M, const float* beta, int rows, float* ZJ, void* stream) {
-    SGA_CHECK_ARG(Z && beta && ZJ && M >= 2 && M <= 4 && rows >= 0, "sga_loss_build_joint: bad argument");
-    if (rows == 0) return SGA_OK;
-    MultiArgs a{};
-    a.M = M; a.beta = beta;
-    for (int m = 0; m < M; ++m) a.Z[m] = Z[m];
-    hipLaunchKernelGGL(build_joint_kernel, dim3(rows_grid(rows)), dim3(256), 0, static_cast<hipStream_t>(stream), a, ZJ, rows);
-    SGA_CHECK_LAUNCH("sga_loss_build_joint");
-    return SGA_OK;
-}
-
-extern "C" int sga_loss_fold_joint(const float* const* Z, int M, const float* beta, const float* dZJ, int rows,
-                                   float* const* dZ, double* gamma2, void* stream) {
-    SGA_CHECK_ARG(Z && beta && dZJ && dZ && gamma2 && M >= 2 && M <= 4 && rows >= 0, "sga_loss_fold_joint: bad argument");
-    if (rows == 0) return SGA_OK;
-    MultiArgs a{};
-    a.M = M; a.beta = beta;
-    for (int m = 0; m < M; ++m) { a.Z[m] = Z[m]; a.dZ[m] = dZ[m]; }
-    hipLaunchKernelGGL(fold_joint_kernel, dim3(rows_grid(rows)), dim3(256), 0, static_cast<hipStream_t>(stream), a, dZJ, rows, gamma2);
-    SGA_CHECK_LAUNCH("sga_loss_fold_joint");
-    return SGA_OK;
-}
-
 extern "C" int sga_loss_check_norms(const float* nrm, int n, float* poison, void* stream) {
     SGA_CHECK_ARG(nrm && poison && n >= 0, "sga_loss_check_norms: bad argument");
     if (n == 0) return SGA_OK;
@@ -2344,7 +2278,7 @@ extern "C" int sga_loss_stash_grad(const float* M1, const float* Z, int A, int D
         if (rc) return rc;
         return sga_gemm(0, 0, A, Dp, ns, M1, ns, 0, X1, Dp, dZ + (size_t)A * Dp, Dp, nullptr, 1, stream);
     }
-    for (int c0 = 0; c0 < Dp; c0 += 320) {               // column blocks of <= 320 (the 104*M-wide joint operand takes one or two)
+    for (int c0 = 0; c0 < Dp; c0 += 320) {               // column blocks of <= 320
         const int w = Dp - c0 < 320 ? Dp - c0 : 320;
         launch_stash(true, w > 128, M1, X2 + c0, dZ + (size_t)a_lo * Dp + c0, ns, A, ns, Dp, w, s);
         launch_stash(false, w > 128, M1, X1 + c0, dZ + (size_t)A * Dp + c0, A, ns, ns, Dp, w, s);
@@ -2369,10 +2303,10 @@ static int fill_anchor_multi(AnchorMultiArgs& a, const float* const* Z, int M, c
     return SGA_OK;
 }
 
-template <int M, bool BWD>
+template <int M>
 static void launch_anchor_multi(const AnchorMultiArgs& a, hipStream_t s) {
     const size_t lds = (size_t)(M * 2 * 32 * 104 + (M + 1) * 8) * sizeof(float);
-    auto k = anchor_multi_kernel<M, BWD>;
+    auto k = anchor_multi_kernel<M>;
     hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const int nib = (a.i_hi - a.i_lo + 31) / 32;
     hipLaunchKernelGGL(k, dim3(nib * a.nsplit), dim3(CT_THREADS), lds, s, a);
@@ -2390,7 +2324,7 @@ extern "C" int sga_loss_anchor_multi_fwd(const float* const* Z, int M, const flo
     int rc = fill_anchor_multi(a, Z, M, beta, A, sums, alpha, tau_icl, tau_ial, a_lo, a_hi);
     if (rc) return rc;
     a.out = out;
-    if (M == 2) launch_anchor_multi<2, false>(a, s); else if (M == 3) launch_anchor_multi<3, false>(a, s); else launch_anchor_multi<4, false>(a, s);
+    if (M == 2) launch_anchor_multi<2>(a, s); else if (M == 3) launch_anchor_multi<3>(a, s); else launch_anchor_multi<4>(a, s);
     fold_slots(out, n, s);
     SGA_CHECK_LAUNCH("sga_loss_anchor_multi_fwd");
     return SGA_OK;

@@ -37,7 +37,6 @@
 // Geometry.  Per 16 owner rows a wave holds 44 operand + 28 gradient-accumulator + 8 S registers PER TABLE; with three tables (240) plus the
 // operands in flight that is more than the 256 registers of a two-wave SIMD, so the M = 3 gradient sweep runs ONE wave per SIMD (4 waves x
 // 16 owner rows, <= 512 registers) with every LDS operand requested a group of MFMAs ahead inside the matrix stream (sched_barrier-pinned); M = 2 and the forward sums (no accumulators) run 8 waves, two per SIMD.
-#include <stdlib.h>
 #include <type_traits>
 
 #include "loss_math.h"
@@ -1078,11 +1077,10 @@ int fill_t(TArgs& a, const void* const* Zb, int M, const float* beta, int A, int
         for (int sg = 0; sg < G.nseg; ++sg) steps += G.seg[sg].jt_hi - G.seg[sg].jt_lo;
         // Work units of 160 .. 640 tile steps: the longer a unit, the fewer owner-operand loads and gradient flushes per tile (configs[2]: 2.80 ->
         // 2.74 s from 160 to 640, flat beyond; SHORTER units, whose tile stream would fit an XCD's L2 whatever the workgroups' phases, only
-        // cost: 2.88 s at 56) -- as long as every CU still gets >= ~12 units of the group.  (SGA_SWEEP3_UNIT overrides, for experiments.)
-        static const int unit_env = [] { const char* e = std::getenv("SGA_SWEEP3_UNIT"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 0; }();
+        // cost: 2.88 s at 56) -- as long as every CU still gets >= ~12 units of the group.
         const long n_ob_g = (G.nown + own_rows - 1) / own_rows;
         const long want = (long)steps * n_ob_g / (12L * sga_num_cus());
-        const int unit_steps = unit_env ? unit_env : want < 160 ? 160 : want > 640 ? 640 : (int)want;
+        const int unit_steps = want < 160 ? 160 : want > 640 ? 640 : (int)want;
         int nsp = (steps + unit_steps - 1) / unit_steps;
         if (nsp > steps) nsp = steps;
         if (nsp < 1) nsp = 1;

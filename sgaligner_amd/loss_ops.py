@@ -126,14 +126,9 @@ class ContrastiveTermsFn(torch.autograd.Function):
                 zh = torch.empty((max(s.R, 1), dp), device=dev, dtype=torch.float16)
                 zt = torch.empty((dp, ldt), device=dev, dtype=torch.float16)
                 _lib.check(L.sga_wide16_prepare(_p(z), dp, s.A, s.J1, s.J2, _p(zh), _p(zt), st), 'sga_wide16_prepare')
-                ev = None
-                if _o.KERNEL_EVENTS is not None:
-                    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                    ev[0].record()
+                ev = _ev_start()
                 _lib.check(L.sga_loss_neg_sums_f16(_p(zh), dp, s.A, s.J1, s.J2, TAU_ICL, TAU_IAL, _p(sk), a_lo, a_hi, st), 'sga_loss_neg_sums_f16')
-                if ev is not None:
-                    ev[1].record()
-                    _o.KERNEL_EVENTS.setdefault('wide16_sums', []).append(ev + ((s.A, s.J1, s.J2, dp),))
+                _ev_stop(ev, 'wide16_sums', (s.A, s.J1, s.J2, dp))
             else:
                 _lib.check(L.sga_loss_neg_sums_shard(_p(z), dp, s.A, s.J1, s.J2, TAU_ICL, TAU_IAL, _p(sk), a_lo, a_hi, st), 'sga_loss_neg_sums')
             sums[k].copy_(sk[:8])
@@ -146,26 +141,20 @@ class ContrastiveTermsFn(torch.autograd.Function):
         # (all tables wide: their 2 nt similarity blocks on the fp16 tile core first, then the epilogue-only kernel -- one anchor-row block at a time)
         all16 = all(dp > 128 for dp in dps)          # every table wide: similarity blocks first (fp16 tile core / fp32 GEMM), epilogue-only kernel
         if all16 and a_hi > a_lo:
-            eva = None
-            if _o.KERNEL_EVENTS is not None:
-                eva = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                eva[0].record()
+            eva = _ev_start() if all(zh is not None for zh in zhs) else None
             out.zero_()
             part = torch.empty_like(out)
             chunks = _anchor_chunks(a_lo, a_hi, s.A, 2 * nt)
             ws = torch.empty((int(L.sga_loss_anchor_f16_ws_bytes(nt, s.A, max(hi - lo for lo, hi in chunks))),), device=dev, dtype=torch.uint8)
             for lo, hi in chunks:
                 _lib.check(L.sga_loss_anchor_fwd_f16(zarr, _ptr_array(zhs), dparr, nt, s.A, _p(sums), float(alpha), TAU_ICL, TAU_IAL, _p(part), lo, hi,
-                                                     _p(ws), ws.numel(), st), 'sga_loss_anchor_fwd')
+                                                     _p(ws), ws.numel(), st), 'sga_loss_anchor_fwd_f16')
                 out += part
             del ws, part
-            if eva is not None:
-                eva[1].record()
-                if all(zh is not None for zh in zhs):
-                    _o.KERNEL_EVENTS.setdefault('wide16_aa_fwd', []).append(eva + ((s.A, sum(dps)),))
+            _ev_stop(eva, 'wide16_aa_fwd', (s.A, sum(dps)))
         else:
             _lib.check(L.sga_loss_anchor_fwd_f16(zarr, _ptr_array(zhs), dparr, nt, s.A, _p(sums), float(alpha), TAU_ICL, TAU_IAL, _p(out), a_lo, a_hi,
-                                                 None, 0, st), 'sga_loss_anchor_fwd')
+                                                 None, 0, st), 'sga_loss_anchor_fwd_f16')
         out = _allreduce_sum(out[:nt + 2 * m].contiguous(), reduce)
         ctx.shard, ctx.reduce = (a_lo, a_hi), reduce
         ctx.s, ctx.alpha, ctx.dps, ctx.nt = s, float(alpha), dps, nt
@@ -199,10 +188,8 @@ class ContrastiveTermsFn(torch.autograd.Function):
             cmax = max(hi - lo for lo, hi in chunks)
             m1 = [torch.empty((A * cmax,), device=dev, dtype=torch.float32) for _ in range(nt)]
             gsc = torch.empty((slots, nt, 8), device=dev, dtype=torch.float64)
-            ws = ws16 = evb = None
-            if all16 and _o.KERNEL_EVENTS is not None:
-                evb = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                evb[0].record()
+            ws = ws16 = None
+            evb = _ev_start() if all(zh is not None for zh in zhs) else None
             if all16:
                 ws = torch.empty((int(L.sga_loss_anchor_f16_ws_bytes(nt, A, cmax)),), device=dev, dtype=torch.uint8)
                 if any(zh is not None for zh in zhs):
@@ -210,7 +197,7 @@ class ContrastiveTermsFn(torch.autograd.Function):
             for lo, hi in chunks:          # bounded stash: one anchor-row block at a time
                 _lib.check(L.sga_loss_anchor_bwd_f16(_ptr_array(zs), _ptr_array(zhs), dparr, nt, A, _p(sums), ctx.alpha, TAU_ICL, TAU_IAL, _p(coef),
                                                      _ptr_array(m1), _p(gsc), lo, hi, _p(ws) if all16 else None, ws.numel() if all16 else 0, st),
-                           'sga_loss_anchor_bwd')
+                           'sga_loss_anchor_bwd_f16')
                 gs += gsc[0]
                 for k in range(nt):
                     # dX1[i] = sum_j G[i,j] X2[j]  (M1 = G^T),  dX2[j] = sum_i G[i,j] X1[i]
@@ -220,32 +207,21 @@ class ContrastiveTermsFn(torch.autograd.Function):
                     else:
                         _lib.check(L.sga_loss_stash_grad(_p(m1[k]), _p(zs[k]), A, dps[k], _p(dzs[k]), lo, hi, st), 'sga_loss_stash_grad')
             del m1, ws, ws16
-            if evb is not None:
-                evb[1].record()
-                if all(zh is not None for zh in zhs):
-                    _o.KERNEL_EVENTS.setdefault('wide16_aa_bwd', []).append(evb + ((A, sum(dps)),))
+            _ev_stop(evb, 'wide16_aa_bwd', (A, sum(dps)))
         gs = _allreduce_sum(gs, ctx.reduce)                      # dL/d(global sums) needs every shard's anchors x anchors tiles
         grads = []
         for k in range(nt):
             z, dp, dz = zs[k], dps[k], dzs[k]
-            ev = None
-            if _o.KERNEL_EVENTS is not None and dp <= 128:
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                ev[0].record()
+            ev = _ev_start() if dp <= 128 else None
             if zhs[k] is not None:
                 # opt-in fp16-input MFMA (configs[4]): S and both gradient GEMMs on v_mfma_f32_32x32x16_f16 (csrc/wide16.hip)
                 need = int(L.sga_loss_neg_grad_f16_bytes(A, s.J1, s.J2))
                 have = max(min(need, _stash_bytes()), int(L.sga_loss_neg_grad_f16_bytes(min(A, 128), s.J1, s.J2)))
                 stash = torch.empty((have,), device=dev, dtype=torch.uint8)
-                ev16 = None
-                if _o.KERNEL_EVENTS is not None:
-                    ev16 = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                    ev16[0].record()
+                ev16 = _ev_start()
                 _lib.check(L.sga_loss_neg_grad_f16(_p(zhs[k]), _p(zts[k]), dp, A, s.J1, s.J2, TAU_ICL, TAU_IAL, gs[k].data_ptr(), _p(dz),
                                                    _p(stash), have, a_lo, a_hi, st), 'sga_loss_neg_grad_f16')
-                if ev16 is not None:
-                    ev16[1].record()
-                    _o.KERNEL_EVENTS.setdefault('wide16_grad', []).append(ev16 + ((A, s.J1, s.J2, dp),))
+                _ev_stop(ev16, 'wide16_grad', (A, s.J1, s.J2, dp))
                 del stash
             elif dp > 128 and _o.WIDE_STASH and a_lo == 0 and a_hi == A:
                 # wide rows: S is the expensive part -> coefficient stash + GEMMs, S computed once (csrc/contrastive.hip, sweep_coef_kernel)
@@ -258,9 +234,7 @@ class ContrastiveTermsFn(torch.autograd.Function):
             else:
                 _lib.check(L.sga_loss_neg_grad_shard(_p(z), dp, A, s.J1, s.J2, TAU_ICL, TAU_IAL, gs[k].data_ptr(), _p(dz), a_lo, a_hi, st),
                            'sga_loss_neg_grad')
-            if ev is not None:
-                ev[1].record()
-                _o.KERNEL_EVENTS.setdefault('sweep_kernel<4,4,grad>', []).append(ev + ((A, s.J1, s.J2, dp),))
+            _ev_stop(ev, 'sweep_kernel<4,4,grad>', (A, s.J1, s.J2, dp))
             t, d = ctx.shapes[k]
             de = torch.zeros((t, d), device=dev, dtype=torch.float32)
             _lib.check(L.sga_loss_scatter(_p(dz), _p(z), _p(nrms[k]), _p(s.idx), s.R, d, dp, _p(de), st), 'sga_loss_scatter')
@@ -484,10 +458,62 @@ def _allreduce_sum(t, group_reduce):
     return t
 
 
+def _aa_walk(s, zs, zbs, zcs, tier, beta, sums, alpha, coef, dzs, walk, sym, out=None):
+    """The anchors x anchors backward of FusedContrastiveFn, one anchor-row block at a time: the kernel writes the block's transposed
+    coefficient stashes (dL/dS_m + beta_m dL/dS_J, no joint stash), the tier's stash products add dL/dZ into dzs[m], the next block reuses
+    the buffers -- memory O(A*D + _o.STASH_BYTES), never A x A (nothing of that size at configs[2]).  walk: _sym_jobs launches
+    (lo, hi, j_lo, j_hi, mir) if `sym` (a launch also evaluates the mirrored elements from column mir on, into a second stash), else
+    _anchor_chunks blocks (lo, hi).  out: the launch's term buffer when the term values are wanted from the same launches (one-pass forward).
+    Returns (terms, gs, gamma) summed over the blocks; terms is empty without `out`."""
+    L = _lib.lib()
+    M, A, nt = len(zs), s.A, len(zs) + 1
+    dev, st = sums.device, _stream()
+    slots = 1 + L.sga_loss_slots()
+    n_terms = nt + 2 * M if out is not None else 0
+    zz = torch.zeros((n_terms + nt * 8 + M,), device=dev, dtype=torch.float64)      # terms | gs | gamma: one fill
+    terms, gs, gam = zz[:n_terms], zz[n_terms:n_terms + nt * 8].view(nt, 8), zz[n_terms + nt * 8:]
+    if not walk:
+        return terms, gs, gam
+    jobs = walk if sym else [(lo, hi, 0, A, A) for lo, hi in walk]
+    gsc = torch.empty((slots + 1, nt, 8), device=dev, dtype=torch.float64)     # + one block: float copy of 1/(sums+eps)
+    gam2 = torch.empty((slots, M), device=dev, dtype=torch.float64)
+    fl = max(((jh - jl) + max(0, jh - mir)) * (hi - lo) for lo, hi, jl, jh, mir in jobs)
+    buf = [torch.empty((fl,), device=dev, dtype=torch.float32) for _ in range(M)]
+    zarr = _ptr_array(zs)
+    zop = zs if tier == 'plain' else zcs              # B operand of the fp32 stash products
+    for lo, hi, jl, jh, mir in jobs:
+        n1 = (jh - jl) * (hi - lo)
+        m1, m2 = [b[:n1] for b in buf], [b[n1:] for b in buf]
+        has2 = mir < jh
+        if sym:
+            _lib.check(L.sga_loss_anchor_multi_bwd_symx(zarr, M, _p(beta), A, _p(sums), alpha, TAU_ICL, TAU_IAL, _p(coef), _ptr_array(m1),
+                                                        _ptr_array(m2) if has2 else (_ct.c_void_p * M)(), _p(gsc), _p(gam2), lo, hi, jl, jh, mir,
+                                                        _p(out), st), 'sga_loss_anchor_multi_bwd_symx')
+        else:
+            _lib.check(L.sga_loss_anchor_multi_bwd(zarr, M, _p(beta), A, _p(sums), alpha, TAU_ICL, TAU_IAL, _p(coef), _ptr_array(m1), _p(gsc),
+                                                   _p(gam2), lo, hi, _p(out), st), 'sga_loss_anchor_multi_bwd')
+        if out is not None:
+            terms += out[:n_terms]
+        gs += gsc[0]
+        gam += gam2[0]
+        for k in range(M):
+            # dX1[i] = sum_j G[i,j] X2[j]  (M1 = G^T),  dX2[j] = sum_i G[i,j] X1[i]
+            if tier == 'planes' and _o.BF16X6_STASH:
+                # the four stash products on the sweeps' three exact bf16 planes (csrc/sweep3.hip: stash3_kernel)
+                _lib.check(L.sga_loss_stash_grad_symx_bf16x6(_p(m1[k]), _p(m2[k]) if has2 else None, _p(zbs[k]), A, s.J1, s.J2, _p(dzs[k]),
+                                                             lo, hi, jl, jh, mir, st), 'sga_loss_stash_grad_symx_bf16x6')
+            elif sym:
+                _lib.check(L.sga_loss_stash_grad_symx(_p(m1[k]), _p(m2[k]) if has2 else None, _p(zop[k]), A, 104, _p(dzs[k]), lo, hi, jl, jh, mir,
+                                                      st), 'sga_loss_stash_grad_symx')
+            else:
+                _lib.check(L.sga_loss_stash_grad(_p(m1[k]), _p(zop[k]), A, 104, _p(dzs[k]), lo, hi, st), 'sga_loss_stash_grad')
+    return terms, gs, gam
+
+
 class FusedContrastiveFn(torch.autograd.Function):
     """Same outputs as ContrastiveTermsFn for tables (E_1..E_M, joint) when joint == MultiModalFusion(E_1..E_M):
     the joint similarities are derived from the modality tiles (S_J = sum_m beta_m S_m), so the 300-d table is
-    never swept.  Inputs: beta [M] (= softmax(w)^2 / sum, differentiable), the M modality tables.
+    never swept.  Inputs: beta [M] (= softmax(w)^2 / sum, differentiable), the M modality tables (M = 2, 3, 4).
 
     Sharding (one process per GPU): `shard = (a_lo, a_hi)` is the anchor range this rank owns and `reduce` an in-place
     SUM all-reduce.  Each rank evaluates its shard's share of every global sum / loss term (all-reduced, so the
@@ -508,6 +534,11 @@ class FusedContrastiveFn(torch.autograd.Function):
         T = tables[0].shape[0]
         st = _stream()
         dp = 104
+        dmax = max(e.shape[1] for e in tables)          # real width: the K step that only covers zero padding is skipped
+        # The arithmetic of the sweeps and the stash products: three exact bf16 planes ('planes'), or in mode 'f32' fp32 MFMA over centred
+        # tables ('centred') -- both deliver the gradient in two parts and keep their bookkeeping in columns 100 and 101 -- or, for tables
+        # wider than 100 columns, fp32 MFMA over the plain tables ('plain').
+        tier = 'plain' if dmax > 100 else 'centred' if get_mfma_mode() == 'f32' else 'planes'
         zs, nrms = [], []
         poison = torch.zeros((1,), device=dev, dtype=torch.float32)
         for k, e in enumerate(tables):
@@ -523,12 +554,9 @@ class FusedContrastiveFn(torch.autograd.Function):
         zarr = _ptr_array(zs)
         slots = 1 + L.sga_loss_slots()
         sums = torch.empty((slots, nt, 8), device=dev, dtype=torch.float64)
-        dmax = max(e.shape[1] for e in tables)          # real width: the K step that only covers zero padding is skipped
         zbs, zcs = [], []
-        split3 = centred32 = False
-        if M in (2, 3, 4) and dmax <= 100 and _o.FUSED_ANCHOR_BWD and get_mfma_mode() in ('bf16x6', 'f16'):
+        if tier == 'planes':
             # three exact bf16 planes per table (csrc/sweep3.hip): blocked h / m / l planes of the centred rows, once per step
-            split3 = True
             nb = L.sga_loss_split3_bytes(s.A, s.J1, s.J2)
             for z in zs:
                 zb = torch.empty((nb,), device=dev, dtype=torch.uint8)
@@ -538,19 +566,13 @@ class FusedContrastiveFn(torch.autograd.Function):
                 zc[2 * s.A:].zero_()
                 _lib.check(L.sga_loss_split3_tables(_p(z), s.A, s.J1, s.J2, _p(zb), _p(zc), st), 'sga_loss_split3_tables')
                 zbs.append(zb); zcs.append(zc)
-            ev = None
-            if _o.KERNEL_EVENTS is not None:
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                ev[0].record()
+            ev = _ev_start()
             lite = _sums_lite(a_hi - a_lo, s.J1, s.J2)
             _lib.check(L.sga_loss_multi_sums_bf16x6(_ptr_array(zbs), M, _p(beta), s.A, s.J1, s.J2, TAU_ICL, TAU_IAL, _p(sums),
                                                     a_lo, a_hi, 1 if lite else 0, st), 'sga_loss_multi_sums_bf16x6')
-            if ev is not None:
-                ev[1].record()
-                _o.KERNEL_EVENTS.setdefault('loss_multi_sums_bf16x6', []).append(ev + ((a_hi - a_lo, s.A, s.J1, s.J2, M, bool(lite)),))
-        elif M in (2, 3, 4) and dmax <= 100 and _o.FUSED_ANCHOR_BWD and _o.CENTRED_F32:
+            _ev_stop(ev, 'loss_multi_sums_bf16x6', (a_hi - a_lo, s.A, s.J1, s.J2, M, bool(lite)))
+        elif tier == 'centred':
             # fp32-MFMA sweeps over the centred fp32 tables (z - zbar | b | 1): the gradient in the same two parts as the three-plane sweeps
-            centred32 = True
             nst = int(L.sga_loss_centre_bytes())
             for z in zs:
                 zc = torch.empty((s.R + 32, dp), device=dev, dtype=torch.float32)
@@ -558,125 +580,58 @@ class FusedContrastiveFn(torch.autograd.Function):
                 stw = torch.empty((nst,), device=dev, dtype=torch.uint8)
                 _lib.check(L.sga_loss_centre_tables(_p(z), s.A, s.J1, s.J2, _p(zc), _p(stw), st), 'sga_loss_centre_tables')
                 zbs.append(stw); zcs.append(zc)
-            ev = None
-            if _o.KERNEL_EVENTS is not None:
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                ev[0].record()
+            ev = _ev_start()
             _lib.check(L.sga_loss_multi_sums_centred(_ptr_array(zcs), M, _p(beta), s.A, s.J1, s.J2, TAU_ICL, TAU_IAL, _p(sums), a_lo, a_hi, st),
                        'sga_loss_multi_sums_centred')
-            if ev is not None:
-                ev[1].record()
-                _o.KERNEL_EVENTS.setdefault('loss_multi_sums', []).append(ev + ((a_hi - a_lo, s.A, s.J1, s.J2, M),))
+            _ev_stop(ev, 'loss_multi_sums', (a_hi - a_lo, s.A, s.J1, s.J2, M))
         else:
-            ev = None
-            if _o.KERNEL_EVENTS is not None:
-                ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                ev[0].record()
+            ev = _ev_start()
             _lib.check(L.sga_loss_multi_sums(zarr, M, dmax, _p(beta), s.A, s.J1, s.J2, TAU_ICL, TAU_IAL, _p(sums), a_lo, a_hi, st),
                        'sga_loss_multi_sums')
-            if ev is not None:
-                ev[1].record()
-                _o.KERNEL_EVENTS.setdefault('loss_multi_sums', []).append(ev + ((a_hi - a_lo, s.A, s.J1, s.J2, M),))
+            _ev_stop(ev, 'loss_multi_sums', (a_hi - a_lo, s.A, s.J1, s.J2, M))
         sums = _allreduce_sum(sums[0].contiguous(), reduce)
-        zj = torch.empty((2 * s.A, M * dp), device=dev, dtype=torch.float32)
-        _lib.check(L.sga_loss_build_joint(zarr, M, _p(beta), 2 * s.A, _p(zj), st), 'sga_loss_build_joint')
         out = torch.empty((slots * (nt + 2 * M),), device=dev, dtype=torch.float64)
-        dps = [dp] * M + [M * dp]
-        onepass = coef_hint is not None and M <= 4 and _o.FUSED_ANCHOR_BWD and _o.FUSED_AA_ONEPASS and s.A >= _o.ONEPASS_MIN_ANCHORS
+        onepass = coef_hint is not None and _o.FUSED_AA_ONEPASS and s.A >= _o.ONEPASS_MIN_ANCHORS
         extra = []
         if onepass:
             # ONE pass over the anchors x anchors similarities: dL/d(terms) is known (coef_hint), so the backward kernel runs now, block
             # by block on the bounded stash, and returns the term values of its rows as well; backward() starts from the saved A x A
             # gradients and only has the negatives' sweep left.
             coef = _req(coef_hint.contiguous(), 'coef_hint')
-            n_terms = nt + 2 * M
             dz_all = torch.zeros((M, s.R, dp), device=dev, dtype=torch.float32)
-            zz = torch.zeros((n_terms + nt * 8 + M,), device=dev, dtype=torch.float64)      # terms | gs | gamma: one fill
-            out_acc, gs_aa, gam_aa = zz[:n_terms], zz[n_terms:n_terms + nt * 8].view(nt, 8), zz[n_terms + nt * 8:]
             # symmetric walk: one GPU, or every rank of an anchor-sharded job when the caller passed all ranks' cuts (on 32-row boundaries)
             cuts, crank = (shard[2], shard[3]) if (shard is not None and len(shard) >= 4) else (([0, s.A], 0) if (a_lo == 0 and a_hi == s.A) else (None, 0))
-            sym = _o.AA_SYMMETRIC and M <= _o.AA_SYMMETRIC_MAX_M and cuts is not None and all(c % 32 == 0 for c in cuts[:-1]) and cuts[-1] == s.A \
+            sym = _o.AA_SYMMETRIC and cuts is not None and all(c % 32 == 0 for c in cuts[:-1]) and cuts[-1] == s.A \
                 and cuts[crank] == a_lo and cuts[crank + 1] == a_hi
-            jobs = _sym_jobs(list(cuts), crank, M) if sym else []
-            chunks = jobs if sym else _anchor_chunks(a_lo, a_hi, s.A, M)
-            if sym and len(cuts) == 2 and len(jobs) < 2:             # one block = one diagonal square: nothing to mirror, the ordered kernel (unmasked interior) does it
-                sym, chunks = False, _anchor_chunks(a_lo, a_hi, s.A, M)
-            if chunks:
-                gsc = torch.empty((slots + 1, nt, 8), device=dev, dtype=torch.float64)
-                gam2 = torch.empty((slots, M), device=dev, dtype=torch.float64)
-            if chunks and sym:
-                # every unordered anchor pair once over all ranks: a launch also evaluates the mirrored elements from column `mir` on (second stash)
-                fl = max(((jh - jl) + max(0, jh - mir)) * (hi - lo) for lo, hi, jl, jh, mir in chunks)
-                buf = [torch.empty((fl,), device=dev, dtype=torch.float32) for _ in range(M)]
-                for lo, hi, jl, jh, mir in chunks:
-                    n1 = (jh - jl) * (hi - lo)
-                    m1 = [b[:n1] for b in buf]
-                    m2 = [b[n1:] for b in buf]
-                    has2 = mir < jh
-                    _lib.check(L.sga_loss_anchor_multi_bwd_symx(zarr, M, _p(beta), s.A, _p(sums), float(alpha), TAU_ICL, TAU_IAL, _p(coef),
-                                     _ptr_array(m1), _ptr_array(m2) if has2 else (_ct.c_void_p * M)(), _p(gsc), _p(gam2),
-                                     lo, hi, jl, jh, mir, _p(out), st), 'sga_loss_anchor_multi_bwd_symx')
-                    out_acc += out[:n_terms]
-                    gs_aa += gsc[0]
-                    gam_aa += gam2[0]
-                    for k in range(M):
-                        if split3 and _o.BF16X6_STASH:
-                            # the four stash products on the sweeps' three exact bf16 planes (csrc/sweep3.hip: stash3_kernel)
-                            _lib.check(L.sga_loss_stash_grad_symx_bf16x6(_p(m1[k]), _p(m2[k]) if has2 else None, _p(zbs[k]), s.A, s.J1, s.J2,
-                                                                         _p(dz_all[k]), lo, hi, jl, jh, mir, st), 'sga_loss_stash_grad_symx_bf16x6')
-                        else:
-                            _lib.check(L.sga_loss_stash_grad_symx(_p(m1[k]), _p(m2[k]) if has2 else None, _p(zcs[k] if (split3 or centred32) else zs[k]), s.A, dp,
-                                                                  _p(dz_all[k]), lo, hi, jl, jh, mir, st), 'sga_loss_stash_grad_symx')
-                del buf, m1, m2
-            elif chunks:
-                cmax = max(hi - lo for lo, hi in chunks)
-                m1 = [torch.empty((s.A * cmax,), device=dev, dtype=torch.float32) for _ in range(M)]
-                for lo, hi in chunks:
-                    _lib.check(L.sga_loss_anchor_multi_bwd(zarr, M, _p(beta), s.A, _p(sums), float(alpha), TAU_ICL, TAU_IAL, _p(coef),
-                                                           _ptr_array(m1), _p(gsc), _p(gam2), lo, hi, _p(out), st), 'sga_loss_anchor_multi_bwd')
-                    out_acc += out[:n_terms]
-                    gs_aa += gsc[0]
-                    gam_aa += gam2[0]
-                    for k in range(M):
-                        if split3 and _o.BF16X6_STASH:
-                            _lib.check(L.sga_loss_stash_grad_symx_bf16x6(_p(m1[k]), None, _p(zbs[k]), s.A, s.J1, s.J2, _p(dz_all[k]), lo, hi, 0, s.A, s.A, st),
-                                       'sga_loss_stash_grad_symx_bf16x6')
-                        else:
-                            _lib.check(L.sga_loss_stash_grad(_p(m1[k]), _p(zcs[k] if (split3 or centred32) else zs[k]), s.A, dp, _p(dz_all[k]), lo, hi, st), 'sga_loss_stash_grad')
-                del m1
-            out = _allreduce_sum(out_acc.clone(), reduce)
+            walk = _sym_jobs(list(cuts), crank, M) if sym else []
+            if sym and len(cuts) == 2 and len(walk) < 2:             # one block = one diagonal square: nothing to mirror, the ordered kernel (unmasked interior) does it
+                sym = False
+            if not sym:
+                walk = _anchor_chunks(a_lo, a_hi, s.A, M)
+            terms, gs_aa, gam_aa = _aa_walk(s, zs, zbs, zcs, tier, beta, sums, float(alpha), coef, dz_all, walk, sym, out=out)
+            out = _allreduce_sum(terms.clone(), reduce)
             extra = [dz_all, gs_aa.clone(), gam_aa.clone(), coef]
         else:
-            if M <= 4 and _o.FUSED_ANCHOR_FWD:      # joint similarities derived in registers, I block resident in LDS
-                _lib.check(L.sga_loss_anchor_multi_fwd(zarr, M, _p(beta), s.A, _p(sums), float(alpha), TAU_ICL, TAU_IAL, _p(out),
-                                                       a_lo, a_hi, st), 'sga_loss_anchor_multi_fwd')
-            else:
-                _lib.check(L.sga_loss_anchor_fwd(_ptr_array(zs + [zj]), (_ct.c_int * nt)(*dps), nt, s.A, _p(sums), float(alpha),
-                                                 TAU_ICL, TAU_IAL, _p(out), a_lo, a_hi, st), 'sga_loss_anchor_fwd')
+            # joint similarities derived in registers, I block resident in LDS
+            _lib.check(L.sga_loss_anchor_multi_fwd(zarr, M, _p(beta), s.A, _p(sums), float(alpha), TAU_ICL, TAU_IAL, _p(out),
+                                                   a_lo, a_hi, st), 'sga_loss_anchor_multi_fwd')
             out = _allreduce_sum(out[:nt + 2 * M].contiguous(), reduce)
         ctx.s, ctx.alpha, ctx.M, ctx.shard, ctx.reduce = s, float(alpha), M, (a_lo, a_hi), reduce
         ctx.shapes = [tuple(t.shape) for t in tables]
-        ctx.n_zb = len(zbs)
-        ctx.split3 = split3
-        ctx.centred32 = centred32
+        ctx.tier = tier
         ctx.onepass = onepass
-        ctx.n_zc = len(zcs)
-        ctx.save_for_backward(sums, beta, zj, *zs, *nrms, *zbs, *zcs, *extra)
+        ctx.save_for_backward(sums, beta, *zs, *nrms, *zbs, *zcs, *extra)
         return out.float() + poison
 
     @staticmethod
     def backward(ctx, gout):
         L = _lib.lib()
-        s, M = ctx.s, ctx.M
+        s, M, tier = ctx.s, ctx.M, ctx.tier
         a_lo, a_hi = ctx.shard
         ns = a_hi - a_lo
-        nt = M + 1
-        sums, beta, zj, *rest = ctx.saved_tensors
-        onepass_saved = None
-        if ctx.onepass:
-            rest, onepass_saved = rest[:-4], rest[-4:]
-        zs, nrms, zbs = rest[:M], rest[M:2 * M], rest[2 * M:2 * M + ctx.n_zb]
-        zcs = rest[2 * M + ctx.n_zb:]
+        sums, beta, *rest = ctx.saved_tensors
+        nb = 0 if tier == 'plain' else M
+        zs, nrms, zbs, zcs = rest[:M], rest[M:2 * M], rest[2 * M:2 * M + nb], rest[2 * M + nb:2 * M + 2 * nb]
         dev = sums.device
         st = _stream()
         dp = 104
@@ -684,12 +639,12 @@ class FusedContrastiveFn(torch.autograd.Function):
         coef = gout.contiguous().float()
         slots = 1 + L.sga_loss_slots()
         gam_neg = torch.empty((slots, M), device=dev, dtype=torch.float64)   # dL/dbeta via the negatives (zeroed by the callee)
-        if onepass_saved is not None:
+        if ctx.onepass:
             # The A x A part was done in forward() for coef_hint; everything it produced is linear in dL/d(terms), so an upstream factor
             # (loss / k, loss * w) is applied here: u = <gout, hint> / <hint, hint>.  A gout that is NOT a multiple of the hint (a caller
             # who backpropagates one of the returned components alone, or re-weights them) cannot be served from the saved gradients:
             # that is detected on the device and raised at the next batch (deferred, no host sync) -- set ops.FUSED_AA_ONEPASS = False.
-            dz_aa, gs_aa, gam_aa, hint = onepass_saved
+            dz_aa, gs_aa, gam_aa, hint = rest[2 * M + 2 * nb:]
             hh = torch.dot(hint, hint)
             u = torch.dot(coef, hint) / hh
             # Always (_o.VALIDATE or not), on the device and without a host sync: a mismatching gradient POISONS what this node returns --
@@ -706,94 +661,38 @@ class FusedContrastiveFn(torch.autograd.Function):
             dzs = [dz_all[k] for k in range(M)]
             gs = _allreduce_sum(gs_aa * u, ctx.reduce)
             gam_anc = gam_aa * u
-            chunks = []
         else:
             dz_all = torch.zeros((M, s.R, dp), device=dev, dtype=torch.float32)      # one fill for the M accumulation targets
             dzs = [dz_all[k] for k in range(M)]
-            gam_anc = torch.zeros((M,), device=dev, dtype=torch.float64)         # ... via the anchors x anchors terms
-        # The anchors x anchors backward runs one anchor-row block [lo, hi) at a time: the kernel writes the block's
-        # transposed coefficient stash M1[m] [A, hi-lo], two GEMMs turn it into dX1 / dX2, the next block reuses the
-        # buffers -- memory O(A*D + _o.STASH_BYTES), never A x A (nothing of that size at configs[2]).
-        fused = M <= 4 and _o.FUSED_ANCHOR_BWD
-        ntab = M if fused else nt
-        if onepass_saved is None:
-            chunks = _anchor_chunks(a_lo, a_hi, A, ntab)
-            zz = torch.zeros((nt * 8 + M,), device=dev, dtype=torch.float64)              # gs and gam_acc: one fill
-            gs = zz[:nt * 8].view(nt, 8)
-        if onepass_saved is not None:
-            pass                                                                       # nothing of the A x A part is left to do
-        elif fused:
-            gsc = torch.empty((slots + 1, nt, 8), device=dev, dtype=torch.float64)     # + one block: float copy of 1/(sums+eps)
-            gam2 = torch.empty((slots, M), device=dev, dtype=torch.float64)
-            gam_acc = zz[nt * 8:]
-        else:
-            gsc = torch.empty((slots, nt, 8), device=dev, dtype=torch.float64)
-            dps = [dp] * M + [M * dp]
-            dzj = torch.zeros((2 * A, M * dp), device=dev, dtype=torch.float32) if chunks else None
-        if chunks:
-            cmax = max(hi - lo for lo, hi in chunks)
-            m1 = [torch.empty((A * cmax,), device=dev, dtype=torch.float32) for _ in range(ntab)]
-        for lo, hi in chunks:
-            if fused:
-                # M1[m] already holds dL/dS_m + beta_m dL/dS_J, dL/dbeta comes out directly; no joint operand / stash
-                _lib.check(L.sga_loss_anchor_multi_bwd(_ptr_array(zs), M, _p(beta), A, _p(sums), ctx.alpha, TAU_ICL, TAU_IAL, _p(coef),
-                                                       _ptr_array(m1), _p(gsc), _p(gam2), lo, hi, None, st), 'sga_loss_anchor_multi_bwd')
-                gam_acc += gam2[0]
-            else:
-                _lib.check(L.sga_loss_anchor_bwd(_ptr_array(list(zs) + [zj]), (_ct.c_int * nt)(*dps), nt, A, _p(sums), ctx.alpha,
-                                                 TAU_ICL, TAU_IAL, _p(coef), _ptr_array(m1), _p(gsc), lo, hi, st), 'sga_loss_anchor_bwd')
-                _lib.check(L.sga_loss_stash_grad(_p(m1[M]), _p(zj), A, M * dp, _p(dzj), lo, hi, st), 'sga_loss_stash_grad')
-            gs += gsc[0]
-            for k in range(M):
-                if ctx.split3 and _o.BF16X6_STASH:
-                    _lib.check(L.sga_loss_stash_grad_symx_bf16x6(_p(m1[k]), None, _p(zbs[k]), A, s.J1, s.J2, _p(dzs[k]), lo, hi, 0, A, A, st),
-                               'sga_loss_stash_grad_symx_bf16x6')
-                else:
-                    _lib.check(L.sga_loss_stash_grad(_p(m1[k]), _p(zcs[k] if (ctx.split3 or ctx.centred32) else zs[k]), A, dp, _p(dzs[k]), lo, hi, st), 'sga_loss_stash_grad')
-        if chunks:
-            del m1
-            if fused:
-                gam_anc = gam_acc
-            else:
-                gam_sq = torch.zeros((M,), device=dev, dtype=torch.float64)
-                _lib.check(L.sga_loss_fold_joint(_ptr_array(zs), M, _p(beta), _p(dzj), 2 * A, _ptr_array(dzs), _p(gam_sq), st),
-                           'sga_loss_fold_joint')
-                gam_anc = gam_sq / (2.0 * torch.sqrt(beta.double()))     # through sqrt(beta_m) in the anchor rows of ZJ
-                del dzj
-        if onepass_saved is None:
+            _, gs, gam_anc = _aa_walk(s, zs, zbs, zcs, tier, beta, sums, ctx.alpha, coef, dzs, _anchor_chunks(a_lo, a_hi, A, M), False)
             gs = _allreduce_sum(gs, ctx.reduce)                          # dL/d(global sums) needs every shard's tiles
-        ev = None
-        if _o.KERNEL_EVENTS is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        if ctx.n_zb and ctx.split3:           # the forward ran in bf16x6 mode: its blocked bf16 h / m / l planes are there
+        ev = _ev_start()
+        if tier == 'planes':                  # the forward's blocked bf16 h / m / l planes
             _lib.check(L.sga_loss_multi_grad_bf16x6(_ptr_array(zbs), M, _p(beta), A, s.J1, s.J2, TAU_ICL, TAU_IAL, _p(gs), _ptr_array(dzs),
                                                     _p(gam_neg), a_lo, a_hi, st), 'sga_loss_multi_grad_bf16x6')
-        elif ctx.centred32:                   # fp32 MFMA over the centred fp32 tables
+        elif tier == 'centred':               # fp32 MFMA over the centred fp32 tables
             _lib.check(L.sga_loss_multi_grad_centred(_ptr_array(zcs), M, _p(beta), A, s.J1, s.J2, TAU_ICL, TAU_IAL, _p(gs), _ptr_array(dzs),
                                                      _p(gam_neg), a_lo, a_hi, st), 'sga_loss_multi_grad_centred')
         else:
             _lib.check(L.sga_loss_multi_grad(_ptr_array(zs), M, max(d for _, d in ctx.shapes), _p(beta), A, s.J1, s.J2, TAU_ICL, TAU_IAL, _p(gs), _ptr_array(dzs),
                                              _p(gam_neg), a_lo, a_hi, st), 'sga_loss_multi_grad')
-        if ev is not None:
-            ev[1].record()
-            _o.KERNEL_EVENTS.setdefault('loss_multi_grad_bf16x6' if ctx.split3 else 'loss_multi_grad', []).append(ev + ((ns, A, s.J1, s.J2, M),))
+        _ev_stop(ev, 'loss_multi_grad_bf16x6' if tier == 'planes' else 'loss_multi_grad', (ns, A, s.J1, s.J2, M))
         grads = []
         same = all(sh == ctx.shapes[0] for sh in ctx.shapes)
         de_all = torch.zeros((M,) + tuple(ctx.shapes[0]), device=dev, dtype=torch.float32) if same else None   # one fill
         for k in range(M):
             t, d = ctx.shapes[k]
             de = de_all[k] if same else torch.zeros((t, d), device=dev, dtype=torch.float32)
-            if ctx.n_zb and ctx.split3:       # the gradient is in two parts (sum c (z - zbar) | sum c): projected without forming their sum
+            if tier == 'planes':              # the gradient is in two parts (sum c (z - zbar) | sum c): projected without forming their sum
                 _lib.check(L.sga_loss_scatter_tangent(_p(dzs[k]), _p(zs[k]), _p(nrms[k]), _p(s.idx), A, s.J1, s.J2, d, _p(zbs[k]), _p(de), st),
                            'sga_loss_scatter_tangent')
-            elif ctx.centred32:
+            elif tier == 'centred':
                 _lib.check(L.sga_loss_scatter_tangent_stat(_p(dzs[k]), _p(zs[k]), _p(nrms[k]), _p(s.idx), s.R, d, _p(zbs[k]), _p(de), st),
                            'sga_loss_scatter_tangent_stat')
             else:
                 _lib.check(L.sga_loss_scatter(_p(dzs[k]), _p(zs[k]), _p(nrms[k]), _p(s.idx), s.R, d, dp, _p(de), st), 'sga_loss_scatter')
             grads.append(de)
-        # d/dbeta_m: through the negatives (gamma) + through sqrt(beta_m) in the anchor rows of ZJ
+        # d/dbeta_m: through the negatives (gamma) + through the anchors x anchors terms
         gbeta = (gam_neg[0] + gam_anc).float()
         return (None, None, None, None, None, gbeta, *grads)
 

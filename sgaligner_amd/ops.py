@@ -53,8 +53,8 @@ if _MODE not in MFMA_MODES:
 
 def set_mfma_mode(mode: str) -> str:
     """Arithmetic of the MFMA kernels that have more than one variant.
-    'f32': fp32 MFMA everywhere (v_mfma_f32_*_f32); the fused loss sweeps run over centred fp32 tables and deliver the gradient in the
-    same two parts as the default (CENTRED_F32).
+    'f32': fp32 MFMA everywhere (v_mfma_f32_*_f32); the fused loss sweeps (emb_dim <= 100) run over centred fp32 tables and deliver the
+    gradient in the same two parts as the default.
     'bf16x6' (THE DEFAULT): the fused 100-d loss sweeps (anchors x negatives: forward sums + gradient) with every fp32 operand split EXACTLY into three
     bf16 terms (8 + 8 + 8 significand bits, fp32's exponent range) and six bf16 MFMAs per product into one fp32 accumulator -- fp32
     arithmetic on the exact operands at 6/16 of the fp32 MFMA's matrix time (csrc/sweep3.hip; SURVEY 7 "fp32 MFMA or split-bf16 x3");
@@ -393,16 +393,12 @@ class IndexSets:
         return IndexSets._cache.get(key, lambda: IndexSets(data_dict, device, n_rows))
 
 
-FUSED_ANCHOR_BWD = True
-CENTRED_F32 = True        # 'f32' mode, fused joint path, emb_dim <= 100: fp32-MFMA sweeps over centred tables, gradient in two parts (tests flip it to compare)
 FUSED_AA_ONEPASS = True      # training: A x A terms + gradients from one pass in forward() when the loss head announces dL/d(terms)
 # One-pass mode: walk the anchors x anchors pairs SYMMETRICALLY -- a block evaluates (i, j) and (j, i) from the same two similarities, every
 # unordered pair once (sga_loss_anchor_multi_bwd_sym: -34 % per ordered pair, tools/bench_aa.py); across ranks by _sym_jobs.
 AA_SYMMETRIC = True
-AA_SYMMETRIC_MAX_M = int(_os.environ.get('SGA_AA_SYM_MAX_M', '4'))     # tools flip this to 3 to time M = 4 on the ordered walk
 ONEPASS_MIN_ANCHORS = 256    # below this the A x A work is negligible and the saved gradients' bookkeeping is not worth its launches
 WIDE_STASH = True         # tables wider than 128 columns: coefficient stash + GEMMs instead of the multi-pass gradient sweep (tests flip it)
-FUSED_ANCHOR_FWD = True   # tests flip this to cross-check the two anchors x anchors forward kernels
 KERNEL_EVENTS = None   # bench.py sets this to {} to time the dominant kernel with HIP events on the launch stream
 
 def _default_stash_bytes():

@@ -30,10 +30,7 @@ def pointnet_forward(x_tp3, w1, b1, w2, b2, w3, b3, want_argmax: bool, bn_sums=N
     C3 = w3.shape[0]
     y = torch.empty((T, C3), device=x_tp3.device, dtype=torch.float32)
     am = torch.empty((T, C3), device=x_tp3.device, dtype=torch.int32) if want_argmax else None
-    ev = None
-    if _o.KERNEL_EVENTS is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
+    ev = _ev_start()
     L = _lib.lib()
     ws, ws_bytes = None, 0
     if 0 < T <= _o.POINTNET_SPLIT_MAX_OBJECTS:      # few objects: split every object over a workgroup's 8 waves (needs a partials buffer)
@@ -55,11 +52,8 @@ def pointnet_forward(x_tp3, w1, b1, w2, b2, w3, b3, want_argmax: bool, bn_sums=N
         rc = L.sga_pointnet_fwd_ws(_p(x_tp3), _p(w1), _p(b1), _p(w2), _p(b2), _p(w3), _p(b3), _p(y), _p(am),
                                    T, P, C3, _p(ws), ws_bytes, _POINTNET_MODE[get_mfma_mode()], _stream())
         _lib.check(rc, 'sga_pointnet_fwd')
-    if ev is not None:
-        ev[1].record()
-        pm = _POINTNET_MODE[get_mfma_mode()]
-        _o.KERNEL_EVENTS.setdefault('pointnet_fwd_kernel', []).append(ev + ((T, P, w1.shape[0], w2.shape[0], C3, 'bf16x6' if pm == 4 else 'f32',
-                                                                          bn_sums is not None),))
+    _ev_stop(ev, 'pointnet_fwd_kernel', (T, P, w1.shape[0], w2.shape[0], C3, 'bf16x6' if _POINTNET_MODE[get_mfma_mode()] == 4 else 'f32',
+                                         bn_sums is not None))
     return y, am
 
 

@@ -93,7 +93,7 @@ def test_headline_loss_gradient_vs_fp64(pairs):
     torch.cuda.empty_cache()
     dd = make_batch_fast(pairs, 128, 512, seed=44, device='cuda')
     steps = AlignerSteps(mods, device='cuda', seed=42)
-    assert ops.get_mfma_mode() == ops.DEFAULT_MFMA_MODE == 'bf16x6' and ops.FUSED_AA_ONEPASS and ops.AA_SYMMETRIC and ops.CENTRED_F32
+    assert ops.get_mfma_mode() == ops.DEFAULT_MFMA_MODE == 'bf16x6' and ops.FUSED_AA_ONEPASS and ops.AA_SYMMETRIC
     ops.DEFERRED_CHECKS.flush()
     res = {'bf16x6': _step(steps, dd, mods)}                            # the default path: one-pass + symmetric walk + sweep3
     res['bf16x6_rerun'] = _step(steps, dd, mods)
