@@ -83,6 +83,33 @@ int sga_colsum(const float* X, long ld, int M, int N, float* out, int accumulate
 int sga_gemm_bnstats(int M, int N, int K, const float* A, long lda, const float* B, long ldb, float* C, long ldc, const float* bias,
                      double* sums, void* stream);
 int sga_cast_f64_f32(const double* in, float* out, size_t n, void* stream);                        /* .float(), sg_aligner.py:73-75 */
+/* Which kernel a GEMM call takes -- the launcher's own decision, for tests that must know what they ran and for callers sizing a batch.  Host
+ * only: with ncu > 0 (the CU count to plan for) no device is touched; ncu = 0 asks the current device.  a_aligned16 / b_aligned16: the operand
+ * pointer is a multiple of 16 bytes.  accumulate / has_bias / has_resid / has_colstats (sga_gemm_bnstats) / act as the call would pass them.
+ * route: one of sga_gemm_route; splits: workgroups along K (> 1: fp32 atomics into C, not run-to-run bit-stable); k_per_split: K rows of each.
+ * SGA_GEMM_REFUSED (sga_gemm_bnstats on a shape the NT kernels do not take) still returns SGA_OK here; the launch returns SGA_ERR_ARG.
+ * Row-chunk invariance: for K < 4096 the route of C = act(A B^T + bias) (+ resid) is a function of (N, K, alignment) and of M only through the
+ * NT tile height (64 | 128 rows, equal bits), so a batch walked in chunks of rows gets the bits of the unchunked call; from K = 4096 on a call
+ * of few rows is split over K (atomics) and that does not hold. */
+enum sga_gemm_route {
+    SGA_GEMM_EMPTY = 0,
+    SGA_GEMM_TN_NARROW,
+    SGA_GEMM_TN_SPLIT,
+    SGA_GEMM_TN_BIG,
+    SGA_GEMM_NN,
+    SGA_GEMM_NT_128,
+    SGA_GEMM_NT_64,
+    SGA_GEMM_NT3_128,
+    SGA_GEMM_NT3_64,
+    SGA_GEMM_SMALL_F32,
+    SGA_GEMM_SMALL_F64,
+    SGA_GEMM_GENERIC_F32,
+    SGA_GEMM_GENERIC_F64,
+    SGA_GEMM_REFUSED
+};
+int sga_gemm_plan(int transA, int transB, int M, int N, int K, long lda, long ldb, long ldc, long ldr, int a_is_f64, int a_aligned16,
+                  int b_aligned16, int has_bias, int accumulate, int act, int has_resid, int has_colstats, int ncu, int* route, int* splits,
+                  int* k_per_split);
 
 /* ---- modality fusion --------------------------------------------------------------------------------
  * replaces MultiModalFusion.forward, src/aligner/sg_aligner.py:30-35:

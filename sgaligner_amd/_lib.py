@@ -69,6 +69,7 @@ SIGNATURES = {
     'sga_colsum': (I, [P, c_long, I, I, P, I, P]),
     'sga_gemm_bnstats': (I, [I, I, I, P, c_long, P, c_long, P, c_long, P, P, P]),
     'sga_cast_f64_f32': (I, [P, P, c_size_t, P]),
+    'sga_gemm_plan': (I, [I, I, I, I, I, c_long, c_long, c_long, c_long] + [I] * 9 + [P, P, P]),
     'sga_loss_gather': (I, [P, I, I, P, I, P, I, P, P]),
     'sga_loss_scatter': (I, [P, P, P, P, I, I, I, P, P]),
     'sga_loss_neg_sums': (I, [P, I, I, I, I, F, F, P, P]),
@@ -108,6 +109,10 @@ SIGNATURES = {
     'sga_fusion_bwd_workspace_bytes': (c_size_t, [I]),
     'sga_fusion_bwd': (I, [P, I, P, P, P, P, I, I, P, c_size_t, P]),
 }
+
+# enum sga_gemm_route, in the header's order (sga_gemm_plan's `route`)
+GEMM_ROUTES = ('EMPTY', 'TN_NARROW', 'TN_SPLIT', 'TN_BIG', 'NN', 'NT_128', 'NT_64', 'NT3_128', 'NT3_64', 'SMALL_F32', 'SMALL_F64',
+               'GENERIC_F32', 'GENERIC_F64', 'REFUSED')
 
 
 class SgaLibraryError(RuntimeError):

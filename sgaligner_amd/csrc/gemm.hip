@@ -572,50 +572,54 @@ extern "C" int sga_cast_f64_f32(const double* in, float* out, size_t n, void* st
     return SGA_OK;
 }
 
-static int gemm_launch(int transA, int transB, int M, int N, int K, const void* A, long lda, int a_is_f64,
-                       const float* B, long ldb, float* C, long ldc, const float* bias, int accumulate,
-                       int act, const float* resid, long ldr, void* stream, double* colstats = nullptr) {
+// The dispatch decision of gemm_launch, on its own so that sga_gemm_plan can report it: every condition that chooses a kernel lives here and
+// nowhere else.  Touches no device unless ncu <= 0 (then the CU count is asked for).  a_al16 / b_al16: the operand POINTER is 16-byte aligned
+// (the leading dimension's share of the alignment rule is checked here).
+struct GemmPlan { int route, splits, kper; };
+
+static int gemm_plan(int transA, int transB, int M, int N, int K, long lda, long ldb, long ldc, long ldr, int a_is_f64, int a_al16, int b_al16,
+                     int has_bias, int accumulate, int act, int has_resid, int has_colstats, int ncu, GemmPlan* p) {
+    (void)accumulate;                                    // part of the call's description; no route depends on it (it only decides who zeroes C)
+    p->route = SGA_GEMM_REFUSED; p->splits = 1; p->kper = 0;
     SGA_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "sga_gemm: negative size");
     // the NT kernel's arithmetic: three exact bf16 planes (gemm_nt3_kernel; fp32-faithful, 6/16 of the fp32 MFMA's matrix time) from K = 256 on
     // -- measured at 163 840 / 40 960 rows (tools/bench_gemm.py): K = 512 -> N = 1024 0.458 -> 0.306 ms, 1024 -> 512 0.407 -> 0.345, 512 -> 256
     // 0.434 -> 0.331, 256 -> 100 0.128 -> 0.121; K = 128 layers are four chunks per tile (latency, not matrix time: 0.080 -> 0.078) and at K = 64 the
     // kernel's 61 KiB of LDS planes cost more occupancy than the MFMAs save (0.054 -> 0.074) -- below 256 the fp32 MFMA kernel stays.  A function of K
-    // only, never of M: a batch walked in chunks of rows gets the same bits as the unchunked call.  -DSGA_GEMM_NT_FP32: fp32 MFMA everywhere
-    // (the A/B of tools/build_variant.sh).
+    // only, never of M: for K < 4096 a batch walked in chunks of rows gets the same bits as the unchunked call (the 64-row and the 128-row tiles
+    // of a kernel give equal bits; tests/test_gemm_routes_gpu.py).  From K = 4096 on the split-K rule below looks at the output grid, so a call of
+    // few rows takes the atomic generic kernel and one of many rows the NT kernel: no such promise there (no layer of the product is that deep).
+    // -DSGA_GEMM_NT_FP32: fp32 MFMA everywhere (the A/B of tools/build_variant.sh).
 #ifdef SGA_GEMM_NT_FP32
     const bool nt3 = false;
 #else
     const bool nt3 = K >= 256;
 #endif
     SGA_CHECK_ARG(act >= 0 && act <= 2, "sga_gemm_ex: act=%d (0 none, 1 relu, 2 leaky-relu 0.2)", act);
-    if (M == 0 || N == 0) return SGA_OK;                 // empty output (a zero-row shard): nothing to do, null pointers allowed
-    SGA_CHECK_ARG(C && (K == 0 || (A && B)), "sga_gemm: null pointer");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (transA && !transB && N <= 8 && K >= 64 && !a_is_f64 && !bias && act == 0 && !resid && !colstats) {
+    if (M == 0 || N == 0) { p->route = SGA_GEMM_EMPTY; return SGA_OK; }     // empty output (a zero-row shard): nothing to do, null pointers allowed
+    if (ncu <= 0) ncu = sga_num_cus();
+    if (transA && !transB && N <= 8 && K >= 64 && !a_is_f64 && !has_bias && act == 0 && !has_resid && !has_colstats) {
         // narrow weight gradient (a function of the shape class only): memory-bound walk over A
-        if (!accumulate && hipMemset2DAsync(C, ldc * sizeof(float), 0, (size_t)N * sizeof(float), M, s) != hipSuccess) { sga_set_error("sga_gemm: memset2d failed"); return SGA_ERR_HIP; }
         const int gxn = (M + 63) / 64;
-        int chunks = (4 * sga_num_cus() + gxn - 1) / gxn;
+        int chunks = (4 * ncu + gxn - 1) / gxn;
         if (chunks > (K + 31) / 32) chunks = (K + 31) / 32;              // at least 32 k rows per workgroup
         if (chunks < 1) chunks = 1;
-        const int kchunk = (K + chunks - 1) / chunks;
-        hipLaunchKernelGGL(gemm_tn_narrow_kernel, dim3(gxn, (K + kchunk - 1) / kchunk), dim3(GM_THREADS), 0, s, static_cast<const float*>(A), lda, B, ldb,
-                           C, ldc, M, N, K, kchunk);
-        SGA_CHECK_LAUNCH("sga_gemm");
+        p->kper = (K + chunks - 1) / chunks;
+        p->splits = (K + p->kper - 1) / p->kper;
+        p->route = SGA_GEMM_TN_NARROW;
         return SGA_OK;
     }
     const int gx = (M + 127) / 128, gy = (N + 127) / 128;
     // split K when the output grid cannot fill the chip (weight-gradient shape)
     int splits = 1;
-    const int ncu = sga_num_cus();
-    if (colstats) {
+    if (has_colstats) {
         // the statistics epilogue lives in the NT kernel only (one workgroup per output tile, no split)
-    } else if (gx * gy < ncu && K >= 4096 && act == 0 && !resid) {          // split-K partial sums cannot carry an epilogue
+    } else if (gx * gy < ncu && K >= 4096 && act == 0 && !has_resid) {          // split-K partial sums cannot carry an epilogue
         // ~4 workgroups per CU, at least 256 K-rows each (64 splits of 1024 left 3/4 of the chip idle: 350-470 us per
         // weight gradient at K = 65536 objects)
         splits = min((4 * ncu) / (gx * gy), (K + 255) / 256);
         if (splits < 1) splits = 1;
-    } else if (transA && !transB && !a_is_f64 && !bias && act == 0 && !resid && K >= 128 && gx * gy < ncu) {
+    } else if (transA && !transB && !a_is_f64 && !has_bias && act == 0 && !has_resid && K >= 128 && gx * gy < ncu) {
         // weight gradients at the reference's own batch sizes (K = a few hundred objects): one or two workgroups walking all of K
         // in the generic kernel took 78 us per GEMM; 64-row splits on the TN kernel put the chip to work (~8 us)
         splits = min((4 * ncu) / (gx * gy), (K + 63) / 64);
@@ -624,83 +628,132 @@ static int gemm_launch(int transA, int transB, int M, int N, int K, const void* 
     int kper = ((K + splits - 1) / splits + SGA_KC - 1) / SGA_KC * SGA_KC;
     if (kper < SGA_KC) kper = SGA_KC;
     splits = K > 0 ? (K + kper - 1) / kper : 1;
-    const int use_atomic = splits > 1;
-    if (use_atomic && !accumulate) {
-        if (ldc == N) {
-            if (hipMemsetAsync(C, 0, (size_t)M * N * sizeof(float), s) != hipSuccess) { sga_set_error("sga_gemm: memset failed"); return SGA_ERR_HIP; }
-        } else {
-            if (hipMemset2DAsync(C, ldc * sizeof(float), 0, (size_t)N * sizeof(float), M, s) != hipSuccess) { sga_set_error("sga_gemm: memset2d failed"); return SGA_ERR_HIP; }
-        }
-    }
-    const bool a_al = (reinterpret_cast<uintptr_t>(A) % 16 == 0) && (lda % 4 == 0);
-    const bool b_al = (reinterpret_cast<uintptr_t>(B) % 16 == 0) && (ldb % 4 == 0);
-    dim3 grid(gx, gy, splits);
+    p->splits = splits; p->kper = kper;
+    const bool use_atomic = splits > 1;
+    const bool a_al = a_al16 && (lda % 4 == 0);
+    const bool b_al = b_al16 && (ldb % 4 == 0);
     // (also unsplit when the output grid fills the chip by itself -- the wide-table stash products of configs[4], [ns x 1024..3072] over K = A:
     // they fell to the generic kernel at ~9 TFLOP/s, 14 % of that step; the TN kernel always accumulates atomically, so C is zeroed first
     // unless the caller accumulates)
-    const bool tn_big = !use_atomic && K >= 256 && gx * gy >= ncu && act == 0 && !resid && !colstats;      // (the TN kernel has no statistics epilogue)
-    if (!a_is_f64 && transA && !transB && (use_atomic || tn_big) && a_al && b_al && M % 4 == 0 && N % 4 == 0 && !bias) {
-        if (tn_big && !accumulate) {
-            if (ldc == N) {
-                if (hipMemsetAsync(C, 0, (size_t)M * N * sizeof(float), s) != hipSuccess) { sga_set_error("sga_gemm: memset failed"); return SGA_ERR_HIP; }
-            } else {
-                if (hipMemset2DAsync(C, ldc * sizeof(float), 0, (size_t)N * sizeof(float), M, s) != hipSuccess) { sga_set_error("sga_gemm: memset2d failed"); return SGA_ERR_HIP; }
-            }
-        }
-        hipLaunchKernelGGL(gemm_tn_kernel, grid, dim3(GM_THREADS), 0, s, static_cast<const float*>(A), lda, B, ldb, C, ldc, M, N, K, kper);
-        SGA_CHECK_LAUNCH("sga_gemm");
+    const bool tn_big = !use_atomic && K >= 256 && gx * gy >= ncu && act == 0 && !has_resid && !has_colstats;      // (the TN kernel has no statistics epilogue)
+    if (!a_is_f64 && transA && !transB && (use_atomic || tn_big) && a_al && b_al && M % 4 == 0 && N % 4 == 0 && !has_bias) {
+        p->route = use_atomic ? SGA_GEMM_TN_SPLIT : SGA_GEMM_TN_BIG;
         return SGA_OK;
     }
-    if (!a_is_f64 && !transA && !transB && a_al && b_al && K % 4 == 0 && N % 4 == 0 && !bias && act == 0 && !resid) {
-        hipLaunchKernelGGL(gemm_nn_kernel, grid, dim3(GM_THREADS), 0, s, static_cast<const float*>(A), lda, B, ldb, C, ldc, M, N, K,
-                           accumulate, kper, use_atomic);
-        SGA_CHECK_LAUNCH("sga_gemm");
+    if (!a_is_f64 && !transA && !transB && a_al && b_al && K % 4 == 0 && N % 4 == 0 && !has_bias && act == 0 && !has_resid) {
+        p->route = SGA_GEMM_NN;
         return SGA_OK;
     }
     if (!a_is_f64 && !transA && transB && splits == 1 && a_al && b_al && K % 4 == 0 && ldc < (1L << 26) && ldr < (1L << 26)) {
         // 64-row tiles when the 128-row grid ends in a mostly idle round (4 workgroups per CU: 163 840 rows x 128 columns = 1 280 tiles on
         // 1 024 slots run two rounds for 1.25 rounds of work; 2 560 half tiles run 2.5)
         const int slots = 4 * ncu, tiles = gx * gy, last = tiles % slots;
-        if (tiles > slots && tiles < 3 * slots && last > 0 && last * 2 < slots) {
-            if (nt3) hipLaunchKernelGGL(gemm_nt3_kernel<64>, dim3((M + 63) / 64, gy), dim3(GM_THREADS), 0, s, static_cast<const float*>(A), lda, B, ldb, C, ldc,
-                                        bias, M, N, K, accumulate, act, resid, ldr, colstats);
-            else
-            hipLaunchKernelGGL(gemm_nt_kernel<64>, dim3((M + 63) / 64, gy), dim3(GM_THREADS), 0, s, static_cast<const float*>(A), lda, B, ldb, C, ldc,
-                               bias, M, N, K, accumulate, act, resid, ldr, colstats);
-            SGA_CHECK_LAUNCH("sga_gemm");
-            return SGA_OK;
-        }
-        if (nt3) hipLaunchKernelGGL(gemm_nt3_kernel<128>, dim3(gx, gy), dim3(GM_THREADS), 0, s, static_cast<const float*>(A), lda, B, ldb, C, ldc,
-                                    bias, M, N, K, accumulate, act, resid, ldr, colstats);
-        else
-        hipLaunchKernelGGL(gemm_nt_kernel<128>, dim3(gx, gy), dim3(GM_THREADS), 0, s, static_cast<const float*>(A), lda, B, ldb, C, ldc,
-                           bias, M, N, K, accumulate, act, resid, ldr, colstats);
-        SGA_CHECK_LAUNCH("sga_gemm");
+        const bool half = tiles > slots && tiles < 3 * slots && last > 0 && last * 2 < slots;
+        p->route = nt3 ? (half ? SGA_GEMM_NT3_64 : SGA_GEMM_NT3_128) : (half ? SGA_GEMM_NT_64 : SGA_GEMM_NT_128);
         return SGA_OK;
     }
-    if (colstats) { sga_set_error("sga_gemm_bnstats: shape not taken by the NT kernel (needs K %% 4 == 0, 16-byte aligned operands)"); return SGA_ERR_ARG; }
+    if (has_colstats) return SGA_OK;                                        // REFUSED: the caller reports it
     // shapes none of the fast kernels take, narrow and short: one workgroup per 32 x 32 tile.  The choice depends on (N, K) only, never on
     // M: a batch walked in chunks of rows (pct inference) must get the same bits as the unchunked call
     if (!use_atomic && N <= 256 && K <= 512) {
-        dim3 g2((M + 31) / 32, (N + 31) / 32);
-        if (a_is_f64)
-            hipLaunchKernelGGL(gemm_small_kernel<double>, g2, dim3(GM_THREADS), 0, s, static_cast<const double*>(A), lda, transA, B, ldb,
-                               transB, C, ldc, bias, M, N, K, accumulate, act, resid, ldr);
-        else
-            hipLaunchKernelGGL(gemm_small_kernel<float>, g2, dim3(GM_THREADS), 0, s, static_cast<const float*>(A), lda, transA, B, ldb,
-                               transB, C, ldc, bias, M, N, K, accumulate, act, resid, ldr);
-        SGA_CHECK_LAUNCH("sga_gemm");
+        p->route = a_is_f64 ? SGA_GEMM_SMALL_F64 : SGA_GEMM_SMALL_F32;
         return SGA_OK;
     }
+    p->route = a_is_f64 ? SGA_GEMM_GENERIC_F64 : SGA_GEMM_GENERIC_F32;
+    return SGA_OK;
+}
+
+extern "C" int sga_gemm_plan(int transA, int transB, int M, int N, int K, long lda, long ldb, long ldc, long ldr, int a_is_f64, int a_aligned16,
+                             int b_aligned16, int has_bias, int accumulate, int act, int has_resid, int has_colstats, int ncu, int* route,
+                             int* splits, int* k_per_split) {
+    GemmPlan p;
+    const int rc = gemm_plan(transA, transB, M, N, K, lda, ldb, ldc, ldr, a_is_f64, a_aligned16, b_aligned16, has_bias, accumulate, act,
+                             has_resid, has_colstats, ncu, &p);
+    if (route) *route = p.route;
+    if (splits) *splits = p.splits;
+    if (k_per_split) *k_per_split = p.kper;
+    return rc;
+}
+
+// zero the M x N window of C (leading dimension ldc) ahead of a kernel that only adds into it
+static int gemm_zero_c(float* C, long ldc, int M, int N, hipStream_t s) {
+    const hipError_t e = ldc == N ? hipMemsetAsync(C, 0, (size_t)M * N * sizeof(float), s)
+                                  : hipMemset2DAsync(C, ldc * sizeof(float), 0, (size_t)N * sizeof(float), M, s);
+    if (e != hipSuccess) { sga_set_error("sga_gemm: memset failed"); return SGA_ERR_HIP; }
+    return SGA_OK;
+}
+
+static int gemm_launch(int transA, int transB, int M, int N, int K, const void* A, long lda, int a_is_f64,
+                       const float* B, long ldb, float* C, long ldc, const float* bias, int accumulate,
+                       int act, const float* resid, long ldr, void* stream, double* colstats = nullptr) {
+    GemmPlan p;
+    const int rc = gemm_plan(transA, transB, M, N, K, lda, ldb, ldc, ldr, a_is_f64, reinterpret_cast<uintptr_t>(A) % 16 == 0,
+                             reinterpret_cast<uintptr_t>(B) % 16 == 0, bias != nullptr, accumulate, act, resid != nullptr, colstats != nullptr, 0, &p);
+    if (rc != SGA_OK) return rc;
+    if (p.route == SGA_GEMM_EMPTY) return SGA_OK;
+    SGA_CHECK_ARG(C && (K == 0 || (A && B)), "sga_gemm: null pointer");
+    if (p.route == SGA_GEMM_REFUSED) { sga_set_error("sga_gemm_bnstats: shape not taken by the NT kernel (needs K %% 4 == 0, 16-byte aligned operands)"); return SGA_ERR_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int gx = (M + 127) / 128, gy = (N + 127) / 128;
+    const int use_atomic = p.splits > 1;
+    const int kper = p.kper;
+    const bool a_al = (reinterpret_cast<uintptr_t>(A) % 16 == 0) && (lda % 4 == 0);      // (the generic kernel's vector loads; the routes' own
+    const bool b_al = (reinterpret_cast<uintptr_t>(B) % 16 == 0) && (ldb % 4 == 0);      //  alignment conditions are in gemm_plan)
+    const float* Af = static_cast<const float*>(A);
+    dim3 grid(gx, gy, p.splits), blk(GM_THREADS);
+    // kernels that only add into C (the narrow walk, the TN kernel, every split-K form) get it zeroed first unless the caller accumulates
+    const bool adds_only = p.route == SGA_GEMM_TN_NARROW || p.route == SGA_GEMM_TN_SPLIT || p.route == SGA_GEMM_TN_BIG || use_atomic;
+    if (adds_only && !accumulate) {
+        const int zrc = gemm_zero_c(C, ldc, M, N, s);
+        if (zrc != SGA_OK) return zrc;
+    }
+    switch (p.route) {
+    case SGA_GEMM_TN_NARROW:
+        hipLaunchKernelGGL(gemm_tn_narrow_kernel, dim3((M + 63) / 64, p.splits), blk, 0, s, Af, lda, B, ldb, C, ldc, M, N, K, kper);
+        break;
+    case SGA_GEMM_TN_SPLIT:
+    case SGA_GEMM_TN_BIG:
+        hipLaunchKernelGGL(gemm_tn_kernel, grid, blk, 0, s, Af, lda, B, ldb, C, ldc, M, N, K, kper);
+        break;
+    case SGA_GEMM_NN:
+        hipLaunchKernelGGL(gemm_nn_kernel, grid, blk, 0, s, Af, lda, B, ldb, C, ldc, M, N, K, accumulate, kper, use_atomic);
+        break;
+    case SGA_GEMM_NT_64:
+        hipLaunchKernelGGL(gemm_nt_kernel<64>, dim3((M + 63) / 64, gy), blk, 0, s, Af, lda, B, ldb, C, ldc, bias, M, N, K, accumulate, act, resid, ldr, colstats);
+        break;
+    case SGA_GEMM_NT3_64:
+        hipLaunchKernelGGL(gemm_nt3_kernel<64>, dim3((M + 63) / 64, gy), blk, 0, s, Af, lda, B, ldb, C, ldc, bias, M, N, K, accumulate, act, resid, ldr, colstats);
+        break;
+    case SGA_GEMM_NT_128:
+        hipLaunchKernelGGL(gemm_nt_kernel<128>, dim3(gx, gy), blk, 0, s, Af, lda, B, ldb, C, ldc, bias, M, N, K, accumulate, act, resid, ldr, colstats);
+        break;
+    case SGA_GEMM_NT3_128:
+        hipLaunchKernelGGL(gemm_nt3_kernel<128>, dim3(gx, gy), blk, 0, s, Af, lda, B, ldb, C, ldc, bias, M, N, K, accumulate, act, resid, ldr, colstats);
+        break;
+    case SGA_GEMM_SMALL_F32:
+        hipLaunchKernelGGL(gemm_small_kernel<float>, dim3((M + 31) / 32, (N + 31) / 32), blk, 0, s, Af, lda, transA, B, ldb, transB, C, ldc, bias, M, N, K,
+                           accumulate, act, resid, ldr);
+        break;
+    case SGA_GEMM_SMALL_F64:
+        hipLaunchKernelGGL(gemm_small_kernel<double>, dim3((M + 31) / 32, (N + 31) / 32), blk, 0, s, static_cast<const double*>(A), lda, transA, B, ldb, transB,
+                           C, ldc, bias, M, N, K, accumulate, act, resid, ldr);
+        break;
+    case SGA_GEMM_GENERIC_F32:
+    case SGA_GEMM_GENERIC_F64:
 #ifdef SGA_GEMM_TRACE
-    fprintf(stderr, "[gemm generic] tA=%d tB=%d M=%d N=%d K=%d splits=%d f64=%d bias=%d acc=%d act=%d\n", transA, transB, M, N, K, splits, a_is_f64, bias != nullptr, accumulate, act);
+        fprintf(stderr, "[gemm generic] tA=%d tB=%d M=%d N=%d K=%d splits=%d f64=%d bias=%d acc=%d act=%d\n", transA, transB, M, N, K, p.splits, a_is_f64, bias != nullptr, accumulate, act);
 #endif
-    if (a_is_f64)
-        hipLaunchKernelGGL(gemm_kernel<double>, grid, dim3(GM_THREADS), 0, s, static_cast<const double*>(A), lda, transA, B, ldb,
-                           transB, C, ldc, bias, M, N, K, accumulate, kper, use_atomic, 0, (int)b_al, act, resid, ldr);
-    else
-        hipLaunchKernelGGL(gemm_kernel<float>, grid, dim3(GM_THREADS), 0, s, static_cast<const float*>(A), lda, transA, B, ldb,
-                           transB, C, ldc, bias, M, N, K, accumulate, kper, use_atomic, (int)a_al, (int)b_al, act, resid, ldr);
+        if (a_is_f64)
+            hipLaunchKernelGGL(gemm_kernel<double>, grid, blk, 0, s, static_cast<const double*>(A), lda, transA, B, ldb, transB, C, ldc, bias, M, N, K,
+                               accumulate, kper, use_atomic, 0, (int)b_al, act, resid, ldr);
+        else
+            hipLaunchKernelGGL(gemm_kernel<float>, grid, blk, 0, s, Af, lda, transA, B, ldb, transB, C, ldc, bias, M, N, K, accumulate, kper, use_atomic,
+                               (int)a_al, (int)b_al, act, resid, ldr);
+        break;
+    default:
+        sga_set_error("sga_gemm: internal: route %d", p.route);
+        return SGA_ERR_ARG;
+    }
     SGA_CHECK_LAUNCH("sga_gemm");
     return SGA_OK;
 }

@@ -94,6 +94,22 @@ def gemm(a, b, trans_a: bool, trans_b: bool, m: int, n: int, k: int, bias=None, 
     return out
 
 
+def gemm_plan(trans_a, trans_b, m, n, k, lda=None, ldb=None, ldc=None, ldr=0, a_is_f64=False, a_aligned16=True, b_aligned16=True,
+              has_bias=False, accumulate=False, act=0, has_resid=False, has_colstats=False, ncu=0):
+    """(route name, K splits, K rows per split) of the GEMM call so described -- sga_gemm_plan, the launcher's own decision.  Leading
+    dimensions default to the contiguous ones.  ncu > 0: plan for that CU count on the host alone; 0: ask the current device."""
+    import ctypes
+    lda = (m if trans_a else k) if lda is None else lda
+    ldb = (k if trans_b else n) if ldb is None else ldb
+    ldc = n if ldc is None else ldc
+    route, splits, kper = ctypes.c_int(-1), ctypes.c_int(0), ctypes.c_int(0)
+    rc = _lib.lib().sga_gemm_plan(int(trans_a), int(trans_b), m, n, k, lda, ldb, ldc, ldr, int(a_is_f64), int(a_aligned16), int(b_aligned16),
+                                  int(has_bias), int(accumulate), int(act), int(has_resid), int(has_colstats), ncu,
+                                  ctypes.byref(route), ctypes.byref(splits), ctypes.byref(kper))
+    _lib.check(rc, 'sga_gemm_plan')
+    return _lib.GEMM_ROUTES[route.value], splits.value, kper.value
+
+
 def colsum(x, out=None):
     m, n = x.shape
     if out is None:

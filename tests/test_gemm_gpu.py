@@ -3,6 +3,8 @@ NT with register prefetch, row-major TN and NN with split-K) and the shapes that
 import pytest
 import torch
 
+import gemm_gate as G
+
 pytestmark = pytest.mark.gpu
 
 
@@ -21,10 +23,16 @@ def test_gemm_variants_vs_fp64(m, n, k, ta, tb):
     b = torch.randn((n, k) if tb else (k, n), device='cuda')
     ref = (a.double().t() if ta else a.double()) @ (b.double().t() if tb else b.double())
     c = ops.gemm(a, b, ta, tb, m, n, k)
-    _check(c, ref, 1e-5 * max(1.0, k ** 0.5))
+    # the accuracy gate of the route this shape takes (tests/gemm_gate.py: envelope-relative error against plain fp32 on the CPU) ...
+    route = G.plan_of(ta, tb, m, n, k, a, b, c)[0]
+    la, lbt = (a.t() if ta else a), (b if tb else b.t())
+    yard = G.yardstick(la, lbt).cuda()
+    G.assert_gate(c, la, lbt, G.r_for(route, k), what=f'{route} {m}x{n}x{k}', yard_c=yard)
+    _check(c, ref, 1e-5 * max(1.0, k ** 0.5))             # ... inside the outer bound this test always had
     # accumulate on top of an existing C (split-K atomics must not clear it)
     c0 = torch.randn(m, n, device='cuda')
     c1 = ops.gemm(a, b, ta, tb, m, n, k, out=c0.clone(), accumulate=True)
+    G.assert_gate(c1, la, lbt, G.r_for(route, k), c0=c0, what=f'{route} {m}x{n}x{k} accumulate', yard_c=yard + c0)
     _check(c1, ref + c0.double(), 1e-5 * max(1.0, k ** 0.5))
 
 
@@ -38,6 +46,8 @@ def test_gemm_strided_views_and_bias():
     out_big = torch.zeros(700, 300, device='cuda')
     out = out_big[:, 100:196]
     ops.gemm(a, w, False, True, 700, 96, 128, bias=bias, out=out)
+    assert G.plan_of(False, True, 700, 96, 128, a, w, out, bias=bias)[0] == 'NT_128'
+    G.assert_gate(out, a, w, G.r_for('NT_128', 128), bias=bias, what='NT_128 strided views')
     _check(out, a.double() @ w.double().t() + bias.double())
     assert out_big[:, :100].abs().max() == 0 and out_big[:, 196:].abs().max() == 0
 

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+import gemm_gate as G
 from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -18,12 +19,18 @@ def test_gemm_variants(ta, tb, m, n, k):
     b = torch.randn((n, k) if tb else (k, n), dtype=torch.float64)
     bias = torch.randn(n, dtype=torch.float64)
     ref = (a.t() if ta else a) @ (b.t() if tb else b) + bias
-    out = ops.gemm(a.float().cuda(), b.float().cuda(), bool(ta), bool(tb), m, n, k, bias=bias.float().cuda())
+    ad, bd, biasd = a.float().cuda(), b.float().cuda(), bias.float().cuda()
+    out = ops.gemm(ad, bd, bool(ta), bool(tb), m, n, k, bias=biasd)
     torch.cuda.synchronize()
+    # the accuracy gate of the route taken (tests/gemm_gate.py), on the fp32 operands the kernel saw ...
+    route = G.plan_of(ta, tb, m, n, k, ad, bd, out, bias=biasd)[0]
+    la, lbt = (ad.t() if ta else ad), (bd if tb else bd.t())
+    G.assert_gate(out, la, lbt, G.r_for(route, k), bias=biasd, what=f'{route} {m}x{n}x{k}')
     err = (out.cpu().double() - ref).abs().max().item()
-    assert err < 1e-4 * max(1.0, k ** 0.5), err
-    out2 = ops.gemm(a.float().cuda(), b.float().cuda(), bool(ta), bool(tb), m, n, k, out=out.clone(), accumulate=True)
+    assert err < 1e-4 * max(1.0, k ** 0.5), err           # ... inside the outer bound against the unrounded fp64 inputs
+    out2 = ops.gemm(ad, bd, bool(ta), bool(tb), m, n, k, out=out.clone(), accumulate=True)
     torch.cuda.synchronize()
+    G.assert_gate(out2, la, lbt, G.r_for(route, k), c0=out, what=f'{route} {m}x{n}x{k} accumulate')
     err2 = (out2.cpu().double() - (2 * ref - bias)).abs().max().item()
     assert err2 < 2e-4 * max(1.0, k ** 0.5), err2
 
