@@ -405,6 +405,27 @@ int sga_hull_candidates(const float* pts, const int32_t* offsets, int n_obj, uns
 int sga_hull_max_candidates(void);
 int sga_hull_vertices(const double* pts, const int32_t* offsets, int n_obj, unsigned char* is_vertex, int32_t* status, void* stream);
 
+/* ---- batched exact nearest-neighbour search, fp64 (the point-cloud geometry either side of the path) ----------
+ * replaces utils/point_cloud.py:136-147 get_nearest_neighbor (cKDTree(s).query(q, k=1)), the radius search of utils/point_cloud.py:91-103
+ * compute_pcl_overlap (preprocessing/scan3r/subgenscan3r.py:107-118: every pair of subscans of every scan) and the per-vertex KD-tree loop
+ * of utils/registration.py:107-129 nn_correspondence.  Brute force, so exact.
+ * pts [total_points, 3] f64, clouds packed back to back; offsets [n_clouds + 1]; pairs [n_pairs, 2] = (query cloud, support cloud);
+ * out_offsets [n_pairs]: where job p's nq results start in out_dist / out_idx [total_queries] (jobs must not overlap).  These three are
+ * DEVICE int32 arrays; offsets_host / pairs_host (nullable) are host copies of offsets / pairs that, when given, are validated before
+ * anything is launched.  max_queries / max_support: the largest query / support cloud of any job (they size the grid; a job larger than
+ * stated is left partly unwritten, never read or written out of bounds -- the kernels re-check every id and offset they read).
+ * Arithmetic: d2 = (dx*dx + dy*dy) + dz*dz, dx = q.x - s.x ..., each operation rounded on its own (no FMA); out_dist = d2 when squared != 0,
+ * else the correctly rounded sqrt(d2): bit-identical to cKDTree's distances.  out_idx: the support-cloud-local index of the nearest
+ * point; among exactly equal minima the LOWEST index (numpy.argmin's rule; cKDTree's choice is arbitrary).  Empty support: +inf, -1.
+ * A NaN distance never wins.  chunk: support points per workgroup pass.  Jobs with ns <= chunk are finished in one pass; larger ones go
+ * chunk by chunk into `workspace` (sga_nn_workspace_bytes(): 12 bytes x ceil(max_support / chunk) x total_queries, 0 when nothing is
+ * split) and a second kernel folds the chunks in ascending order.  No atomics: the output is a pure function of the input. */
+size_t sga_nn_workspace_bytes(int total_queries, int max_support, int chunk);
+int sga_nn_search(const double* pts, const int32_t* offsets, int n_clouds, int total_points, const int32_t* pairs, int n_pairs,
+                  const int32_t* out_offsets, int total_queries, int max_queries, int max_support, int chunk,
+                  const int32_t* offsets_host, const int32_t* pairs_host, int squared, double* out_dist, int32_t* out_idx,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* Wide tables (Dp > 128) of sga_loss_neg_grad: one anchor-owner sweep writes c_ij = dL/dS_ij to a caller-owned stash (anchor-row blocks
  * sized to stash_floats; sga_loss_neg_grad_wide_floats() = everything in one block), both gradients are GEMMs on it: the K = Dp
  * similarity tile is computed once instead of 2 x ceil(Dp / 320) times.  Same results as sga_loss_neg_grad up to fp32 summation order. */

@@ -65,6 +65,8 @@ SIGNATURES = {
     'sga_hull_candidates': (I, [P, P, I, P, P, P]),
     'sga_hull_max_candidates': (I, []),
     'sga_hull_vertices': (I, [P, P, I, P, P, P]),
+    'sga_nn_workspace_bytes': (c_size_t, [I, I, I]),
+    'sga_nn_search': (I, [P, P, I, I, P, I, P, I, I, I, I, P, P, I, P, P, P, c_size_t, P]),
     'sga_gemm': (I, [I, I, I, I, I, P, c_long, I, P, c_long, P, c_long, P, I, P]),
     'sga_colsum': (I, [P, c_long, I, I, P, I, P]),
     'sga_gemm_bnstats': (I, [I, I, I, P, c_long, P, c_long, P, c_long, P, P, P]),

@@ -1,7 +1,11 @@
 """Drop-in for the reference's `utils.alignment` (utils/alignment.py) + the FPS step of `utils.point_cloud`.
 With `<root>/sgaligner_amd` on sys.path this package is found as top-level `utils`; only `utils.alignment` is taken
 over then -- every other `utils.*` module (torch_util, common, scan3r, the full point_cloud ...) keeps resolving to
-the reference tree further down sys.path (see sgaligner_amd/_dropin.py)."""
+the reference tree further down sys.path (see sgaligner_amd/_dropin.py).
+
+`sgaligner_amd.utils.point_cloud` also carries the exact nearest-neighbour helpers (get_nearest_neighbor, compute_pcl_overlap[_pairs],
+apply_transform) and `sgaligner_amd.utils.registration` the chamfer / mosaicking / registration metrics built on them (csrc/nnsearch.hip).
+Neither is aliased: callers import them from `sgaligner_amd.utils...` explicitly."""
 if __name__ == 'utils':
     import os as _os
     import sys as _sys

@@ -1,10 +1,14 @@
-"""Host-side mirror of the reference's utils/point_cloud.py sampling helpers, backed by the HIP FPS kernel.
+"""Host-side mirror of the reference's utils/point_cloud.py sampling and nearest-neighbour helpers, backed by the HIP kernels.
 
 `pcl_farthest_sample(point, npoint, return_idxs)` keeps the reference signature and semantics (utils/point_cloud.py:
 61-89): N < npoint -> random draw with replacement on the host (np.random.choice, :70-73); otherwise the first sample is
 drawn with np.random.randint(0, N) (:77) and the remaining ones come from csrc/fps.hip (bit-identical index sequence).
 `farthest_point_sample_batch` is the batched form preprocessing wants: all objects of a scan (or of many scans) in
-one launch."""
+one launch.
+
+`get_nearest_neighbor`, `compute_pcl_overlap` and `apply_transform` keep the reference signatures (utils/point_cloud.py:136-157,
+91-103); `nearest_neighbor_batch` / `compute_pcl_overlap_pairs` are the batched forms (csrc/nnsearch.hip: exact fp64 brute force,
+distances bit-identical to cKDTree's, ties to the lowest index)."""
 from __future__ import annotations
 
 import numpy as np
@@ -154,3 +158,142 @@ def convex_hull_barycenter(obj_pcl):
     """Single-object form: (cx, cy, cz) exactly as preprocess.py:93-96 binds them."""
     c = convex_hull_barycenters_batch([obj_pcl])[0]
     return float(c[0]), float(c[1]), float(c[2])
+
+
+# ---- exact nearest neighbours (utils/point_cloud.py:91-103, 136-147; utils/registration.py:107-129) -------------------------
+NN_CHUNK = None           # support points per workgroup pass of csrc/nnsearch.hip; None = chosen per call (_nn_chunk).  Tests lower it
+                          # to force the split (chunked + merged) form on mid-sized inputs.
+NN_QUERY_TILE = 1024      # queries per workgroup of nn_kernel (256 lanes x 4)
+NN_MIN_CHUNK = 2048       # never split a support finer than this: below it the partial workspace costs more than idle CUs
+
+
+def _nn_chunk(sizes_q, sizes_s) -> int:
+    """Chunk size for a job list: split the supports just far enough that the grid fills the device a few times over (about 16
+    workgroups per CU), no further -- the partial workspace is 12 B x n_chunks x total queries."""
+    tiles = int(sum(-(-int(q) // NN_QUERY_TILE) for q in sizes_q)) or 1
+    ns_max = int(max(sizes_s, default=0))
+    want = 16 * int(_lib.lib().sga_device_cus())
+    n_chunks = max(1, min(-(-want // tiles), -(-ns_max // NN_MIN_CHUNK)))
+    return max(NN_MIN_CHUNK, -(-ns_max // n_chunks))
+
+
+def nearest_neighbor_batch(points, offsets, pairs, chunk=None, squared=False):
+    """points [sum N, 3] float64 CUDA tensor (clouds packed back to back), offsets [n_clouds+1] host ints, pairs [n_pairs, 2] host ints
+    (query cloud, support cloud).  One launch for all jobs.  Returns (dist [sum nq] float64, idx [sum nq] int32, out_offsets
+    [n_pairs+1] int64 numpy): job p's results are dist[out_offsets[p]:out_offsets[p+1]]; idx is support-cloud-local, the LOWEST index among
+    exactly equal minima; an empty support gives (+inf, -1).  dist is the correctly rounded sqrt of (dx*dx + dy*dy) + dz*dz (bit-identical
+    to cKDTree(s).query(q)[0]); squared=True returns that sum itself."""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda:
+        raise RuntimeError(f'sgaligner_amd: `points` must be a HIP device tensor (got '
+                           f'{points.device if isinstance(points, torch.Tensor) else type(points)}); there is no CPU path')
+    if points.dtype != torch.float64:
+        raise RuntimeError(f'sgaligner_amd: `points` must be torch.float64 (got {points.dtype})')
+    pts = points.contiguous()
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f'points must be [N,3], got {tuple(pts.shape)}')
+    off = np.ascontiguousarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets, dtype=np.int64).reshape(-1)
+    n_clouds = len(off) - 1
+    if n_clouds < 0 or off[0] != 0 or off[-1] != pts.shape[0] or (np.diff(off) < 0).any():
+        raise ValueError('offsets must be a monotone prefix array covering all points')
+    pr = np.ascontiguousarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
+    if pr.size and (pr.min() < 0 or pr.max() >= n_clouds):
+        raise ValueError(f'pairs must name clouds in [0, {n_clouds})')
+    sizes = np.diff(off)
+    nq, ns = sizes[pr[:, 0]], sizes[pr[:, 1]]
+    out_off = np.concatenate([[0], np.cumsum(nq)]).astype(np.int64)
+    total_q = int(out_off[-1])
+    if pts.shape[0] >= 2 ** 31 or total_q >= 2 ** 31:
+        raise ValueError('nearest_neighbor_batch indexes with int32: fewer than 2^31 points and 2^31 queries per call')
+    from .. import ops
+    if ops.VALIDATE and pts.numel() and not bool(torch.isfinite(pts).all()):
+        raise RuntimeError('sgaligner_amd: `points` holds NaN or infinite coordinates')
+    dev = pts.device
+    dist = torch.empty((total_q,), device=dev, dtype=torch.float64)
+    idx = torch.empty((total_q,), device=dev, dtype=torch.int32)
+    if total_q == 0:
+        return dist, idx, out_off
+    chunk = int(chunk if chunk is not None else NN_CHUNK if NN_CHUNK is not None else _nn_chunk(nq, ns))
+    if chunk < 1:
+        raise ValueError(f'chunk must be >= 1, got {chunk}')
+    L = _lib.lib()
+    h_off, h_pr, h_oo = off.astype(np.int32), np.ascontiguousarray(pr, dtype=np.int32), out_off[:-1].astype(np.int32)
+    meta = torch.from_numpy(np.concatenate([h_off, h_pr.reshape(-1), h_oo])).to(dev)          # one small upload
+    d_off, d_pr, d_oo = meta[:len(h_off)], meta[len(h_off):len(h_off) + h_pr.size], meta[len(h_off) + h_pr.size:]
+    ws_bytes = int(L.sga_nn_workspace_bytes(total_q, int(ns.max()), chunk))
+    ws = torch.empty((max((ws_bytes + 7) // 8, 1),), device=dev, dtype=torch.float64)
+    rc = L.sga_nn_search(_p(pts), _p(d_off), n_clouds, int(pts.shape[0]), _p(d_pr), len(pr), _p(d_oo), total_q, int(nq.max()), int(ns.max()),
+                         chunk, h_off.ctypes.data, h_pr.ctypes.data, 1 if squared else 0, _p(dist), _p(idx), _p(ws), ws_bytes, _stream())
+    _lib.check(rc, 'sga_nn_search')
+    return dist, idx, out_off
+
+
+def _need_device(what: str):
+    if not torch.cuda.is_available():
+        raise RuntimeError(f'sgaligner_amd: `{what}` needs a HIP device (torch.cuda.is_available() is False); there is no CPU path')
+
+
+def _cloud64(a, name: str):
+    a = np.asarray(a)
+    if a.ndim != 2 or a.shape[1] < 3:
+        raise ValueError(f'{name} must be [N, 3], got {a.shape}')
+    return np.ascontiguousarray(a[:, :3], dtype=np.float64)
+
+
+def _nn_numpy(clouds, pairs):
+    """clouds: list of [N_i, 3] float64 numpy arrays; one upload, one launch, one download.  -> list of (dist, idx int64) per pair."""
+    off = np.concatenate([[0], np.cumsum([len(c) for c in clouds])]).astype(np.int64)
+    pts = torch.from_numpy(np.concatenate(clouds) if len(clouds) > 1 else clouds[0]).cuda()
+    dist, idx, oo = nearest_neighbor_batch(pts, off, pairs)
+    dist, idx = dist.cpu().numpy(), idx.cpu().numpy().astype(np.int64)
+    return [(dist[oo[p]:oo[p + 1]], idx[oo[p]:oo[p + 1]]) for p in range(len(pairs))]
+
+
+def get_nearest_neighbor(q_points: np.ndarray, s_points: np.ndarray, return_index: bool = False):
+    """Reference signature (utils/point_cloud.py:136): the distance from every query point to its nearest support point (float64
+    numpy, bit-identical to cKDTree(s_points).query(q_points, k=1)[0] for 3-D input) and, with return_index, that point's index (int64;
+    the lowest one among exactly equal minima, where cKDTree's choice is arbitrary)."""
+    _need_device('get_nearest_neighbor')
+    q, s = _cloud64(q_points, 'q_points'), _cloud64(s_points, 's_points')
+    if len(s) == 0:
+        raise ValueError('get_nearest_neighbor: s_points is empty')
+    dist, idx = _nn_numpy([q, s], [(0, 1)])[0]
+    return (dist, idx) if return_index else dist
+
+
+def _overlap_of(dist, n_source: int, threshold: float):
+    common = np.flatnonzero(dist <= threshold).astype(np.int64)          # sorted and unique by construction, as np.unique returns them
+    return round(common.shape[0] / n_source, 4), common
+
+
+def compute_pcl_overlap(source, target, threshold=1e-7):
+    """Reference signature (utils/point_cloud.py:91): (round(ratio, 4), common_pts_idx_src) -- the source points that have a target point
+    within `threshold` (fp64), as sorted unique int64 indices, and their share of the source.  A source point is common iff the distance
+    to its NEAREST target point is <= threshold.  The reference asks open3d's RadiusSearch; whether that includes a neighbour exactly AT
+    the radius is not pinned here (open3d is not available to compare against) -- with the default 1e-7 on scan data the question does
+    not arise: shared points are bitwise copies (distance 0), all others are millimetres apart."""
+    _need_device('compute_pcl_overlap')
+    return compute_pcl_overlap_pairs([source, target], [(0, 1)], threshold)[0]
+
+
+def compute_pcl_overlap_pairs(clouds, pairs, threshold=1e-7):
+    """The batched form preprocessing/scan3r/subgenscan3r.py:107-118 wants: clouds = the subscans of a scan (list of [N_i, 3] arrays),
+    pairs = [(source, target), ...] cloud ids.  One upload and one launch for all pairs; returns [compute_pcl_overlap(clouds[s],
+    clouds[t], threshold) for s, t in pairs]."""
+    _need_device('compute_pcl_overlap_pairs')
+    cl = [_cloud64(c, f'clouds[{i}]') for i, c in enumerate(clouds)]
+    pairs = [(int(a), int(b)) for a, b in pairs]
+    for a, b in pairs:
+        if len(cl[a]) == 0 or len(cl[b]) == 0:
+            raise ValueError(f'compute_pcl_overlap: cloud {a if len(cl[a]) == 0 else b} is empty')
+    if not pairs:
+        return []
+    return [_overlap_of(d, len(cl[a]), threshold) for (d, _), (a, _b) in zip(_nn_numpy(cl, pairs), pairs)]
+
+
+def apply_transform(points: np.ndarray, transform: np.ndarray, normals=None):
+    """Reference signature (utils/point_cloud.py:149): points @ R^T + t for a 4x4 rigid transform (numpy, on the host)."""
+    rot, trans = transform[:3, :3], transform[:3, 3]
+    moved = np.matmul(points, rot.T) + trans
+    if normals is None:
+        return moved
+    return moved, np.matmul(normals, rot.T)
