@@ -426,6 +426,29 @@ int sga_nn_search(const double* pts, const int32_t* offsets, int n_clouds, int t
                   const int32_t* offsets_host, const int32_t* pairs_host, int squared, double* out_dist, int32_t* out_idx,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- batched RANSAC rigid registration from point correspondences, fp64 -------------------------------------------------------
+ * the estimator of src/engine/registration_evaluator.py:129-208 (pygcransac.findRigidTransform with min_iters == max_iters and
+ * spatial_coherence_weight == 0: a fixed number of three-point hypotheses, scored against every correspondence, then least-squares refits
+ * on the inliers) and of utils/open3d.py:172-201.  Jobs are packed back to back: corr [total_rows, 6] f64, a row = source xyz | reference
+ * xyz; offsets [n_jobs + 1]; samples [total_hyp, 3] job-local row indices; hyp_offsets [n_jobs + 1].  These are DEVICE arrays;
+ * offsets_host / hyp_offsets_host (nullable) are host copies that, when given, are validated before anything is launched.  max_rows /
+ * max_hyp: the largest job (they size the grid; the kernels re-check every offset and sample they read, a bad one makes them do nothing).
+ * The samples are an input and no atomics are used: the output is a pure function of the arguments, bit for bit.
+ * Hypothesis h: the least-squares proper rotation + translation of its three pairs (Horn's quaternion by Jacobi sweeps); invalid (a
+ * repeated or out-of-range index, a non-finite result) -> count 0, never selected.  hyp_count[h] = #{i : |R s_i + t - r_i|^2 <= threshold^2}.
+ * Selected: the LOWEST index among the hypotheses with the maximal count.  Then refine_rounds times: least-squares fit over the current
+ * inliers, recount, keep it if the count did not drop, else stop.  Per job: transform [4, 4] row-major, column-vector convention
+ * (ref ~ R src + t); inlier_count; best_hyp; status 0 = ok, 1 = no model (fewer than 3 rows, no valid hypothesis, best count below 3:
+ * identity, count 0, mask 0, best_hyp -1); inlier_mask [total_rows] and inlier_count belong to the final transform.
+ * refine_rounds == -1 stops after the scoring: hyp_count is written, the per-job outputs and the mask are left untouched.
+ * chunk: rows per scoring workgroup pass; per-chunk counts go to the workspace and are folded in ascending order. */
+size_t sga_ransac_workspace_bytes(int n_jobs, int total_hyp, int max_rows, int chunk);
+int sga_ransac_rigid(const double* corr, const int32_t* offsets, int n_jobs, int total_rows, const int32_t* samples,
+                     const int32_t* hyp_offsets, int total_hyp, int max_rows, int max_hyp, int chunk, const int32_t* offsets_host,
+                     const int32_t* hyp_offsets_host, double threshold, int refine_rounds, double* transform, int32_t* inlier_count,
+                     int32_t* best_hyp, int32_t* status, unsigned char* inlier_mask, int32_t* hyp_count, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* Wide tables (Dp > 128) of sga_loss_neg_grad: one anchor-owner sweep writes c_ij = dL/dS_ij to a caller-owned stash (anchor-row blocks
  * sized to stash_floats; sga_loss_neg_grad_wide_floats() = everything in one block), both gradients are GEMMs on it: the K = Dp
  * similarity tile is computed once instead of 2 x ceil(Dp / 320) times.  Same results as sga_loss_neg_grad up to fp32 summation order. */
