@@ -7,6 +7,7 @@
 // value, alignment.py:7,18) and its K nearest other objects with their distances.  The full n x n
 // sort and the seven device->host copies of the rank list (alignment.py:4,14,29) disappear.
 // Ties: broken by object index (a stable ascending sort); the reference's sort is unstable there.
+// (tests/test_simrank_exact_gpu.py: every route on tie-dense data where the arithmetic is exact.)
 //
 // simrank_staged_kernel / simrank_stream_kernel: the per-pair E E^T blocks on the matrix cores.  A workgroup = 4 waves = 64
 // consecutive objects of one pair (its "query rows"); only blocks that hold a query are launched (blk_pair / blk_row), so the work
@@ -322,7 +323,8 @@ __global__ void pair_metrics_kernel(const int* __restrict__ rank, const int* __r
                 const float sj = top1_sim[(size_t)(q0 + j) * ldk];
                 pos += (sj < s || (sj == s && j < i)) ? 1 : 0;
             }
-            const bool wrong = top1[(size_t)(q0 + i) * ldk] != q_tgt[q0 + i] - o0;
+            const int p1 = top1[(size_t)(q0 + i) * ldk];   // -1: a pair of one object has no prediction (never "right", whatever the target)
+            const bool wrong = p1 < 0 || p1 != q_tgt[q0 + i] - o0;
             if (wrong) { bad100 = 1; if (pos < 2) bad2 = 1; if (pos < na / 2) bad50 = 1; }
         }
 #pragma unroll
@@ -368,9 +370,16 @@ int simrank_launch(const float* E, int T, int D, const int32_t* pair_off, const 
     a.rank = rank; a.topk_idx = topk_idx; a.topk_sim = topk_sim;
     a.npad_max = ((max_pair_objects + 15) / 16) * 16 + 1;
     const int nkq = (D + 15) / 16;
+    // the strip of a 512-object pair plus the KQ = 26 tile is 158 208 B of the 160 KB: a refused request is reported, not launched
+    auto grant = [&](const void* kern, size_t lds) {
+        const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) sga_set_error("%s: %zu B of dynamic LDS refused: %s", who, lds, hipGetErrorString(e));
+        return e == hipSuccess;
+    };
+    bool granted = true;
     auto launch = [&](auto kern, size_t lds) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(256), lds, s, a);
+        granted = grant(reinterpret_cast<const void*>(kern), lds);
+        if (granted) hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(256), lds, s, a);
     };
     const size_t strip_b = (size_t)4 * 16 * a.npad_max * sizeof(float);
     auto tile_b = [](int kq) { return (size_t)16 * (kq * 16 + 4) * sizeof(float); };
@@ -382,10 +391,13 @@ int simrank_launch(const float* E, int T, int D, const int32_t* pair_off, const 
         const int Dp = (D + 31) / 32 * 32;
         SGA_CHECK_ARG(workspace_bytes >= sga_simrank_workspace_bytes_f16(T, D), "%s: workspace too small for the fp16 table (sga_simrank_workspace_bytes_f16)", who);
         _Float16* Eh = reinterpret_cast<_Float16*>(reinterpret_cast<char*>(workspace) + (sga_simrank_workspace_bytes(T) + 255) / 256 * 256);
-        hipLaunchKernelGGL(normalize_f16_kernel, dim3(g), dim3(256), 0, s, E, T, D, Dp, Eh);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(simrank_stream16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)strip_b);
-        hipLaunchKernelGGL(simrank_stream16_kernel, dim3(n_blocks), dim3(256), strip_b, s, a, Eh, Dp);
+        granted = grant(reinterpret_cast<const void*>(simrank_stream16_kernel), strip_b);
+        if (granted) {
+            hipLaunchKernelGGL(normalize_f16_kernel, dim3(g), dim3(256), 0, s, E, T, D, Dp, Eh);
+            hipLaunchKernelGGL(simrank_stream16_kernel, dim3(n_blocks), dim3(256), strip_b, s, a, Eh, Dp);
+        }
     } else launch(simrank_stream_kernel<F16>, strip_b);                                   // wider: both operands streamed per wave
+    if (!granted) { (void)hipGetLastError(); return SGA_ERR_HIP; }
     hipError_t e_ = hipGetLastError();
     if (e_ != hipSuccess) { sga_set_error("%s: launch failed: %s", who, hipGetErrorString(e_)); return SGA_ERR_HIP; }
     return SGA_OK;

@@ -83,10 +83,10 @@ def evaluate_batch(embedding, data_dict, all_k=(1, 2, 3, 4, 5), recall_modes=('2
         pm = ops.pair_metrics(rank, tki, tks, e2i, lay, e1c)
         host = torch.cat([rank.float(), pm.reshape(-1)]).cpu().numpy()          # one read-back
         rk, pm = host[:len(e1i)], host[len(e1i):].reshape(-1, 12)
-        res['mrr'] = (1.0 / rk).tolist()
+        res['mrr'] = np.where(rk >= 1, 1.0 / np.maximum(rk, 1), 0.0).tolist()   # rank -1 (target outside the pair): a miss, as on the device
         has = e1c > 0
         for k in all_k:
-            res[k]['correct'] = int(pm[:, k - 1].sum()) if 1 <= k <= 5 else int((rk <= k).sum())
+            res[k]['correct'] = int(pm[:, k - 1].sum()) if 1 <= k <= 5 else int(((rk >= 1) & (rk <= k)).sum())
             res[k]['total'] = int(e1c.sum())
         col = {'2': 7, '50': 8, '100': 9}
         for m in recall_modes:
