@@ -263,8 +263,8 @@ struct TArgs {
 // start from zero in every tile and are added to the tile's gacc by a plain fp32 v_add (round to nearest: unbiased, unlike the MFMA's chop)
 // two column-tile groups later, under other MFMAs.  28 registers instead of 28 MG: four tables' owner gradients fit ONE launch (M = 4: every
 // similarity formed once, 328 instead of 2 x 244 MFMAs per 16 x 32 pairs), at 28 VALU per table and tile.
-template <int M, bool GRAD, int WV, int MG = M, bool GAM = true, bool LITE = false, bool FOLD = false>
-__global__ __launch_bounds__(WV * 64, WV == 8 ? 2 : 1) void sweep3_kernel(TArgs a) {
+template <int M, bool GRAD, int WV, int MG, bool GAM, bool LITE, bool FOLD>
+__device__ __forceinline__ void sweep3_body(const TArgs& a, const int g) {
     static_assert(!LITE || !GRAD, "LITE: the forward sums only");
     static_assert(!FOLD || (GRAD && WV == 4), "FOLD: the one-wave-per-SIMD gradient sweep only");
     constexpr int NCT = 7;
@@ -291,9 +291,6 @@ __global__ __launch_bounds__(WV * 64, WV == 8 ? 2 : 1) void sweep3_kernel(TArgs 
     extern __shared__ __attribute__((aligned(16))) unsigned char lds3[];      // [2][M][S3_BLOCK]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g4 = lane >> 4, l15 = lane & 15;
-    int g = 0;
-#pragma unroll
-    for (int i = 1; i < 4; ++i) if (i < a.ngroups && (int)blockIdx.x >= a.grp[i].blk0) g = i;
     const TGroup& grp = a.grp[g];
     // XCD-aware work order (as sweep16_kernel, contrastive.hip): the group's (split major, owner block minor) work list in 8 contiguous per-XCD chunks
     const int wg_in_grp = (int)blockIdx.x - grp.blk0;
@@ -378,42 +375,77 @@ __global__ __launch_bounds__(WV * 64, WV == 8 ? 2 : 1) void sweep3_kernel(TArgs 
 #pragma unroll
     for (int m = 0; m < M; ++m) gam[m] = 0.f;
 
-    // Tile transport: ONE contiguous 22-KiB copy per table by LDS-DMA (global_load_lds, 1 KiB per wave instruction), slot (table m, k) ->
+    // Tile transport: ONE contiguous 22-KiB copy per table by LDS-DMA (buffer_load_dwordx4 ... lds, 1 KiB per wave instruction), slot (table m, k) ->
     // chunk (wave + m) % WAVES + WAVES k: the table index of every DMA is a compile-time constant.  Issued in one burst at the top of a
     // tile for the NEXT tile.
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);        // M0 (the DMA's LDS address) must be provably uniform
-    unsigned l16 = threadIdx.x;                                     // (unsigned: base + zext(offset) is what selects the saddr form)
-    asm volatile("" : "+v"(l16));
-    l16 = (l16 & 63u) * 16u;
+    const unsigned l16 = (threadIdx.x & 63u) * 16u;                 // the copies' lane offset: their only address VGPR, loop invariant
     // flat copy slots [f_lo, f_hi) of the M * KMAX (table, k) slots.  The copies of the NEXT tile are spread over this tile's first S
     // sub-steps (a burst of all of them at the top of the tile queues up behind the CU's one texture-address unit -- 16 cycles per 1-KiB
     // instruction, 66 of them per tile from the four waves -- and stalled every wave's in-order stream for ~12 % of the tile,
     // S3_DBG_TIMING); BRANCH-FREE: a slot past the block's last chunk copies the wave's previous chunk again (same bytes to the same
     // place), a tile without successor copies itself into the idle buffer -- a branch here splits the MFMA stream into basic blocks, and
     // hipcc opens every block that follows a join with s_waitcnt lgkmcnt(0) right behind the operand requests it has just issued.
-    unsigned long long tb[M];                                                      // scalar base of the tile being copied, per table
-    auto set_tile = [&](int blk) {
+    // Addresses: the BUFFER form of the LDS copy.  One resource descriptor per table (base = the segment's first block, records = the
+    // segment's bytes: a copy can never leave the segment; built per segment, held in SGPRs), the tile's and the chunk's byte offset in the
+    // scalar offset, the loop-invariant lane offset l16 in the one address VGPR: a copy costs two scalar adds (offset, M0) and no VALU.
+    // (The global form took a 64-bit v_lshl_add_u64 per lane and copy plus three scalar adds, whatever the source spelled.)
+    // Slot (m, k) copies chunk c = rot_m + WAVES k, rot_m = (wave + m) % WAVES: byte offset crot[m] + 1024 WAVES k in the block and in its
+    // LDS image alike.  Per tile and table ONE scalar add each forms trot[m] (tile + crot) and brot[m] (buffer + table + crot); a copy adds
+    // its compile-time k part to both.  Only a block's LAST k slot can leave that pattern (fall off the block; LITE: the tail image's
+    // chunks): its offset clast[m] is a loop invariant of its own.
+    __amdgpu_buffer_rsrc_t rs[M];
+    typedef __attribute__((address_space(3))) unsigned char* lds_ptr;
+    constexpr bool LAST_ODD = KMAX * WAVES > NCH || (LITE && KMAX * WAVES > 2 * (S3_PLANE / 1024));   // the last k slot needs clast
+    unsigned crot[M], clast[M], trot[M], brot[M];
+    unsigned tile_off = 0, buf_off = 0;                                             // the tile being copied: byte offset in its segment / of its LDS buffer
 #pragma unroll
-        for (int m = 0; m < M; ++m) tb[m] = sreg64(reinterpret_cast<unsigned long long>(a.Zb[m]) + (unsigned long long)blk * S3_BLOCK);
+    for (int m = 0; m < M; ++m) {
+        const int rot = (wave_u + m) & (WAVES - 1);
+        int c = rot + (KMAX - 1) * WAVES;
+        c = c >= NCH ? c - WAVES : c;                                               // past the block: the wave's previous chunk again
+        if (LITE) c = c >= 2 * (S3_PLANE / 1024) ? c + S3_PLANE / 1024 : c;         // chunks 0..11 = h, m planes; 12..13 -> the tail image (18, 19)
+        crot[m] = (unsigned)rot * 1024u; clast[m] = (unsigned)c * 1024u;
+        trot[m] = 0; brot[m] = 0;
+    }
+    auto set_seg = [&](const TSeg& sgm) {
+#pragma unroll
+        for (int m = 0; m < M; ++m)
+            rs[m] = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.Zb[m]) + (size_t)sgm.blk0 * S3_BLOCK, (short)0,
+                                                      (int)((unsigned)sgm.jt_hi * (unsigned)S3_BLOCK), 0x00020000);
     };
-    auto issue_slots = [&](unsigned char* buf, int f_lo, int f_hi) {
+    auto set_tile = [&](int jt, unsigned char* buf) {
+        tile_off = (unsigned)jt * (unsigned)S3_BLOCK;
+        buf_off = (unsigned)(buf - lds3);
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            trot[m] = tile_off + crot[m]; brot[m] = buf_off + (unsigned)(m * S3_BLOCK) + crot[m];
+            asm("" : "+s"(trot[m]), "+s"(brot[m]));                                 // (opaque: or the sums are re-associated and all formed at the top of the tile, 45 SGPRs)
+        }
+    };
+    auto issue_slots = [&](int f_lo, int f_hi) {                                   // (of the tile and into the buffer set_tile named)
 #ifdef S3_DBG_NODMA
         return;
+#endif
+#ifdef S3_DBG_DMA_WAVES
+        // TIMING-ONLY ablation (wrong results by construction, never the library's build): only the waves of this bit mask issue their copies.
+        // The mask is opaque, so every mask gives the same code -- 0xf (all, as the library), 0x1 (one wave), 0x0 (none) differ in nothing
+        // but which waves' copies reach the texture-address unit; the branch is in all three.
+        unsigned dma_mask = S3_DBG_DMA_WAVES;
+        asm volatile("" : "+s"(dma_mask));
+        if (!((dma_mask >> wave_u) & 1u)) return;
 #endif
 #pragma unroll
         for (int f = f_lo; f < f_hi; ++f) {
             if (f >= M * KMAX) break;                                               // compile time
             const int m = f / KMAX, k = f % KMAX;
-            const int rot = (wave_u + m) & (WAVES - 1);
-            int c = rot + k * WAVES;
-            if ((k + 1) * WAVES > NCH) c = c >= NCH ? c - WAVES : c;                // only the last k can fall off the block (scalar select)
-            if (LITE) c = c >= 2 * (S3_PLANE / 1024) ? c + S3_PLANE / 1024 : c;     // chunks 0..11 = h, m planes; 12..13 -> the tail image (18, 19)
-            // scalar base + 32-bit lane offset (the saddr form: no 64-bit VALU address per copy)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const unsigned char*>(tb[m] + (unsigned)(c * 1024)) + l16),
-                                             (__attribute__((address_space(3))) void*)(buf + m * S3_BLOCK + c * 1024), 16, 0, 0);
+            unsigned so, lo;
+            if (LAST_ODD && k == KMAX - 1) { so = tile_off + clast[m]; lo = buf_off + (unsigned)(m * S3_BLOCK) + clast[m]; }
+            else { so = trot[m] + (unsigned)(k * WAVES * 1024); lo = brot[m] + (unsigned)(k * WAVES * 1024); }
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[m], (lds_ptr)lds3 + lo, 16, l16, so, 0, 0);
         }
     };
-    auto issue = [&](int blk, unsigned char* buf) { set_tile(blk); issue_slots(buf, 0, M * KMAX); };
+    auto issue = [&](int jt, unsigned char* buf) { set_tile(jt, buf); issue_slots(0, M * KMAX); };
 
     // lane-derived LDS offsets: S product (lane-linear up to the swizzle) and the transpose reads of the gradient GEMM's B operand:
     // lane i of a 16-lane group addresses the 8-byte piece (row 8 g4 + 4 rd + (i >> 2), columns 16 ct + 4 (i & 3) ..)
@@ -427,6 +459,7 @@ __global__ __launch_bounds__(WV * 64, WV == 8 ? 2 : 1) void sweep3_kernel(TArgs 
     for (int sg = 0; sg < 2; ++sg) {
         if (sg >= grp.nseg) break;
         const TSeg seg = grp.seg[sg];
+        set_seg(seg);
         float c0[M + 1], c1[M + 1];
 #pragma unroll
         for (int m = 0; m <= M; ++m) {
@@ -445,7 +478,7 @@ __global__ __launch_bounds__(WV * 64, WV == 8 ? 2 : 1) void sweep3_kernel(TArgs 
         for (int m = 0; m < (LITE ? M + 1 : 1); ++m) { pl0[m] = 0.f; pl1[m] = 0.f; }
 
         __syncthreads();
-        if (seg.jt_lo + split < seg.jt_hi) issue(seg.blk0 + seg.jt_lo + split, lds3);
+        if (seg.jt_lo + split < seg.jt_hi) issue(seg.jt_lo + split, lds3);
         int it = 0;
 #pragma unroll 1
         for (int jt = seg.jt_lo + split; jt < seg.jt_hi; jt += nsplit, ++it) {
@@ -454,9 +487,9 @@ __global__ __launch_bounds__(WV * 64, WV == 8 ? 2 : 1) void sweep3_kernel(TArgs 
             S3_T(5)
             __syncthreads();                                   // tile `it` has landed (every wave waited for its own chunks), buffer it + 1 is free
             S3_T(0)
-            const int next_blk = seg.blk0 + (jt + nsplit < seg.jt_hi ? jt + nsplit : jt);      // (the last tile re-copies itself: see issue_slots)
+            const int next_jt = jt + nsplit < seg.jt_hi ? jt + nsplit : jt;                    // (the last tile re-copies itself: see issue_slots)
             unsigned char* next_buf = lds3 + ((it + 1) & 1) * BUF;
-            set_tile(next_blk);
+            set_tile(next_jt, next_buf);
             S3_T(1)
             if (GRAD) {
                 // A segment's first / last tile may hold rows outside [lo, hi) (uniform test).  Zeroing those rows' 16-byte slots in the
@@ -493,6 +526,12 @@ __global__ __launch_bounds__(WV * 64, WV == 8 ? 2 : 1) void sweep3_kernel(TArgs 
             // ss + 1 is requested right behind the FIRST MFMA of sub-step ss -- hipcc waits with s_waitcnt lgkmcnt(0) (never a counted wait:
             // the LDS-DMAs in flight make the counter "out of order" in its model) in front of the first MFMA that reads requested data, so
             // that one wait per sub-step must sit where nothing younger than 19 MFMAs is outstanding.
+            // (The buffer-form copies count on vmcnt alone, so hipcc now COULD count lgkmcnt -- and puts a counted wait in front of every MFMA that
+            // reads a requested operand, ~45 per tile, each an issue slot of a wave that has nobody to hide it.  One explicit lgkmcnt(0) at the top
+            // of a sub-step, where the youngest request is >= 10 MFMAs old, retires the whole set and the compiler emits none of its own.)
+            auto substep_wait = [&](int ss) {
+                if (ss > 0) { __builtin_amdgcn_s_waitcnt(0xc07f); __builtin_amdgcn_sched_barrier(0); }
+            };
             constexpr int NSET = PIPE ? 2 : 1;
             u32x4 at[NSET], ap[NSET][3][3];                    // ap[.][0]: h, [1]: m, [2]: l
             auto ld_one = [&](int ss, int idx) {               // idx 0: the tail image; 1 + 3 p' + q: plane l, m, h (p' = 0, 1, 2) K step q
@@ -535,6 +574,7 @@ __global__ __launch_bounds__(WV * 64, WV == 8 ? 2 : 1) void sweep3_kernel(TArgs 
                     const int m = ss % M, jh = ss / M, e = ss % NSET, pa = ss & 1;
                     const int pm = ss > 0 ? (ss - 1) % M : 0, pjh = ss > 0 ? (ss - 1) / M : 0;
                     accp[pa][0] = f32x4{0.f, 0.f, 0.f, 0.f}; accp[pa][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    substep_wait(ss);
 #pragma unroll
                     for (int x = 0; x < 20; ++x) {
                         if (x == 0) accp[pa][0] = mfma_b(at[e], otl[m][1], accp[pa][0]);
@@ -542,7 +582,7 @@ __global__ __launch_bounds__(WV * 64, WV == 8 ? 2 : 1) void sweep3_kernel(TArgs 
                         else accp[pa][x & 1] = mfma_b(ap[e][PA[(x - 2) / 3]][(x - 2) % 3], opl[m][PB[(x - 2) / 3]][(x - 2) % 3], accp[pa][x & 1]);
                         __builtin_amdgcn_sched_barrier(0);
                         if (ss + 1 < 2 * M && x < 10) ld_one(ss + 1, x);
-                        if (ss < NDS && (x % 3) == 1 && (x / 3) < PER) issue_slots(next_buf, ss * PER + (x / 3), ss * PER + (x / 3) + 1);
+                        if (ss < NDS && (x % 3) == 1 && (x / 3) < PER) issue_slots(ss * PER + (x / 3), ss * PER + (x / 3) + 1);
                         if (ss > 0) {
                             // the previous sub-step's similarities, then its own coefficient part: gaps 3 .. 18 but the copies' (1, 4, 7, 10, 13)
                             if (x == 0) { sacc[pm][pjh][0] = accp[pa ^ 1][0][0] + accp[pa ^ 1][1][0]; sacc[pm][pjh][1] = accp[pa ^ 1][0][1] + accp[pa ^ 1][1][1]; }
@@ -579,6 +619,7 @@ __global__ __launch_bounds__(WV * 64, WV == 8 ? 2 : 1) void sweep3_kernel(TArgs 
             for (int ss = 0; ss < 2 * M; ++ss) {
                 const int m = ss >> 1, jh = ss & 1, e = ss % NSET;
                 if (!PIPE) ld_set(ss);
+                if (PIPE) substep_wait(ss);
                 // 20 products, the small ones first, dealt alternately to TWO accumulator chains: between MFMAs on different accumulators
                 // another instruction costs its issue slot, between two dependent ones it breaks the back-to-back forwarding (+43 cycles,
                 // MI355X_MICROARCH.md) -- and a wave that is alone on its SIMD has to place 11 operand requests and up to 5 copies per
@@ -604,7 +645,7 @@ __global__ __launch_bounds__(WV * 64, WV == 8 ? 2 : 1) void sweep3_kernel(TArgs 
                     if (PIPE) {
                         __builtin_amdgcn_sched_barrier(0);
                         if (ss + 1 < 2 * M && x < 10 && !(LITE && x >= 1 && x <= 3)) ld_one(ss + 1, x);       // (LITE: not the l plane)
-                        if (ss < NDS && (x % 3) == 1 && (x / 3) < PER) issue_slots(next_buf, ss * PER + (x / 3), ss * PER + (x / 3) + 1);
+                        if (ss < NDS && (x % 3) == 1 && (x / 3) < PER) issue_slots(ss * PER + (x / 3), ss * PER + (x / 3) + 1);
                         // the previous table's own coefficient part under this table's MFMAs (half jh here): three VALU per gap 11 .. 18
                         if (OWN_IN_S && m > 0 && m - 1 < MG && x >= 11 && x < 19) {
                             const int r = (x - 11) >> 1;
@@ -618,7 +659,7 @@ __global__ __launch_bounds__(WV * 64, WV == 8 ? 2 : 1) void sweep3_kernel(TArgs 
                         }
                         __builtin_amdgcn_sched_barrier(0);
                     } else if (x == 1 && ss < NDS) {
-                        issue_slots(next_buf, ss * PER, (ss + 1) * PER);
+                        issue_slots(ss * PER, (ss + 1) * PER);
                     }
                 }
 #pragma unroll
@@ -867,6 +908,22 @@ __global__ __launch_bounds__(WV * 64, WV == 8 ? 2 : 1) void sweep3_kernel(TArgs 
     }
 }
 
+// The kernel: which group this workgroup serves, then the body.  Gamma is kept by the anchor-owner groups only (0, 1: each pair once); the
+// negative-owner groups (2, 3: half of all tiles) run the GAM = false body, which never forms it -- chosen HERE, once per workgroup and
+// uniformly, so that no branch lands inside the tile loop.
+template <int M, bool GRAD, int WV, int MG = M, bool GAM = true, bool LITE = false, bool FOLD = false>
+__global__ __launch_bounds__(WV * 64, WV == 8 ? 2 : 1) void sweep3_kernel(TArgs a) {
+    int g = 0;
+#pragma unroll
+    for (int i = 1; i < 4; ++i) if (i < a.ngroups && (int)blockIdx.x >= a.grp[i].blk0) g = i;
+#ifndef S3_GAM_ALL          // (experiment switch: every group forms Gamma, as before)
+    if constexpr (GRAD && GAM) {
+        if (g >= 2) { sweep3_body<M, GRAD, WV, MG, false, LITE, FOLD>(a, g); return; }
+    }
+#endif
+    sweep3_body<M, GRAD, WV, MG, GAM, LITE, FOLD>(a, g);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // The stash products of the anchors x anchors backward on the same three exact bf16 planes: out[own] += sum_oth C[own, oth] Z[oth], C a block
 // of the fp32 coefficient stash the A x A kernel wrote (replaces the four fp32-MFMA GEMMs of sga_loss_stash_grad_symx; the autograd of
@@ -1069,6 +1126,13 @@ int fill_t(TArgs& a, const void* const* Zb, int M, const float* beta, int A, int
         add(on2, J2, on2, bn2, X1f1, X2f2);
     }
     a.ngroups = g;
+    // the copies address a tile by a 32-bit byte offset from its segment's first block (sweep3_body: set_seg)
+    for (int i = 0; i < g; ++i)
+        for (int sg = 0; sg < a.grp[i].nseg; ++sg)
+            if ((long long)a.grp[i].seg[sg].jt_hi * S3_BLOCK >= (1LL << 32)) {
+                sga_set_error("%s: a segment of %d 32-row blocks exceeds the 4 GiB a copy descriptor spans", who, a.grp[i].seg[sg].jt_hi);
+                return SGA_ERR_ARG;
+            }
     // uniform work units; see sweep16_kernel (contrastive.hip) for the XCD argument
     int nwg = 0;
     for (int i = 0; i < g; ++i) {

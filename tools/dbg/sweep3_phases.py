@@ -1,5 +1,7 @@
 """Where a wave of sweep3_kernel spends its cycles (build with `python -m sgaligner_amd._build -DS3_DBG_TIMING` first; s_memtime stamps
-cost ~10 % themselves).  python tools/dbg/sweep3_phases.py [pairs=512] [objects=64]"""
+cost ~10 % themselves).  python tools/dbg/sweep3_phases.py [pairs=512] [objects=64]
+What the copies cost and how much of it is the four waves queueing behind one another: add -DS3_DBG_DMA_WAVES=0xf / 0x1 / 0x0 (all waves, wave 0
+only, nobody issues the copies -- identical code, timing only: the results of the last two are wrong) and compare the S phase's wave-cycles."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
