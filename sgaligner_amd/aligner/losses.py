@@ -1,6 +1,6 @@
 """Contrastive (ICL) + alignment (IAL) losses -- drop-in for reference src/aligner/losses.py
 (CustomMultiLossLayer :17-34, ICLLoss :36-58, IALLoss :60-97, OverallLoss :99-152) on the tiled HIP
-loss kernels (csrc/contrastive.hip).  The heavy op is ops.contrastive_terms, which returns the raw
+loss kernels (csrc/contrastive.hip, loss_anchor.hip, loss_pertable.hip).  The heavy op is ops.contrastive_terms, which returns the raw
 double-summed terms; what remains here is the reference's scalar arithmetic on 1-element tensors."""
 import torch
 from torch import nn

@@ -5,7 +5,7 @@
 // with the CPU reference run b pairs at a time (SURVEY.md 8d "loss grouping switch").
 //
 // A group is reference-sized (b in {2,4} pairs: <= ~150 anchors, <= ~400 negatives per side), so -- unlike the
-// batch-global loss in contrastive.hip -- its similarity blocks ARE materialised, per group and per modality table:
+// batch-global loss in contrastive.hip / loss_anchor.hip -- its similarity blocks ARE materialised, per group and per modality table:
 //     Sg [2 na, W],  W = na + nj1 + nj2,     rows 0..na-1 = X1_g (top), rows na..2na-1 = X2_g (bottom)
 //     top    row i : [ X1_i.X2_j (j < na) | X1_i.N1 | X1_i.N2 ]
 //     bottom row i : [ X2_i.X1_j (= S[j,i]) | X2_i.N1 | X2_i.N2 ]
@@ -56,7 +56,7 @@ __device__ __forceinline__ int col_z(const Grp& g, int A, int J1, int half, int 
     if (c < g.na + g.nj1) return 2 * A + g.j1 + (c - g.na);
     return 2 * A + J1 + g.j2 + (c - g.na - g.nj1);
 }
-// sum family of a negatives column for a row half: s11, s12 (top) / s22, s21 (bottom) -- contrastive.hip fill_groups
+// sum family of a negatives column for a row half: s11, s12 (top) / s22, s21 (bottom) -- sweep_groups.h fill_groups
 __device__ __forceinline__ int fam_of(const Grp& g, int half, int c) {
     const bool n1 = c < g.na + g.nj1;
     return half ? (n1 ? 3 : 2) : (n1 ? 0 : 1);
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(GL_THREADS) void group_bwd_kernel(GroupArgs a) {
 
     // ---- anchors x anchors: G_m[i,j] = dL/dS_m[i,j] (both roles of S[i,j]: the x of term (i,j), the y of term (j,i)) + beta_m dL/dS_J[i,j];
     //      written over the top-left block, the bottom-left (transposed duplicate) block becomes 0.  Same algebra as
-    //      contrastive.hip anchor_multi_bwd16_kernel.
+    //      loss_anchor.hip anchor_multi_bwd16_kernel.
     {
         float ags[NT * 8];
 #pragma unroll

@@ -1,0 +1,664 @@
+// Fused anchors x anchors pass of the contrastive / alignment loss (contrastive.hip describes the loss) for the "joint = fusion of the M
+// tables" case, M = 2..4, Dp == 104: the forward terms, and the backward that writes the dL/dS stashes, dL/d(sums) and dL/dbeta, in its
+// ordered and symmetric (every unordered pair once) forms; the stash products run on gemm.hip.  Every fused step of every MFMA mode ends here.
+#include "mfma_tiles.h"
+#include <type_traits>
+
+#include "loss_math.h"
+
+// gemm.hip (include/sgaligner_hip.h): the stash gradient of the anchors x anchors backward runs on the GEMM kernels
+extern "C" int sga_gemm(int transA, int transB, int M, int N, int K, const void* A, long lda, int a_is_f64, const float* B,
+                        long ldb, float* C, long ldc, const float* bias, int accumulate, void* stream);
+
+namespace {
+
+constexpr int CT_THREADS = 256;
+// ------------------------------------------------------------------------------------------------
+// Fused anchors x anchors kernel for the "joint = fusion of the M tables" case (Dp == 104).
+//
+// Same math as anchor_kernel, but S_J = sum_m beta_m S_m is derived in registers, so neither the 312-wide joint
+// operand nor its dL/dS stash exist: G_m = dL/dS_m + beta_m dL/dS_J is written directly, and Gamma_m = sum dL/dS_J S_m
+// (dL/dbeta) is accumulated on the side.  Geometry, chosen from the counters of anchor_kernel (49 % of wave time in
+// waitcnt/barrier on single-buffered K-chunk staging, 512 registers -> 1 wave/SIMD):
+//   * a workgroup owns 32 anchor rows I for ALL its J tiles: X1_I / X2_I of the M tables (2*M*13 KiB) are staged into
+//     LDS once and are the MFMA B operands (ds_read_b128), so "lane = anchor row i";
+//   * each of the 4 waves walks its own 32-row J tiles; the J-side operands go straight from global/L2 into MFMA
+//     A-operand fragments (one float4 per lane per 4 MFMAs) -- no staging, no barriers in the loop;
+//   * all 2*M S tiles of a (I,J) tile stay in registers (96 for M = 3), ~200 VGPRs total -> 2 waves per SIMD, so one
+//     wave's transcendental-heavy epilogue overlaps the other's MFMAs / loads.
+// ------------------------------------------------------------------------------------------------
+struct AnchorMultiArgs {
+    int M, A, i_lo, i_hi, nsplit;
+    const float* Z[4];
+    const float* beta;             // [M]
+    const double* sums;            // [(M+1)][8]
+    const float* inv;              // [(M+1)][8] = 1/(sums + 1e-9) as floats (inv_sums_kernel): uniform global loads -> SGPRs
+    float alpha, kc, ki, itc, iti;
+    double* out;                   // fwd: [(M+1) + 2M] (+ slots)
+    const float* coef;             // bwd: dL/d(out)
+    float* M1[4];                  // bwd: M1[m][j*ns + (i - i_lo)] = dL/dS_m[i,j] (+ beta_m dL/dS_J)
+    double* gs;                    // bwd: [(M+1)][8] (+ slots)
+    double* gamma;                 // bwd: [M] (+ slots)
+    int j_lo;                      // bwd: first column (a multiple of 16); stash rows are j - j_lo.  0 except in the symmetric mode
+    float* M2[4];                  // symmetric mode: M2[m][(j - mir)*ns + (i - i_lo)] = the MIRRORED coefficient dL/dS_m[j,i], j >= mir
+    int j_hi, mir;                 // symmetric mode: columns [j_lo, j_hi); tiles at j >= mir also produce the mirrored element (one GPU: A, i_hi)
+};
+
+template <int M>
+__global__ __launch_bounds__(CT_THREADS, M <= 3 ? 2 : 1) void anchor_multi_kernel(AnchorMultiArgs a) {
+    constexpr int DP = 104, NQ = 13, NT = M + 1;
+    extern __shared__ __attribute__((aligned(16))) float lds[];      // [M][2][32][DP] own rows + inv_s[NT*8]
+    float* inv_s = lds + M * 2 * 32 * DP;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, l31 = lane & 31;
+    const int A = a.A, ns = a.i_hi - a.i_lo;
+    const int ib = blockIdx.x / a.nsplit, split = blockIdx.x % a.nsplit;
+    const int i0 = a.i_lo + ib * 32;
+    const int my_i = i0 + l31;
+    const bool iv = my_i < a.i_hi;
+
+    // ---- stage the I block (rows past the shard end are clamped; masked in the epilogue)
+    for (int e = tid; e < M * 2 * 32 * (DP / 4); e += CT_THREADS) {
+        const int c = (e % (DP / 4)) * 4, r = (e / (DP / 4)) % 32, side = (e / (DP / 4) / 32) % 2, m = e / (DP / 4) / 64;
+        const int row = min(i0 + r, a.i_hi - 1) + side * A;
+        *reinterpret_cast<f32x4*>(lds + ((m * 2 + side) * 32 + r) * DP + c) = *reinterpret_cast<const f32x4*>(a.Z[m] + (size_t)row * DP + c);
+    }
+    for (int e = tid; e < NT * 8; e += CT_THREADS) inv_s[e] = (float)(1.0 / (a.sums[e] + 1e-9));
+    __syncthreads();
+    float beta[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) beta[m] = a.beta[m];
+
+    // per-lane partial sums: fp32 within a tile (16 elements), fp64 across this wave's tiles.  (All-fp32 partials lost 1.7e-4 of the IAL
+    // terms at configs[2] -- 19 456 nearly equal addends per lane round with a bias, not a random walk; tools/dbg/aa_check64.py.)
+    double acc_d[NT + 2 * M];
+#pragma unroll
+    for (int e = 0; e < NT + 2 * M; ++e) acc_d[e] = 0.0;
+
+    const int ntile = (A + 31) / 32;
+    for (int jt = split * 4 + wave; jt < ntile; jt += a.nsplit * 4) {
+        const int j0 = jt * 32;
+        float acc_out[NT + 2 * M];
+#pragma unroll
+        for (int e = 0; e < NT + 2 * M; ++e) acc_out[e] = 0.f;
+        const int jrow = min(j0 + l31, A - 1);                       // this lane's J row as an MFMA A-operand row
+        // ---- S tiles: P[m][r] = S_m[i = lane, j = j0 + row(r,h)],  Q[m][r] = S_m[j, i]
+        f32x16 P[M], Q[M];
+        zero_acc<M>(P);
+        zero_acc<M>(Q);
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            const float* gp = a.Z[m] + (size_t)(A + jrow) * DP + 4 * h;      // X2[j] for P
+            const float* gq = a.Z[m] + (size_t)jrow * DP + 4 * h;            // X1[j] for Q
+            const float* bp = lds + ((m * 2 + 0) * 32 + l31) * DP + 4 * h;   // X1[i]
+            const float* bq = lds + ((m * 2 + 1) * 32 + l31) * DP + 4 * h;   // X2[i]
+            // J-side fragments are prefetched exactly one K-group ahead into the other of two register pairs; the
+            // sched_barrier per group stops the scheduler from hoisting all 2*13 global loads of the table (spills).
+            f32x4 apA = *reinterpret_cast<const f32x4*>(gp), aqA = *reinterpret_cast<const f32x4*>(gq), apB = apA, aqB = aqA;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                if (q + 1 < NQ) {
+                    if (q & 1) { apA = *reinterpret_cast<const f32x4*>(gp + 8 * (q + 1)); aqA = *reinterpret_cast<const f32x4*>(gq + 8 * (q + 1)); }
+                    else { apB = *reinterpret_cast<const f32x4*>(gp + 8 * (q + 1)); aqB = *reinterpret_cast<const f32x4*>(gq + 8 * (q + 1)); }
+                }
+                const f32x4 b1 = *reinterpret_cast<const f32x4*>(bp + 8 * q);
+                const f32x4 b2 = *reinterpret_cast<const f32x4*>(bq + 8 * q);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    P[m] = __builtin_amdgcn_mfma_f32_32x32x2f32((q & 1) ? apB[r] : apA[r], b1[r], P[m], 0, 0, 0);
+                    Q[m] = __builtin_amdgcn_mfma_f32_32x32x2f32((q & 1) ? aqB[r] : aqA[r], b2[r], Q[m], 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        // From here on the S tiles are handled as SCALARS: in-place element updates of the 16-wide accumulator vectors
+        // (Q[m][r] = ...) make hipcc keep several versions of each vector alive -- >6 KB of scratch per lane.
+        float xs[M][16], ys[M][16];
+#pragma unroll
+        for (int m = 0; m < M; ++m)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { xs[m][r] = P[m][r]; ys[m][r] = Q[m][r]; }
+        // ---- epilogue, one element at a time (forward)
+        const float* js = inv_s + M * 8;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int j = j0 + mfma32_row(r, h);
+            const bool ok = iv && j < A;
+            float xj = 0.f, yj = 0.f;
+#pragma unroll
+            for (int m = 0; m < M; ++m) { xj = fmaf(beta[m], xs[m][r], xj); yj = fmaf(beta[m], ys[m][r], yj); }
+            {
+                const float dji = fexp2(xj * a.ki);
+                const float qma = g_val(dji, js[1], js[3]), qmb = g_val(dji, js[5], js[7]);
+                const float lqma = flog(qma), lqmb = flog(qmb);
+#pragma unroll
+                for (int k = 0; k < NT; ++k) {
+                    const float x = k < M ? xs[k < M ? k : 0][r] : xj, y = k < M ? ys[k < M ? k : 0][r] : yj;
+                    const float* is = inv_s + k * 8;
+                    const float qa = g_val(fexp2(x * a.kc), is[0], is[2]);
+                    const float qb = g_val(fexp2(y * a.kc), is[4], is[6]);
+                    const float term = -flog(a.alpha * qa + (1.f - a.alpha) * qb);
+                    acc_out[k] += ok ? term : 0.f;
+                    if (k < M) {
+                        const float dm = fexp2(x * a.ki);
+                        const float qoa = g_val(dm, is[1], is[3]), qob = g_val(dm, is[5], is[7]);
+                        const float ta = __expf(qoa) * (qoa - lqma), tb = __expf(qob) * (qob - lqmb);
+                        acc_out[NT + (k < M ? k : 0)] += ok ? ta : 0.f;
+                        acc_out[NT + M + (k < M ? k : 0)] += ok ? tb : 0.f;
+                    }
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < NT + 2 * M; ++e) asm volatile("" : "+v"(acc_out[e]));   // keep the updates out of the loop latch
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int e = 0; e < NT + 2 * M; ++e) acc_d[e] += (double)acc_out[e];
+    }
+    // ---- flush the wave's partial sums into its slot
+    const int slot = my_slot();
+#pragma unroll
+    for (int e = 0; e < NT + 2 * M; ++e) {
+        const double v = wave_sum_d(acc_d[e]);
+        if (lane == 0 && v != 0.0) atomicAdd(a.out + (NT + 2 * M) * (1 + slot) + e, v);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Backward of the fused anchors x anchors terms on 16x16x4 MFMA tiles.
+// The 32x32 form of this epilogue (16 elements per lane, 4 table-major passes, everything unrolled) is ~25 000
+// instructions in one loop body and hipcc's register allocator collapses on it (6 KB/lane of scratch, 50 ms).  With
+// v_mfma_f32_16x16x4_f32 a lane holds 4 elements of a 16x16 tile, the J loop stays ROLLED, and the body is 4x smaller:
+// no scratch, <= 128 registers.  Same geometry otherwise: 32 anchor rows of all M tables resident in LDS (MFMA B
+// operand, "lane & 15 = anchor row"), J-side fragments straight from global/L2, waves = (anchor half, J interleave).
+// ------------------------------------------------------------------------------------------------
+__global__ void inv_sums_kernel(const double* __restrict__ sums, float* __restrict__ inv, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) inv[i] = (float)(1.0 / (sums[i] + 1e-9));
+}
+
+// RB = anchor rows staged per workgroup: 32 (two wave pairs, each walking its own J tiles) for M <= 3; 16 for M = 4, where 32 rows of
+// four tables are 106 KiB of LDS = one workgroup per CU (all four waves then share the 16 rows and split the J tiles four ways).
+// TERMS: the same launch also accumulates the forward TERM values (what anchor_multi_kernel<M> returns): the epilogue already holds
+// every q they are made of, so a training step whose dL/d(terms) is known at forward time (ops.FusedContrastiveFn one-pass mode) runs the
+// A x A similarities once instead of twice.
+// SYM (M <= 3, TERMS): every UNORDERED anchor pair is visited once.  The block's rows [i_lo, i_hi) meet the columns j >= i_lo only; in a
+// tile right of the block (j >= i_hi) a lane holds x = S[i,j] and y = S[j,i] anyway, so it also produces the mirrored element (j, i) --
+// its terms, its sum gradients and its coefficient dL/dS[j,i], which goes to a second stash M2 -- instead of leaving it to the block that
+// owns row j.  The ICL halves of the two elements share every exp2 / g() evaluation and both denominators; the IAL halves are
+// independent.  Half the MFMAs and J-operand loads, ~0.78 of the VALU work per pair.  Tiles inside the block's own
+// column range (the diagonal square) run the ordinary epilogue.
+template <int M, bool TERMS = false, int RB = (M <= 3 ? 32 : 16), bool SYM = false>
+__global__ __launch_bounds__(CT_THREADS, 2) void anchor_multi_bwd16_kernel(AnchorMultiArgs a) {
+    static_assert(!SYM || TERMS, "symmetric mode: one-pass build");
+    constexpr int DP = 104, NT = M + 1, NSUB = RB / 16, TW = 4 / NSUB;
+    extern __shared__ __attribute__((aligned(16))) float lds[];      // [M][2][RB][DP] own rows
+    // The (M+1)*8 sum coefficients and the 3M+1 upstream coefficients are read from global memory at uniform addresses, per element
+    // of the epilogue (the compiler re-issues them as vector loads after every stash store: it cannot rule out aliasing).  Measured
+    // alternatives, 2048 x 155 648 block: as is 9.50 ms; loaded once before the loop (the compiler turns them into s_loads, 82 SGPRs)
+    // 10.43 ms; pinned in SGPRs by readfirstlane 11.05 ms -- two-SGPR-operand VALU forms do not exist on gfx9, so the uniform values
+    // cost v_movs in the arithmetic, more than the L1-hit loads they replace (tools/bench_aa.py).  As LDS reads each value cost an
+    // address VGPR + a data VGPR and pushed the kernel into scratch.
+    const float* __restrict__ inv_s = a.inv;
+    auto CF = [&](int e) { return a.coef[e]; };
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, l15 = lane & 15;
+    const int A = a.A, ns = a.i_hi - a.i_lo;
+    const int JH = SYM ? a.j_hi : A;                                 // column end (the symmetric walk of a rank stops where another rank's starts)
+    const int ib = blockIdx.x / a.nsplit, split = blockIdx.x % a.nsplit;
+    const int i0 = a.i_lo + ib * RB;
+    const int ih = wave % NSUB, tw = wave / NSUB;                    // which 16 anchor rows of the block / which share of the J tiles
+    const int my_i = i0 + ih * 16 + l15;
+    const bool iv = my_i < a.i_hi;
+
+    for (int e = tid; e < M * 2 * RB * (DP / 4); e += CT_THREADS) {
+        const int c = (e % (DP / 4)) * 4, r = (e / (DP / 4)) % RB, side = (e / (DP / 4) / RB) % 2, m = e / (DP / 4) / (2 * RB);
+        const int row = min(i0 + r, a.i_hi - 1) + side * A;
+        *reinterpret_cast<f32x4*>(lds + ((m * 2 + side) * RB + r) * DP + c) = *reinterpret_cast<const f32x4*>(a.Z[m] + (size_t)row * DP + c);
+    }
+    __syncthreads();
+    float beta[M];
+#pragma unroll
+    for (int m = 0; m < M; ++m) beta[m] = a.beta[m];
+
+    float acc_gs[NT][8], acc_gam[M];
+#pragma unroll
+    for (int k = 0; k < NT; ++k)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc_gs[k][e] = 0.f;
+#pragma unroll
+    for (int m = 0; m < M; ++m) acc_gam[m] = 0.f;
+    float acc_out[TERMS ? NT + 2 * M : 1];                           // TERMS: [ICL_0..M | IAL_a 0..M-1 | IAL_b 0..M-1] partial sums
+#pragma unroll
+    for (int e = 0; e < (TERMS ? NT + 2 * M : 1); ++e) acc_out[e] = 0.f;
+    int tiles_done = 0;
+    // All running sums are fp32 per lane and leave for the fp64 slots every 32 tiles (<= 128 addends per partial): at configs[2] a lane
+    // sees thousands of nearly equal addends, whose fp32 rounding is a bias, not a random walk (1.7e-4 on the IAL terms with
+    // whole-sweep fp32 partials; tools/dbg/aa_check64.py).
+    const int slot = my_slot();
+    auto flush = [&]() {
+        if (TERMS) {
+#pragma unroll
+            for (int e = 0; e < NT + 2 * M; ++e) {
+                const float v = wave_sum(acc_out[TERMS ? e : 0]);
+                if (lane == 0 && v != 0.f) atomicAdd(a.out + (NT + 2 * M) * (1 + slot) + e, (double)v);
+                acc_out[TERMS ? e : 0] = 0.f;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NT; ++k)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float iv2 = inv_s[k * 8 + e];
+                const float v = -iv2 * iv2 * wave_sum(acc_gs[k][e]);          // dg/dsum = -d inv^2 (g/u)^2: the uniform factor, once
+                if (lane == 0 && v != 0.f) atomicAdd(a.gs + NT * 8 * (1 + slot) + k * 8 + e, (double)v);
+                acc_gs[k][e] = 0.f;
+            }
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            const float v = wave_sum(acc_gam[m]);
+            if (lane == 0 && v != 0.f) atomicAdd(a.gamma + M * (1 + slot) + m, (double)v);
+            acc_gam[m] = 0.f;
+        }
+    };
+    const float* js = inv_s + M * 8;
+
+    const int ntile = (JH + 15) / 16;
+#pragma unroll 1
+    for (int jt = (a.j_lo >> 4) + split * TW + tw; jt < ntile; jt += a.nsplit * TW) {
+        const int j0 = jt * 16;
+        const int jrow = min(j0 + l15, A - 1);
+        // The anchor-row operands are loop invariant; left alone, LICM parks all M*2*26 of them in registers
+        // (156 for M = 3) and the kernel drops to one wave per SIMD with AGPR/scratch spills.  An opaque zero
+        // offset keeps the ds_reads inside the loop: ~100 registers, two waves per SIMD hide each other's loads.
+        int lofs = 0;
+        asm volatile("" : "+v"(lofs));
+        f32x4 P[M], Q[M];
+        // J-side operands of table m + 1 are requested (all 12 quads + tails) before table m's MFMAs start: a whole table of flight time
+        // for loads that come straight from L2 (compiler-scheduled two loads ahead: 12.80 ms per symmetric 2048 x 155 648 block; this: 12.39)
+        struct JOps { f32x4 p[6], q[6]; float pt[2], qt[2]; };
+        auto jload = [&](int m, JOps& o) {
+            const float* gp = a.Z[m] + (size_t)(A + jrow) * DP;              // X2[j] for P
+            const float* gq = a.Z[m] + (size_t)jrow * DP;                    // X1[j] for Q
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                o.p[q] = *reinterpret_cast<const f32x4*>(gp + 16 * q + 4 * g);
+                o.q[q] = *reinterpret_cast<const f32x4*>(gq + 16 * q + 4 * g);
+            }
+#pragma unroll
+            for (int t = 0; t < 2; ++t) { o.pt[t] = gp[96 + 4 * t + g]; o.qt[t] = gq[96 + 4 * t + g]; }
+        };
+        constexpr bool JDB = true;        // (M = 4, symmetric: 54 VGPRs go to scratch with or without the second buffer -- cold values, 2 reloads per element)
+        JOps jb[JDB ? 2 : 1];
+        jload(0, jb[0]);
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            if (JDB) { if (m + 1 < M) jload(m + 1, jb[JDB ? (m + 1) & 1 : 0]); }
+            else if (m > 0) jload(m, jb[0]);
+            __builtin_amdgcn_sched_barrier(0);
+            P[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+            Q[m] = P[m];
+            const JOps& o = jb[JDB ? m & 1 : 0];
+            const float* bp = lds + lofs + ((m * 2 + 0) * RB + ih * 16 + l15) * DP;   // X1[i]
+            const float* bq = lds + lofs + ((m * 2 + 1) * RB + ih * 16 + l15) * DP;   // X2[i]
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {                                    // k = 16q + 4g + r
+                const f32x4 b1 = *reinterpret_cast<const f32x4*>(bp + 16 * q + 4 * g);
+                const f32x4 b2 = *reinterpret_cast<const f32x4*>(bq + 16 * q + 4 * g);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    P[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(o.p[q][r], b1[r], P[m], 0, 0, 0);
+                    Q[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(o.q[q][r], b2[r], Q[m], 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int kk = 96 + 4 * t + g;
+                P[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(o.pt[t], bp[kk], P[m], 0, 0, 0);
+                Q[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(o.qt[t], bq[kk], Q[m], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // P[m][r] = S_m[i = lane&15, j = j0 + 4g + r], Q[m][r] = S_m[j, i].  One element (r) at a time, with a
+        // scheduling barrier between elements: interleaving the four independent chains keeps ~4x the temporaries
+        // live and pushes the loop into scratch.  Masks are multiplied in (rows/columns past the end are clamped
+        // copies of valid rows, so every intermediate is finite) -- selects here become 28 exec-mask branches.
+        // Interior tiles (all 16 anchor rows and all 16 columns valid: everything but the last row block / column tile) run the
+        // mask-free instantiation -- the ~20 multiplications by okf and the predicated stores are 4 % of this VALU-bound loop.
+        const float cJ = CF(M);
+        auto epilogue = [&](auto masked_c) {
+        constexpr bool MASKED = decltype(masked_c)::value;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int j = j0 + 4 * g + r;
+            const bool ok = !MASKED || (iv && (j < JH));
+            const float okf = (!MASKED || ok) ? 1.f : 0.f;
+            float xj = 0.f, yj = 0.f;
+#pragma unroll
+            for (int m = 0; m < M; ++m) { xj = fmaf(beta[m], P[m][r], xj); yj = fmaf(beta[m], Q[m][r], yj); }
+            float gJ, EA = 0.f, EB = 0.f;
+            // joint ICL
+            {
+                const float dx = fexp2(xj * a.kc), dy = fexp2(yj * a.kc);
+                const GP Ax = g_parts(dx, js[0], js[2]), Bx = g_parts(dx, js[4], js[6]);
+                const float qAy = g_val(dy, js[0], js[2]), qBy = g_val(dy, js[4], js[6]);
+                const float denA = a.alpha * Ax.q + (1.f - a.alpha) * qBy;
+                const float wA = okf * (-cJ * a.alpha) * frcp(denA) * dx;      // weight * d
+                const float wB = okf * (-cJ * (1.f - a.alpha)) * frcp(a.alpha * qAy + (1.f - a.alpha) * Bx.q) * dx;
+                if (TERMS) acc_out[TERMS ? M : 0] = fmaf(okf, -flog(denA), acc_out[TERMS ? M : 0]);     // -log(a qA(x) + (1-a) qB(y)), losses.py:55-57
+                gJ = fmaf(wA, Ax.dd, wB * Bx.dd) * a.itc;
+                acc_gs[M][0] = fmaf(wA, Ax.p, acc_gs[M][0]); acc_gs[M][2] = fmaf(wA, Ax.r, acc_gs[M][2]);
+                acc_gs[M][4] = fmaf(wB, Bx.p, acc_gs[M][4]); acc_gs[M][6] = fmaf(wB, Bx.r, acc_gs[M][6]);
+            }
+            // joint IAL reference distribution (qm), shared by every modality
+            const float dji = fexp2(xj * a.ki);
+            const GP MA = g_parts(dji, js[1], js[3]), MB = g_parts(dji, js[5], js[7]);
+            const float lqma = flog(MA.q), lqmb = flog(MB.q);
+            float gx[M];
+            // per modality ICL + IAL (qo part)
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+                const float* is = inv_s + m * 8;
+                const float c = CF(m), ca = CF(NT + m), cb = CF(NT + M + m);
+                const float x = P[m][r], y = Q[m][r];
+                const float dx = fexp2(x * a.kc), dy = fexp2(y * a.kc);
+                const GP Ax = g_parts(dx, is[0], is[2]), Bx = g_parts(dx, is[4], is[6]);
+                const float qAy = g_val(dy, is[0], is[2]), qBy = g_val(dy, is[4], is[6]);
+                const float denA = a.alpha * Ax.q + (1.f - a.alpha) * qBy;
+                const float wA = okf * (-c * a.alpha) * frcp(denA) * dx;
+                const float wB = okf * (-c * (1.f - a.alpha)) * frcp(a.alpha * qAy + (1.f - a.alpha) * Bx.q) * dx;
+                if (TERMS) acc_out[TERMS ? m : 0] = fmaf(okf, -flog(denA), acc_out[TERMS ? m : 0]);
+                float gxm = fmaf(wA, Ax.dd, wB * Bx.dd) * a.itc;
+                acc_gs[m][0] = fmaf(wA, Ax.p, acc_gs[m][0]); acc_gs[m][2] = fmaf(wA, Ax.r, acc_gs[m][2]);
+                acc_gs[m][4] = fmaf(wB, Bx.p, acc_gs[m][4]); acc_gs[m][6] = fmaf(wB, Bx.r, acc_gs[m][6]);
+                const float dm = fexp2(x * a.ki);
+                const GP OA = g_parts(dm, is[1], is[3]), OB = g_parts(dm, is[5], is[7]);
+                const float xA = okf * __expf(OA.q), xB = okf * __expf(OB.q);
+                const float eA = ca * xA, eB = cb * xB;
+                if (TERMS) {                                                       // exp(qo) (qo - log qm): KLDiv with log_target, losses.py:90-94
+                    acc_out[TERMS ? NT + m : 0] = fmaf(xA, OA.q - lqma, acc_out[TERMS ? NT + m : 0]);
+                    acc_out[TERMS ? NT + M + m : 0] = fmaf(xB, OB.q - lqmb, acc_out[TERMS ? NT + M + m : 0]);
+                }
+                const float tA = eA * (OA.q - lqma + 1.f) * dm, tB = eB * (OB.q - lqmb + 1.f) * dm;
+                gxm = fmaf(fmaf(tA, OA.dd, tB * OB.dd), a.iti, gxm);
+                acc_gs[m][1] = fmaf(tA, OA.p, acc_gs[m][1]); acc_gs[m][3] = fmaf(tA, OA.r, acc_gs[m][3]);
+                acc_gs[m][5] = fmaf(tB, OB.p, acc_gs[m][5]); acc_gs[m][7] = fmaf(tB, OB.r, acc_gs[m][7]);
+                EA += eA; EB += eB;
+                gx[m] = gxm;
+            }
+            // joint IAL (qm part), totals + stash
+            {
+                const float uA = -EA * frcp(MA.q) * dji, uB = -EB * frcp(MB.q) * dji;
+                gJ = fmaf(fmaf(uA, MA.dd, uB * MB.dd), a.iti, gJ);
+                acc_gs[M][1] = fmaf(uA, MA.p, acc_gs[M][1]); acc_gs[M][3] = fmaf(uA, MA.r, acc_gs[M][3]);
+                acc_gs[M][5] = fmaf(uB, MB.p, acc_gs[M][5]); acc_gs[M][7] = fmaf(uB, MB.r, acc_gs[M][7]);
+            }
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+                acc_gam[m] = fmaf(gJ, P[m][r], acc_gam[m]);
+                if (ok) a.M1[m][(size_t)(j - a.j_lo) * ns + (my_i - a.i_lo)] = fmaf(beta[m], gJ, gx[m]);
+            }
+            // pin the running sums here: otherwise their updates are sunk into the loop latch (they are only
+            // consumed by the next iteration) and every factor of all four elements stays live until then
+#pragma unroll
+            for (int k = 0; k < NT; ++k)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) asm volatile("" : "+v"(acc_gs[k][e]));
+#pragma unroll
+            for (int m = 0; m < M; ++m) asm volatile("" : "+v"(acc_gam[m]));
+            if (TERMS) {
+#pragma unroll
+                for (int e = 0; e < NT + 2 * M; ++e) asm volatile("" : "+v"(acc_out[TERMS ? e : 0]));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        };
+        // Symmetric epilogue: elements (i, j) [x = P, "dir 0", stash M1] and (j, i) [y = Q, "dir 1", stash M2] together.
+        auto epilogue_sym = [&](auto) {      // generic: only instantiated where it is called
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int j = j0 + 4 * g + r;
+            const bool ok = iv && (j < JH);
+            const float okf = ok ? 1.f : 0.f;
+            float xj = 0.f, yj = 0.f;
+#pragma unroll
+            for (int m = 0; m < M; ++m) { xj = fmaf(beta[m], P[m][r], xj); yj = fmaf(beta[m], Q[m][r], yj); }
+            float gci[NT][2];                                        // ICL part of dL/dx, dL/dy per table (joint = M)
+            // ---- ICL, every table and the joint: term(i,j) = -log(a qA(x) + (1-a) qB(y)), term(j,i) = -log(a qA(y) + (1-a) qB(x))
+#pragma unroll
+            for (int k = 0; k < NT; ++k) {
+                const float* is = inv_s + k * 8;
+                const float x = k < M ? P[k < M ? k : 0][r] : xj, y = k < M ? Q[k < M ? k : 0][r] : yj;
+                const float c = CF(k);
+                const float dx = fexp2(x * a.kc), dy = fexp2(y * a.kc);
+                const GP Ax = g_parts(dx, is[0], is[2]), Bx = g_parts(dx, is[4], is[6]);
+                const GP Ay = g_parts(dy, is[0], is[2]), By = g_parts(dy, is[4], is[6]);
+                const float den1 = a.alpha * Ax.q + (1.f - a.alpha) * By.q;
+                const float den2 = a.alpha * Ay.q + (1.f - a.alpha) * Bx.q;
+                const float r1 = okf * -c * frcp(den1), r2 = okf * -c * frcp(den2);
+                const float wAx = a.alpha * r1 * dx, wBx = (1.f - a.alpha) * r2 * dx;
+                const float wAy = a.alpha * r2 * dy, wBy = (1.f - a.alpha) * r1 * dy;
+                acc_out[TERMS ? k : 0] = fmaf(okf, -(flog(den1) + flog(den2)), acc_out[TERMS ? k : 0]);
+                gci[k][0] = fmaf(wAx, Ax.dd, wBx * Bx.dd) * a.itc;
+                gci[k][1] = fmaf(wAy, Ay.dd, wBy * By.dd) * a.itc;
+                acc_gs[k][0] = fmaf(wAx, Ax.p, fmaf(wAy, Ay.p, acc_gs[k][0])); acc_gs[k][2] = fmaf(wAx, Ax.r, fmaf(wAy, Ay.r, acc_gs[k][2]));
+                acc_gs[k][4] = fmaf(wBx, Bx.p, fmaf(wBy, By.p, acc_gs[k][4])); acc_gs[k][6] = fmaf(wBx, Bx.r, fmaf(wBy, By.r, acc_gs[k][6]));
+#pragma unroll
+                for (int e = 0; e < 8; e += 2) asm volatile("" : "+v"(acc_gs[k][e]));
+                asm volatile("" : "+v"(acc_out[TERMS ? k : 0]));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            // ---- IAL, one direction at a time (nothing shared between x and y here)
+#pragma unroll
+            for (int dir = 0; dir < 2; ++dir) {
+                const float vj = dir ? yj : xj;
+                const float dji = fexp2(vj * a.ki);
+                const GP MA = g_parts(dji, js[1], js[3]), MB = g_parts(dji, js[5], js[7]);
+                const float lqma = flog(MA.q), lqmb = flog(MB.q);
+                float gx[M], EA = 0.f, EB = 0.f;
+#pragma unroll
+                for (int m = 0; m < M; ++m) {
+                    const float* is = inv_s + m * 8;
+                    const float ca = CF(NT + m), cb = CF(NT + M + m);
+                    const float v = dir ? Q[m][r] : P[m][r];
+                    const float dm = fexp2(v * a.ki);
+                    const GP OA = g_parts(dm, is[1], is[3]), OB = g_parts(dm, is[5], is[7]);
+                    const float xA = okf * __expf(OA.q), xB = okf * __expf(OB.q);
+                    const float eA = ca * xA, eB = cb * xB;
+                    acc_out[TERMS ? NT + m : 0] = fmaf(xA, OA.q - lqma, acc_out[TERMS ? NT + m : 0]);
+                    acc_out[TERMS ? NT + M + m : 0] = fmaf(xB, OB.q - lqmb, acc_out[TERMS ? NT + M + m : 0]);
+                    const float tA = eA * (OA.q - lqma + 1.f) * dm, tB = eB * (OB.q - lqmb + 1.f) * dm;
+                    gx[m] = fmaf(fmaf(tA, OA.dd, tB * OB.dd), a.iti, gci[m][dir]);
+                    acc_gs[m][1] = fmaf(tA, OA.p, acc_gs[m][1]); acc_gs[m][3] = fmaf(tA, OA.r, acc_gs[m][3]);
+                    acc_gs[m][5] = fmaf(tB, OB.p, acc_gs[m][5]); acc_gs[m][7] = fmaf(tB, OB.r, acc_gs[m][7]);
+                    EA += eA; EB += eB;
+                }
+                const float uA = -EA * frcp(MA.q) * dji, uB = -EB * frcp(MB.q) * dji;
+                const float gJ = fmaf(fmaf(uA, MA.dd, uB * MB.dd), a.iti, gci[M][dir]);
+                acc_gs[M][1] = fmaf(uA, MA.p, acc_gs[M][1]); acc_gs[M][3] = fmaf(uA, MA.r, acc_gs[M][3]);
+                acc_gs[M][5] = fmaf(uB, MB.p, acc_gs[M][5]); acc_gs[M][7] = fmaf(uB, MB.r, acc_gs[M][7]);
+                float* const* dst = dir ? a.M2 : a.M1;
+                const size_t off = (size_t)(j - (dir ? a.mir : a.j_lo)) * ns + (my_i - a.i_lo);
+#pragma unroll
+                for (int m = 0; m < M; ++m) {
+                    acc_gam[m] = fmaf(gJ, dir ? Q[m][r] : P[m][r], acc_gam[m]);
+                    if (ok) dst[m][off] = fmaf(beta[m], gJ, gx[m]);
+                }
+#pragma unroll
+                for (int k = 0; k < NT; ++k)
+#pragma unroll
+                    for (int e = 1; e < 8; e += 2) asm volatile("" : "+v"(acc_gs[k][e]));
+#pragma unroll
+                for (int m = 0; m < M; ++m) asm volatile("" : "+v"(acc_gam[m]));
+#pragma unroll
+                for (int e = NT; e < NT + 2 * M; ++e) asm volatile("" : "+v"(acc_out[TERMS ? e : 0]));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        };
+        if constexpr (SYM) {
+            if (j0 >= a.mir) epilogue_sym(0); else epilogue(std::true_type{});                               // uniform
+        } else {
+            if (j0 + 16 <= A && i0 + RB <= a.i_hi) epilogue(std::false_type{}); else epilogue(std::true_type{});   // uniform
+        }
+        if ((++tiles_done & (SYM ? 15 : 31)) == 0) flush();          // uniform
+    }
+    flush();
+}
+
+}  // namespace
+
+// ---- fused anchors x anchors entry points -------------------------------------------------------------------------
+static int fill_anchor_multi(AnchorMultiArgs& a, const float* const* Z, int M, const float* beta, int A, const double* sums,
+                             float alpha, float tau_icl, float tau_ial, int a_lo, int a_hi) {
+    if (M < 2 || M > 4) { sga_set_error("sga_loss_anchor_multi: M=%d not in {2,3,4} (use the per-table kernels)", M); return SGA_ERR_ARG; }
+    if (a_lo < 0 || a_hi > A || a_lo > a_hi) { sga_set_error("sga_loss_anchor_multi: anchor shard [%d,%d) outside [0,%d]", a_lo, a_hi, A); return SGA_ERR_ARG; }
+    a.M = M; a.A = A; a.i_lo = a_lo; a.i_hi = a_hi; a.beta = beta; a.sums = sums; a.alpha = alpha;
+    a.kc = LOG2E / tau_icl; a.ki = LOG2E / tau_ial; a.itc = 1.f / tau_icl; a.iti = 1.f / tau_ial;
+    for (int m = 0; m < M; ++m) { if (!Z[m]) { sga_set_error("sga_loss_anchor_multi: null table"); return SGA_ERR_ARG; } a.Z[m] = Z[m]; }
+    const int nib = (a_hi - a_lo + 31) / 32, ntile = (A + 31) / 32;
+    int ns = (4 * sga_num_cus() + nib - 1) / (nib > 0 ? nib : 1);
+    if (ns > (ntile + 3) / 4) ns = (ntile + 3) / 4;
+    if (ns < 1) ns = 1;
+    a.nsplit = ns;
+    return SGA_OK;
+}
+
+template <int M>
+static void launch_anchor_multi(const AnchorMultiArgs& a, hipStream_t s) {
+    const size_t lds = (size_t)(M * 2 * 32 * 104 + (M + 1) * 8) * sizeof(float);
+    auto k = anchor_multi_kernel<M>;
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const int nib = (a.i_hi - a.i_lo + 31) / 32;
+    hipLaunchKernelGGL(k, dim3(nib * a.nsplit), dim3(CT_THREADS), lds, s, a);
+}
+
+extern "C" int sga_loss_anchor_multi_fwd(const float* const* Z, int M, const float* beta, int A, const double* sums,
+                                         float alpha, float tau_icl, float tau_ial, double* out, int a_lo, int a_hi,
+                                         void* stream) {
+    SGA_CHECK_ARG(Z && beta && sums && out && A >= 0, "sga_loss_anchor_multi_fwd: bad argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int n = (M + 1) + 2 * M;
+    if (int rc0 = zero_slots(out, n, s, "sga_loss_anchor_multi_fwd")) return rc0;
+    if (A == 0 || a_hi <= a_lo) return SGA_OK;
+    AnchorMultiArgs a{};
+    int rc = fill_anchor_multi(a, Z, M, beta, A, sums, alpha, tau_icl, tau_ial, a_lo, a_hi);
+    if (rc) return rc;
+    a.out = out;
+    if (M == 2) launch_anchor_multi<2>(a, s); else if (M == 3) launch_anchor_multi<3>(a, s); else launch_anchor_multi<4>(a, s);
+    fold_slots(out, n, s);
+    SGA_CHECK_LAUNCH("sga_loss_anchor_multi_fwd");
+    return SGA_OK;
+}
+
+// The backward launch over the columns [j_lo, j_hi) for a block whose shard, tables, coefficients, outputs and stashes are set (tiles at
+// j >= mir also produce the mirrored element when sym): 1/(sums + eps), the split plan, the kernel, the folds.  TERMS follows a.out.
+static void launch_anchor_multi_bwd(AnchorMultiArgs& a, int j_lo, int j_hi, int mir, bool sym, hipStream_t s) {
+    const int M = a.M;
+    a.j_lo = j_lo; a.j_hi = j_hi; a.mir = mir;
+    // float copy of 1/(sums+eps): lives in the block after the gs slots (gs buffers hold (2 + slots) * (M+1)*8 doubles)
+    float* inv = reinterpret_cast<float*>(a.gs + (size_t)(1 + SGA_SLOTS) * (M + 1) * 8);
+    hipLaunchKernelGGL(inv_sums_kernel, dim3(1), dim3(64), 0, s, a.sums, inv, (M + 1) * 8);
+    a.inv = inv;
+    const int RB = M <= 3 ? 32 : 16, TW = M <= 3 ? 2 : 4;
+    const size_t lds = (size_t)(M * 2 * RB * 104 + (M + 1) * 8) * sizeof(float);
+    const int nib = (a.i_hi - a.i_lo + RB - 1) / RB, ntile16 = (j_hi - j_lo + 15) / 16;
+    int nsp = (6 * sga_num_cus() + nib - 1) / nib;
+    if (nsp > (ntile16 + TW - 1) / TW) nsp = (ntile16 + TW - 1) / TW;
+    if (nsp < 1) nsp = 1;
+    a.nsplit = nsp;
+    auto go = [&](auto k) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(k, dim3(nib * nsp), dim3(CT_THREADS), lds, s, a);
+    };
+    if (sym) { if (M == 2) go(anchor_multi_bwd16_kernel<2, true, 32, true>); else if (M == 3) go(anchor_multi_bwd16_kernel<3, true, 32, true>); else go(anchor_multi_bwd16_kernel<4, true, 16, true>); }
+    else if (a.out) { if (M == 2) go(anchor_multi_bwd16_kernel<2, true>); else if (M == 3) go(anchor_multi_bwd16_kernel<3, true>); else go(anchor_multi_bwd16_kernel<4, true>); }
+    else { if (M == 2) go(anchor_multi_bwd16_kernel<2, false>); else if (M == 3) go(anchor_multi_bwd16_kernel<3, false>); else go(anchor_multi_bwd16_kernel<4, false>); }
+    if (a.out) fold_slots(a.out, (M + 1) + 2 * M, s);
+    fold_slots(a.gs, (M + 1) * 8, s);
+    fold_slots(a.gamma, M, s);
+}
+
+extern "C" int sga_loss_anchor_multi_bwd(const float* const* Z, int M, const float* beta, int A, const double* sums,
+                                         float alpha, float tau_icl, float tau_ial, const float* coef, float* const* M1,
+                                         double* gs, double* gamma, int a_lo, int a_hi, double* out_terms, void* stream) {
+    SGA_CHECK_ARG(Z && beta && sums && coef && M1 && gs && gamma && A >= 0, "sga_loss_anchor_multi_bwd: bad argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc0 = zero_slots(gs, (M + 1) * 8, s, "sga_loss_anchor_multi_bwd")) return rc0;
+    if (int rc1 = zero_slots(gamma, M, s, "sga_loss_anchor_multi_bwd")) return rc1;
+    if (out_terms) { if (int rc2 = zero_slots(out_terms, (M + 1) + 2 * M, s, "sga_loss_anchor_multi_bwd")) return rc2; }
+    if (A == 0 || a_hi <= a_lo) return SGA_OK;
+    AnchorMultiArgs a{};
+    int rc = fill_anchor_multi(a, Z, M, beta, A, sums, alpha, tau_icl, tau_ial, a_lo, a_hi);
+    if (rc) return rc;
+    a.coef = coef; a.gs = gs; a.gamma = gamma; a.out = out_terms;
+    for (int m = 0; m < M; ++m) { SGA_CHECK_ARG(M1[m], "sga_loss_anchor_multi_bwd: null stash"); a.M1[m] = M1[m]; }
+    launch_anchor_multi_bwd(a, 0, A, A, false, s);
+    SGA_CHECK_LAUNCH("sga_loss_anchor_multi_bwd");
+    return SGA_OK;
+}
+
+/* Symmetric form of sga_loss_anchor_multi_bwd for an UNSHARDED anchor set walked in blocks (M = 2, 3; terms always returned): block
+ * [a_lo, a_hi) meets the columns j >= a_lo only and also produces the mirrored elements (j, i), j >= a_hi, i in the block, so every
+ * unordered pair is evaluated once over the whole walk.  a_lo must be a multiple of 32, a_hi a multiple of 32 or == A.
+ *   M1[m][(j - a_lo) * ns + (i - a_lo)] = dL/dS_m[i, j],  j in [a_lo, A)          ([A - a_lo, ns] floats)
+ *   M2[m][(j - a_hi) * ns + (i - a_lo)] = dL/dS_m[j, i],  j in [a_hi, A)          ([A - a_hi, ns] floats)
+ * out_terms / gs / gamma as in sga_loss_anchor_multi_bwd: this block's share (both elements of every pair it visits). */
+extern "C" int sga_loss_anchor_multi_bwd_symx(const float* const* Z, int M, const float* beta, int A, const double* sums, float alpha,
+                                              float tau_icl, float tau_ial, const float* coef, float* const* M1, float* const* M2,
+                                              double* gs, double* gamma, int a_lo, int a_hi, int j_lo, int j_hi, int mir, double* out_terms,
+                                              void* stream) {
+    SGA_CHECK_ARG(Z && beta && sums && coef && M1 && M2 && gs && gamma && out_terms && A >= 0, "sga_loss_anchor_multi_bwd_symx: bad argument");
+    SGA_CHECK_ARG(M >= 2 && M <= 4, "sga_loss_anchor_multi_bwd_symx: M=%d (2, 3 or 4)", M);
+    SGA_CHECK_ARG(a_lo % 32 == 0 && (a_hi % 32 == 0 || a_hi == A), "sga_loss_anchor_multi_bwd_symx: block [%d,%d) not on 32-row boundaries", a_lo, a_hi);
+    SGA_CHECK_ARG(j_lo >= 0 && j_lo % 16 == 0 && j_hi <= A && j_lo <= j_hi && (j_hi % 16 == 0 || j_hi == A) && mir >= j_lo && (mir % 16 == 0 || mir >= j_hi),
+                  "sga_loss_anchor_multi_bwd_symx: columns [%d,%d) / mirror start %d not on 16-column boundaries", j_lo, j_hi, mir);
+    // columns left of the mirror start are visited in the ordered way: they must lie in the block's own square
+    SGA_CHECK_ARG(mir <= j_lo || (j_lo >= a_lo && (mir < j_hi ? mir : j_hi) <= a_hi), "sga_loss_anchor_multi_bwd_symx: ordered columns [%d,%d) outside the block's square [%d,%d)",
+                  j_lo, mir, a_lo, a_hi);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc0 = zero_slots(gs, (M + 1) * 8, s, "sga_loss_anchor_multi_bwd_symx")) return rc0;
+    if (int rc1 = zero_slots(gamma, M, s, "sga_loss_anchor_multi_bwd_symx")) return rc1;
+    if (int rc2 = zero_slots(out_terms, (M + 1) + 2 * M, s, "sga_loss_anchor_multi_bwd_symx")) return rc2;
+    if (A == 0 || a_hi <= a_lo || j_hi <= j_lo) return SGA_OK;
+    AnchorMultiArgs a{};
+    int rc = fill_anchor_multi(a, Z, M, beta, A, sums, alpha, tau_icl, tau_ial, a_lo, a_hi);
+    if (rc) return rc;
+    a.coef = coef; a.gs = gs; a.gamma = gamma; a.out = out_terms;
+    for (int m = 0; m < M; ++m) {
+        SGA_CHECK_ARG(M1[m] && (M2[m] || mir >= j_hi), "sga_loss_anchor_multi_bwd_symx: null stash");
+        a.M1[m] = M1[m]; a.M2[m] = M2[m];
+    }
+    launch_anchor_multi_bwd(a, j_lo, j_hi, mir, true, s);
+    SGA_CHECK_LAUNCH("sga_loss_anchor_multi_bwd_symx");
+    return SGA_OK;
+}
+
+extern "C" int sga_loss_anchor_multi_bwd_sym(const float* const* Z, int M, const float* beta, int A, const double* sums, float alpha,
+                                             float tau_icl, float tau_ial, const float* coef, float* const* M1, float* const* M2,
+                                             double* gs, double* gamma, int a_lo, int a_hi, double* out_terms, void* stream) {
+    return sga_loss_anchor_multi_bwd_symx(Z, M, beta, A, sums, alpha, tau_icl, tau_ial, coef, M1, M2, gs, gamma, a_lo, a_hi, a_lo, A, a_hi, out_terms, stream);
+}
+
+/* The four products of a symmetric block's two stashes for one table (Z = [X1 | X2 | ...] rows of width Dp; R = [a_lo, a_hi), C = [j_lo, j_hi),
+ * C' = [mir, j_hi)):    dX1[R] += M1^T X2[C]     dX2[C] += M1 X1[R]     dX1[C'] += M2 X2[R]     dX2[R] += M2^T X1[C'] */
+extern "C" int sga_loss_stash_grad_symx(const float* M1, const float* M2, const float* Z, int A, int Dp, float* dZ, int a_lo, int a_hi,
+                                        int j_lo, int j_hi, int mir, void* stream) {
+    SGA_CHECK_ARG(M1 && Z && dZ && A >= 0 && Dp >= 8 && Dp % 8 == 0 && a_lo >= 0 && a_hi <= A && a_lo <= a_hi && j_lo >= 0 && j_lo <= j_hi && j_hi <= A &&
+                  mir >= j_lo && (M2 || mir >= j_hi), "sga_loss_stash_grad_symx: bad argument");
+    const int ns = a_hi - a_lo, c1 = j_hi - j_lo, c2 = mir < j_hi ? j_hi - mir : 0;
+    if (A == 0 || ns == 0 || c1 == 0) return SGA_OK;
+    // (a last block whose row count is not a multiple of 4 takes sga_gemm's general kernel: correct, slower)
+    const float* X1 = Z;
+    const float* X2 = Z + (size_t)A * Dp;
+    float* d1 = dZ;
+    float* d2 = dZ + (size_t)A * Dp;
+    int rc = sga_gemm(1, 0, ns, Dp, c1, M1, ns, 0, X2 + (size_t)j_lo * Dp, Dp, d1 + (size_t)a_lo * Dp, Dp, nullptr, 1, stream);
+    if (!rc) rc = sga_gemm(0, 0, c1, Dp, ns, M1, ns, 0, X1 + (size_t)a_lo * Dp, Dp, d2 + (size_t)j_lo * Dp, Dp, nullptr, 1, stream);
+    if (!rc && c2 > 0) rc = sga_gemm(0, 0, c2, Dp, ns, M2, ns, 0, X2 + (size_t)a_lo * Dp, Dp, d1 + (size_t)mir * Dp, Dp, nullptr, 1, stream);
+    if (!rc && c2 > 0) rc = sga_gemm(1, 0, ns, Dp, c2, M2, ns, 0, X1 + (size_t)mir * Dp, Dp, d2 + (size_t)a_lo * Dp, Dp, nullptr, 1, stream);
+    return rc;
+}
+
+extern "C" int sga_loss_stash_grad_sym(const float* M1, const float* M2, const float* Z, int A, int Dp, float* dZ, int a_lo, int a_hi,
+                                       void* stream) {
+    return sga_loss_stash_grad_symx(M1, M2, Z, A, Dp, dZ, a_lo, a_hi, a_lo, A, a_hi, stream);
+}

@@ -1,4 +1,4 @@
-// Scalar math of the contrastive / alignment loss shared by contrastive.hip (batch-global loss) and grouploss.hip
+// Scalar math of the contrastive / alignment loss shared by contrastive.hip, loss_pertable.hip, loss_anchor.hip (batch-global loss) and grouploss.hip
 // (loss_group = b): reference src/aligner/losses.py:5-15 written per element, with its derivatives.
 #pragma once
 #include "sga_common.h"

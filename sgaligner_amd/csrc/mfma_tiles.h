@@ -1,4 +1,4 @@
-// LDS-tile + fp32-MFMA building blocks shared by gemm.hip and contrastive.hip (gfx950).
+// LDS-tile + fp32-MFMA building blocks shared by gemm.hip and the loss kernels (contrastive.hip, loss_pertable.hip, loss_anchor.hip; gfx950).
 //
 // Conventions
 //   * LDS operand tiles are stored [row][k] with a row stride of (KC + 4) floats, KC a multiple of 8:

@@ -1,7 +1,7 @@
 // fp16-input / fp32-accumulate path of the batch-global loss on WIDE tables (BASELINE.json configs[4]: 1024-d embeddings, "MFMA
 // similarity GEMM at fp16").  Opt-in (ops.set_mfma_mode('f16')); exact fp32 stays the default everywhere.
 //
-// Replaces, for packed tables wider than 128 columns, the fp32 sweeps of contrastive.hip:
+// Replaces, for packed tables wider than 128 columns, the fp32 sweeps of loss_pertable.hip:
 //   sga_loss_neg_sums      -> sga_loss_neg_sums_f16       the 4x2 global sums  sum_ij exp(S_ij / tau)              (losses.py:6-11)
 //   sga_loss_neg_grad_wide -> sga_loss_neg_grad_f16       dL/dZ through the anchors x negatives similarities       (autograd of :6-11)
 // with S = Z Z^T and both gradient GEMMs on v_mfma_f32_32x32x16_f16.  One tiled NT-GEMM core (out[m][n] = sum_k A[m][k] B[n][k],
@@ -11,7 +11,7 @@
 //   COEF  c_ij = (g0/tau0 exp(S/tau0) + g1/tau1 exp(S/tau1)) / alpha  written as fp16 (alpha = the coefficient's bound, so |c/alpha| <= 1:
 //         inside fp16's range whatever the loss scale; values below 6e-8 of the bound flush to zero);
 //   GEMM  out += alpha * acc  (fp32 atomics; split over K for occupancy);
-//   STORE out  = acc          (fp32; the anchors x anchors similarity blocks of contrastive.hip's epilogue-only kernels, wide16_api.h).
+//   STORE out  = acc          (fp32; the anchors x anchors similarity blocks of loss_pertable.hip's epilogue-only kernels, wide16_api.h).
 // Operand layouts (sga_wide16_prepare): Zh [R][Dp] = fp16 copy of the packed normalised table (S operand), ZhT [Dp][ldt] = its
 // transpose with every segment (X1 | X2 | N1 | N2) starting at a multiple of 8 columns (the gradient GEMMs' B operand: k = packed row).
 // The gradient GEMMs need the coefficient tile in both orientations (anchor-major C for dZ[anchors] = C Z[neg], negative-major C^T for

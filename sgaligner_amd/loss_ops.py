@@ -1,4 +1,4 @@
-"""The contrastive / alignment loss (reference src/aligner/losses.py) on csrc/contrastive.hip, sweep3.hip, wide16.hip, grouploss.hip, losshead.hip.
+"""The contrastive / alignment loss (reference src/aligner/losses.py) on csrc/contrastive.hip, loss_anchor.hip, loss_pertable.hip, sweep3.hip, wide16.hip, grouploss.hip, losshead.hip.
 
 Part of the autograd layer over the C-ABI HIP kernels (see ops.py, which re-exports everything here: `sgaligner_amd.ops.<name>` keeps
 working).  The run-time switches live in ops.py and are read through the module at call time (`_o.FLAG`), so `ops.FLAG = value` set by a
@@ -28,7 +28,7 @@ def _anchor_chunks(a_lo, a_hi, A, n_tables):
 
 
 def _sym_chunks(A, n_tables):
-    """Blocks of the SYMMETRIC anchors x anchors walk (csrc/contrastive.hip, anchor_multi_bwd16_kernel<.., SYM>): block [lo, hi) meets
+    """Blocks of the SYMMETRIC anchors x anchors walk (csrc/loss_anchor.hip, anchor_multi_bwd16_kernel<.., SYM>): block [lo, hi) meets
     the columns >= lo and keeps two stashes, [A - lo, hi - lo] and [A - hi, hi - lo] floats per table, bounded together by _o.STASH_BYTES --
     so blocks get taller as the walk moves right.  32-row boundaries except the end."""
     return [(lo, hi) for lo, hi, _, _, _ in _sym_jobs([0, A], 0, n_tables)]
@@ -109,7 +109,7 @@ class ContrastiveTermsFn(torch.autograd.Function):
         f16 = get_mfma_mode() == 'f16'
         sums = torch.empty((nt, 8), device=dev, dtype=torch.float64)
         st = _stream()
-        slots = 1 + L.sga_loss_slots()          # scalar accumulators are [result | per-wave slots] (contrastive.hip)
+        slots = 1 + L.sga_loss_slots()          # scalar accumulators are [result | per-wave slots] (loss_math.h)
         for k, e in enumerate(tables):
             d = e.shape[1]
             dp = (d + 7) // 8 * 8
@@ -224,7 +224,7 @@ class ContrastiveTermsFn(torch.autograd.Function):
                 _ev_stop(ev16, 'wide16_grad', (A, s.J1, s.J2, dp))
                 del stash
             elif dp > 128 and _o.WIDE_STASH and a_lo == 0 and a_hi == A:
-                # wide rows: S is the expensive part -> coefficient stash + GEMMs, S computed once (csrc/contrastive.hip, sweep_coef_kernel)
+                # wide rows: S is the expensive part -> coefficient stash + GEMMs, S computed once (csrc/loss_pertable.hip, sweep_coef_kernel)
                 need = int(L.sga_loss_neg_grad_wide_floats(A, s.J1, s.J2))
                 have = max(min(need, _stash_bytes() // 4), 2 * (s.J1 + s.J2) * min(A, 32))
                 stash = torch.empty((have,), device=dev, dtype=torch.float32)

@@ -16,8 +16,8 @@ def test_headline_kernels_do_not_spill():
         pytest.skip('hipcc not available')
     hot = {
         'contrastive.hip': ['14sweep16_kernelILi3ELb1ELb0E', '14sweep16_kernelILi3ELb0ELb0E', '14sweep16_kernelILi2ELb1ELb0E',
-                            '16sweep16x2_kernelILb1E', '16sweep16x2_kernelILb0E',
-                            '25anchor_multi_bwd16_kernelILi3ELb1ELi32ELb1E', '25anchor_multi_bwd16_kernelILi3ELb1ELi32ELb0E',
+                            '16sweep16x2_kernelILb1E', '16sweep16x2_kernelILb0E'],
+        'loss_anchor.hip': ['25anchor_multi_bwd16_kernelILi3ELb1ELi32ELb1E', '25anchor_multi_bwd16_kernelILi3ELb1ELi32ELb0E',
                             '25anchor_multi_bwd16_kernelILi4ELb1ELi16ELb0E', '19anchor_multi_kernelILi3EE'],
         # (the three-plane forward of the training step -- arg-max, BN sums, whole objects per workgroup -- and the three-plane backward: the defaults)
         'pointnet.hip': ['19pointnet_fwd_kernelILi256ELb1ELb0E', '25pointnet_bwd_fused_kernel',

@@ -1,10 +1,12 @@
 """Per-kernel resource report of the HIP sources (registers, LDS, scratch, spills) and what sits INSIDE loops that should not: scalar
 loads (a dynamically indexed kernel argument), scratch traffic (spills), v_readlane (spilled SGPRs).  Cross-compiles, needs no GPU.
   python tools/kernel_resources.py [file.hip ...]        # default: every csrc/*.hip; prints only kernels with something to report
-  python tools/kernel_resources.py --all contrastive.hip # every kernel of the file
+  python tools/kernel_resources.py --all loss_anchor.hip # every kernel of the file
+  python tools/kernel_resources.py --all --digest        # + mangled name and a sha256 of each kernel's instruction stream (comments, directives
+                                                         #   and blank lines dropped, .LBB<n>_ -> .LBB_): proves a refactor left the code alone
 This is the audit of DESIGN.md 3a: a kernel on the hot path must report scratch 0 and no scalar loads in its tile loop."""
 import concurrent.futures as cf
-import glob, os, re, subprocess, sys, tempfile
+import glob, hashlib, os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -43,6 +45,9 @@ def analyse(src):
                 kern = None
             if kern not in res:
                 continue
+            code = ' '.join(line.split(';')[0].split())
+            if code and (not code.startswith('.') or code.endswith(':')):
+                res[kern].setdefault('sha', hashlib.sha256()).update((re.sub(r'\.LBB\d+_', '.LBB_', code) + '\n').encode())
             if re.match(r'^(\.LBB\S+:|; %bb\.\d+:)', line):
                 md = re.search(r'Depth[= ](\d+)', line)
                 depth = int(md.group(1)) if md else 0
@@ -52,11 +57,13 @@ def analyse(src):
                 for key, pre in (('loop_s_load', 's_load'), ('loop_scratch', 'scratch_'), ('loop_readlane', 'v_readlane')):
                     if op.startswith(pre):
                         res[kern][key] = res[kern].get(key, 0) + 1
+    for v in res.values():
+        v['sha'] = v['sha'].hexdigest() if 'sha' in v else ''
     return base, res
 
 
 def main(argv):
-    show_all = '--all' in argv
+    show_all, digest = '--all' in argv, '--digest' in argv
     files = [a for a in argv if not a.startswith('--')] or sorted(glob.glob(os.path.join(_build.CSRC, '*.hip')))
     files = [f if os.path.exists(f) else os.path.join(_build.CSRC, f) for f in files]
     with cf.ThreadPoolExecutor(max_workers=8) as ex:
@@ -68,7 +75,7 @@ def main(argv):
             if show_all or flagged:
                 extra = ' '.join(f'{kk}={v[kk]}' for kk in ('loop_s_load', 'loop_scratch', 'loop_readlane') if v.get(kk))
                 print(f'{base:16s} {names[k][:72]:72s} VGPR {v["vgpr"]:3d} AGPR {v["agpr"]:3d} SGPR {v["sgpr"]:3d} occ {v["occ"]} LDS {v["lds"]:6d} '
-                      f'scratch {v["scratch"]:4d} spills v{v["vspill"]}/s{v["sspill"]} {extra}')
+                      f'scratch {v["scratch"]:4d} spills v{v["vspill"]}/s{v["sspill"]} {extra}' + (f' {k} sha256 {v["sha"]}' if digest else ''))
     return results
 
 
