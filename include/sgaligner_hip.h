@@ -449,6 +449,43 @@ int sga_ransac_rigid(const double* corr, const int32_t* offsets, int n_jobs, int
                      int32_t* best_hyp, int32_t* status, unsigned char* inlier_mask, int32_t* hyp_count, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ---- batched subscan generation: frame visibility, frustum walk, per-object counts (fp64 tests, integer walk) ----------------------
+ * replaces the per-frame loop of preprocessing/scan3r/subgenscan3r.py:188-234: utils/point_cloud.py:112-134 get_visible_pts_from_cam_pose
+ * for every frame, the running OR of the masks with a subscan closed whenever the union reaches the point budget, and the per-object
+ * visible-point counts of gen_scene_graph (:51-85).  Scans are packed back to back: pts [total_points, 3] f32 (the ply vertices as stored)
+ * / pt_off [n_scans + 1]; w2c [total_frames, 12] f64 (rows 0-2 of the world-to-camera matrix, row-major) / fr_off [n_scans + 1]; intr
+ * [n_scans, 6] f64 = fx, fy, cx, cy, u_max, v_max.  Scan s owns a bit matrix of F_s rows by W_s = ceil(N_s / 64) 64-bit words that starts
+ * at word vis_off[s] of a [total_words] array (vis_off [n_scans + 1] int64, the prefix sum of F_t * W_t); bit p % 64 of word p / 64 of a row
+ * is point p, the padding bits of the last word are 0.  These are DEVICE arrays; pt_off_host / fr_off_host / vis_off_host (nullable) are host
+ * copies that, when given, are validated before anything is launched.  max_points / max_frames: the largest scan (they size the grid; the
+ * kernels re-check every offset they read, a bad one makes them do nothing).  Stream-ordered, no allocation, no synchronisation.
+ * sga_frame_visibility writes the bit matrices.  Per (frame, point), every fp64 operation rounded on its own (no FMA), x, y, z the f32
+ * vertex widened to f64:  X = ((x*m00 + y*m01) + z*m02) + m03 (Y, Z with rows 1, 2);  r = (Z != 0) ? 1.0 / Z : 1.0 (correctly rounded);
+ * u = (X*r)*fx + cx, v = (Y*r)*fy + cy;  visible = (Z > 0) && (u >= 0) && (u <= u_max) && (v >= 0) && (v <= v_max).  A NaN anywhere gives
+ * invisible.  (The reference compares the first image coordinate with the HEIGHT and the second with the WIDTH; its callers here pass
+ * u_max = height, v_max = width.)
+ * sga_subscan_walk, per scan with max_pts[s]:  cur = 0; k = 0; for f in 0 .. F-1: cur |= vis[f]; cum[f] = cur; c = popcount(cur);
+ * frame_count[f] = c; if c >= max_pts: seg_end[k] = f; seg_count[k] = c; k += 1; cur = 0.  n_seg[s] = k (the unclosed tail is discarded, as
+ * in the reference).  cum may be vis itself (in place): subscan k's mask is then row seg_end[k].  seg_end / seg_count / frame_count are
+ * [total_frames], scan s's entries start at fr_off[s]; seg_end is scan-local.  A scan with N == 0 or F == 0 gets n_seg = 0 and nothing else.
+ * sga_subscan_object_counts: rows [n_rows, 2] = (scan, scan-local frame row) of the matrix `bits`; slot [total_points] the dense object slot
+ * of every point in [0, n_slots) (a slot outside that range is not counted); counts [n_rows, n_slots] = set bits of the row per slot,
+ * zeroed by the call.  Integer atomics (a workgroup-private histogram up to sga_subscan_lds_slots() slots, global atomics above): exact and
+ * independent of the order of execution. */
+int sga_subscan_lds_slots(void);
+int sga_frame_visibility(const float* pts, const int32_t* pt_off, const double* w2c, const int32_t* fr_off, const double* intr,
+                         const int64_t* vis_off, int n_scans, int total_points, int total_frames, int64_t total_words, int max_points,
+                         int max_frames, const int32_t* pt_off_host, const int32_t* fr_off_host, const int64_t* vis_off_host,
+                         uint64_t* vis, void* stream);
+int sga_subscan_walk(const uint64_t* vis, uint64_t* cum, const int32_t* pt_off, const int32_t* fr_off, const int64_t* vis_off,
+                     const int32_t* max_pts, int n_scans, int total_points, int total_frames, int64_t total_words,
+                     const int32_t* pt_off_host, const int32_t* fr_off_host, const int64_t* vis_off_host, int32_t* seg_end,
+                     int32_t* seg_count, int32_t* frame_count, int32_t* n_seg, void* stream);
+int sga_subscan_object_counts(const uint64_t* bits, const int32_t* pt_off, const int32_t* fr_off, const int64_t* vis_off, int n_scans,
+                              int total_points, int total_frames, int64_t total_words, int max_points, const int32_t* rows, int n_rows,
+                              const int32_t* slot, int n_slots, const int32_t* pt_off_host, const int32_t* fr_off_host,
+                              const int64_t* vis_off_host, const int32_t* rows_host, int32_t* counts, void* stream);
+
 /* Wide tables (Dp > 128) of sga_loss_neg_grad: one anchor-owner sweep writes c_ij = dL/dS_ij to a caller-owned stash (anchor-row blocks
  * sized to stash_floats; sga_loss_neg_grad_wide_floats() = everything in one block), both gradients are GEMMs on it: the K = Dp
  * similarity tile is computed once instead of 2 x ceil(Dp / 320) times.  Same results as sga_loss_neg_grad up to fp32 summation order. */

@@ -69,6 +69,10 @@ SIGNATURES = {
     'sga_nn_search': (I, [P, P, I, I, P, I, P, I, I, I, I, P, P, I, P, P, P, c_size_t, P]),
     'sga_ransac_workspace_bytes': (c_size_t, [I, I, I, I]),
     'sga_ransac_rigid': (I, [P, P, I, I, P, P, I, I, I, I, P, P, c_double, I, P, P, P, P, P, P, P, c_size_t, P]),
+    'sga_subscan_lds_slots': (I, []),
+    'sga_frame_visibility': (I, [P, P, P, P, P, P, I, I, I, c_int64, I, I, P, P, P, P, P]),
+    'sga_subscan_walk': (I, [P, P, P, P, P, P, I, I, I, c_int64, P, P, P, P, P, P, P, P]),
+    'sga_subscan_object_counts': (I, [P, P, P, P, I, I, I, c_int64, I, P, I, P, I, P, P, P, P, P, P]),
     'sga_gemm': (I, [I, I, I, I, I, P, c_long, I, P, c_long, P, c_long, P, I, P]),
     'sga_colsum': (I, [P, c_long, I, I, P, I, P]),
     'sga_gemm_bnstats': (I, [I, I, I, P, c_long, P, c_long, P, c_long, P, P, P]),

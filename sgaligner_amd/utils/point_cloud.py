@@ -8,7 +8,10 @@ one launch.
 
 `get_nearest_neighbor`, `compute_pcl_overlap` and `apply_transform` keep the reference signatures (utils/point_cloud.py:136-157,
 91-103); `nearest_neighbor_batch` / `compute_pcl_overlap_pairs` are the batched forms (csrc/nnsearch.hip: exact fp64 brute force,
-distances bit-identical to cKDTree's, ties to the lowest index)."""
+distances bit-identical to cKDTree's, ties to the lowest index).
+
+`inverse_relative` and `get_visible_pts_from_cam_pose` keep the reference signatures (utils/point_cloud.py:105-134);
+`visible_masks_batch` is the packed form (csrc/visibility.hip: every frame of every scan in one launch, bit masks out)."""
 from __future__ import annotations
 
 import numpy as np
@@ -297,3 +300,150 @@ def apply_transform(points: np.ndarray, transform: np.ndarray, normals=None):
     if normals is None:
         return moved
     return moved, np.matmul(normals, rot.T)
+
+
+# ---- frame visibility (utils/point_cloud.py:105-134; the frame loop of preprocessing/scan3r/subgenscan3r.py:188-234) ---------------------
+def inverse_relative(pose1To2):
+    """Reference signature (utils/point_cloud.py:105): the inverse of a rigid 4x4 pose, on the host.  The result is a FLOAT32 array, as in
+    the reference -- the world-to-camera matrix the visibility test sees is float32-valued."""
+    pose1To2 = np.asarray(pose1To2)
+    rot_t = np.transpose(pose1To2[:3, :3])
+    pose2To1 = np.zeros((4, 4), dtype='float32')
+    pose2To1[:3, :3] = rot_t
+    pose2To1[:3, 3:4] = -np.dot(rot_t, pose1To2[:3, 3:4])
+    pose2To1[3, 3] = 1
+    return pose2To1
+
+
+def intrinsic_row(intrinsic_info) -> np.ndarray:
+    """fx, fy, cx, cy, u_max, v_max (float64) of a load_intrinsics() dict.  The reference compares the FIRST image coordinate against
+    `height` and the second against `width` (utils/point_cloud.py:130-131); that is reproduced on purpose: u_max = height, v_max = width."""
+    mat = np.asarray(intrinsic_info['intrinsic_mat'])
+    return np.array([mat[0, 0], mat[1, 1], mat[0, 2], mat[1, 2], intrinsic_info['height'], intrinsic_info['width']], dtype=np.float64)
+
+
+def world_to_cam_rows(cam_2_world_poses) -> np.ndarray:
+    """[F, 4, 4] camera-to-world poses -> [F, 12] float64: rows 0-2 of inverse_relative(pose), row-major (float32 values, widened)."""
+    poses = np.asarray(cam_2_world_poses)
+    if poses.ndim != 3 or poses.shape[1:] != (4, 4):
+        raise ValueError(f'poses must be [F, 4, 4], got {poses.shape}')
+    out = np.empty((poses.shape[0], 12), dtype=np.float64)
+    for f in range(poses.shape[0]):
+        out[f] = inverse_relative(poses[f])[:3].reshape(12)
+    return out
+
+
+def visibility_offsets(pt_off, fr_off):
+    """Host prefix arrays of the packed bit matrices: (words per row W [S], vis_off [S + 1] int64 = prefix sum of F_s * W_s)."""
+    pt_off, fr_off = np.asarray(pt_off, dtype=np.int64), np.asarray(fr_off, dtype=np.int64)
+    words = (np.diff(pt_off) + 63) // 64
+    return words, np.concatenate([[0], np.cumsum(np.diff(fr_off) * words)]).astype(np.int64)
+
+
+def _host_offsets(a, name: str, total: int):
+    off = np.ascontiguousarray(a.cpu() if isinstance(a, torch.Tensor) else a, dtype=np.int64).reshape(-1)
+    if len(off) < 1 or off[0] != 0 or off[-1] != total or (np.diff(off) < 0).any():
+        raise ValueError(f'{name} must be a monotone prefix array covering all {total} rows')
+    return off
+
+
+def _device_tensor(t, name: str, dtype):
+    if isinstance(t, torch.Tensor) and t.dtype != dtype:
+        raise RuntimeError(f'sgaligner_amd: `{name}` must be {dtype} (got {t.dtype})')
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f'sgaligner_amd: `{name}` must be a HIP device tensor (got '
+                           f'{t.device if isinstance(t, torch.Tensor) else type(t)}); there is no CPU path')
+    return t.contiguous()
+
+
+class ScanLayout:
+    """Offsets of a list of scans packed back to back, on the host and on the device: pt_off / fr_off [S + 1] (int32 on the device),
+    words per bit-matrix row W [S], vis_off [S + 1] int64.  `meta`, when given, is an int32 device tensor that already holds
+    `host_meta()` (so that a caller can fold the offsets into a larger upload); otherwise the layout uploads it itself."""
+
+    def __init__(self, pt_off, fr_off, total_points: int, total_frames: int, device=None, meta=None):
+        self.pt_off, self.fr_off = _host_offsets(pt_off, 'pt_off', total_points), _host_offsets(fr_off, 'fr_off', total_frames)
+        self.n_scans = len(self.pt_off) - 1
+        if len(self.fr_off) != self.n_scans + 1:
+            raise ValueError(f'pt_off names {self.n_scans} scans, fr_off {len(self.fr_off) - 1}')
+        if total_points >= 2 ** 31 or total_frames >= 2 ** 31:
+            raise ValueError('scans are indexed with int32: fewer than 2^31 points and frames per call')
+        self.total_points, self.total_frames = int(total_points), int(total_frames)
+        self.words, self.vis_off = visibility_offsets(self.pt_off, self.fr_off)
+        self.total_words = int(self.vis_off[-1])
+        self.max_points = int(np.diff(self.pt_off).max()) if self.n_scans else 0
+        self.max_frames = int(np.diff(self.fr_off).max()) if self.n_scans else 0
+        self.h_pt, self.h_fr = self.pt_off.astype(np.int32), self.fr_off.astype(np.int32)
+        if meta is None and device is not None:
+            meta = torch.from_numpy(self.host_meta()).to(device)                      # one small upload
+        if meta is not None:
+            n = self.n_scans + 1
+            self.d_vis, self.d_pt, self.d_fr = meta[:2 * n], meta[2 * n:3 * n], meta[3 * n:4 * n]
+
+    def host_meta(self) -> np.ndarray:
+        """vis_off (int64, viewed as int32 pairs; first, for its alignment) | pt_off | fr_off as one int32 array of 4 (S + 1) entries."""
+        return np.concatenate([self.vis_off.view(np.int32), self.h_pt, self.h_fr])
+
+    def host_args(self):
+        return self.h_pt.ctypes.data, self.h_fr.ctypes.data, self.vis_off.ctypes.data
+
+
+def _bit_matrix(t, name: str, total_words: int):
+    t = _device_tensor(t, name, torch.int64)
+    if t.dim() != 1 or t.numel() < total_words:
+        raise ValueError(f'{name} must be a flat int64 tensor of at least {total_words} words, got {tuple(t.shape)}')
+    return t
+
+
+def visible_masks_batch(points, pt_off, w2c, fr_off, intr, out=None, layout=None):
+    """The packed form (csrc/visibility.hip, sga_frame_visibility): points [sum N, 3] float32, w2c [sum F, 12] float64 (world_to_cam_rows),
+    intr [S, 6] float64 (intrinsic_row) HIP device tensors, scans packed back to back; pt_off / fr_off [S + 1] host ints (or a ScanLayout
+    that already holds them).  One launch.  Returns (vis, vis_off): vis [total_words] int64 device tensor holding every scan's bit matrix --
+    scan s's F_s rows of W_s = ceil(N_s / 64) words start at vis_off[s] (int64 numpy, [S + 1]); bit p % 64 of word p / 64 of a row is point
+    p, padding bits 0."""
+    for t, name, dt in ((points, 'points', torch.float32), (w2c, 'w2c', torch.float64), (intr, 'intr', torch.float64)):
+        if isinstance(t, torch.Tensor) and t.dtype != dt:                     # every dtype before any device: told apart without a device
+            raise RuntimeError(f'sgaligner_amd: `{name}` must be {dt} (got {t.dtype})')
+    pts = _device_tensor(points, 'points', torch.float32)
+    m = _device_tensor(w2c, 'w2c', torch.float64)
+    k = _device_tensor(intr, 'intr', torch.float64)
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f'points must be [N, 3], got {tuple(pts.shape)}')
+    if m.dim() != 2 or m.shape[1] != 12:
+        raise ValueError(f'w2c must be [F, 12], got {tuple(m.shape)}')
+    L = layout if layout is not None else ScanLayout(pt_off, fr_off, pts.shape[0], m.shape[0], device=pts.device)
+    if L.total_points != pts.shape[0] or L.total_frames != m.shape[0] or tuple(k.shape) != (L.n_scans, 6):
+        raise ValueError(f'{L.n_scans} scans of {L.total_points} points and {L.total_frames} frames: got points {tuple(pts.shape)}, w2c '
+                         f'{tuple(m.shape)}, intr {tuple(k.shape)} (intr must be [S, 6])')
+    out = torch.empty((L.total_words,), device=pts.device, dtype=torch.int64) if out is None else _bit_matrix(out, 'out', L.total_words)
+    if L.n_scans == 0 or L.total_words == 0:
+        return out, L.vis_off
+    rc = _lib.lib().sga_frame_visibility(_p(pts), _p(L.d_pt), _p(m), _p(L.d_fr), _p(k), _p(L.d_vis), L.n_scans, L.total_points, L.total_frames,
+                                         L.total_words, L.max_points, L.max_frames, *L.host_args(), _p(out), _stream())
+    _lib.check(rc, 'sga_frame_visibility')
+    return out, L.vis_off
+
+
+def unpack_mask_words(words, n_points: int) -> np.ndarray:
+    """Host: [..., ceil(n / 64)] 64-bit words (numpy, any 8-byte integer dtype) -> bool [..., n]."""
+    words = np.ascontiguousarray(words)
+    lead = words.shape[:-1]
+    bits = np.unpackbits(words.view(np.uint8).reshape(lead + (-1,)), axis=-1, bitorder='little')
+    return bits[..., :n_points].astype(bool)
+
+
+def get_visible_pts_from_cam_pose(scene_pts, cam_2_world_pose, intrinsic_info):
+    """Reference signature (utils/point_cloud.py:112): the bool mask [N] of the scene points that project into the frame with positive
+    depth.  One frame per call: upload, launch, download -- preprocessing.subscans.generate_subscan_masks runs all frames of many scans at once."""
+    _need_device('get_visible_pts_from_cam_pose')
+    pts = np.asarray(scene_pts)
+    if pts.ndim != 2 or pts.shape[1] < 3:
+        raise ValueError(f'scene_pts must be [N, 3], got {pts.shape}')
+    n = int(pts.shape[0])
+    if n == 0:
+        return np.zeros((0,), dtype=bool)
+    d_pts = torch.from_numpy(np.ascontiguousarray(pts[:, :3], dtype=np.float32)).cuda()
+    d_m = torch.from_numpy(world_to_cam_rows(np.asarray(cam_2_world_pose)[None])).cuda()
+    d_k = torch.from_numpy(intrinsic_row(intrinsic_info)[None]).cuda()
+    vis, _ = visible_masks_batch(d_pts, [0, n], d_m, [0, 1], d_k)
+    return unpack_mask_words(vis.cpu().numpy(), n)
