@@ -486,6 +486,49 @@ int sga_subscan_object_counts(const uint64_t* bits, const int32_t* pt_off, const
                               const int32_t* slot, int n_slots, const int32_t* pt_off_host, const int32_t* fr_off_host,
                               const int64_t* vis_off_host, const int32_t* rows_host, int32_t* counts, void* stream);
 
+/* ---- scene-graph records (preprocessing/scan3r/preprocess.py:40-211 process_scan and the two bag-of-words passes :280-361) ----
+ * Integers only: every output is a pure function of the input (integer atomics and prefix sums in index order).  Scans are packed back to
+ * back: slot [sum N] int32 = each point's dense object slot within its scan (np.unique(objectId, return_inverse=True)[1]; a value outside
+ * the scan's slot range, e.g. -1, belongs to no object), pt_off / slot_off [S + 1] the point and slot ranges.  *_host: host copies,
+ * validated before any launch (nullable for sga_object_counts and sga_bow_counts, required elsewhere); the kernels re-derive their ranges
+ * from the device arrays and do nothing on a bad one.  Caller-owned buffers, caller's stream, no synchronisation.
+ *
+ * sga_object_counts: counts [sum slots] = points per slot (zeroed by the call); an LDS histogram up to sga_scenegraph_lds_slots() slots per
+ * scan, global integer atomics above.
+ *
+ * sga_object_partition: the stable split.  dest_off [sum slots]: the start of the slot's points in the packed output, -1 = dropped;
+ * counts_host: what sga_object_counts returned.  perm [n_kept_points] int32 (scan-local point index) and pts_out [n_kept_points, 3] f32 with
+ * perm[dest_off[k] : dest_off[k] + counts[k]] == flatnonzero(slot_s == k): ascending point order, from per-tile histograms
+ * (sga_scenegraph_tile() points per tile), an exclusive scan over tiles in tile order and an in-tile ballot rank -- never from the arrival
+ * order of an atomic.  At most sga_scenegraph_lds_slots() slots per scan; overlapping or out-of-range destination ranges are refused.
+ * ws: sga_object_partition_ws_bytes(n_scans, max_points, max_slots) bytes.
+ *
+ * sga_graph_complete: one workgroup per graph; node_off / pair_off / trip_off / edge_off [G + 1] int32 prefix arrays.  Graph g has
+ * N = diff(node_off) nodes, its listed pairs [P, 2] (graph-local, list order) at pairs + 2 pair_off[g], the relation ids of its listed
+ * triples [Tr >= P] at rels + trip_off[g], and room for diff(edge_off) >= P + N (N - 1) edges.  edges [sum, 2] int64: the listed pairs,
+ * then every ordered pair (i, j), i != j, that is not listed, row-major; n_edges [G]; bow [sum N, V] int32 (zeroed by the call):
+ * bow[edges[idx][0], rel(idx)] += 1 for idx < n_edges, rel(idx) = rels[idx] for idx < Tr, else none_id -- the edge index applied to the
+ * TRIPLES list, as the reference does (:303-306), so a pair listed with two relations shifts every later edge by one.  N at most
+ * sga_graph_max_nodes() (the adjacency bit matrix and one counter per row fit 64 KiB of LDS).
+ *
+ * sga_bow_counts: out [T, V] int32 (zeroed by the call), out[rows[i], cols[i]] += 1 for i < n; the host check refuses an entry outside. */
+int sga_scenegraph_lds_slots(void);
+int sga_scenegraph_tile(void);
+int sga_graph_max_nodes(void);
+int sga_object_counts(const int32_t* slot, const int32_t* pt_off, const int32_t* slot_off, int n_scans, int total_points, int total_slots,
+                      int max_points, const int32_t* pt_off_host, const int32_t* slot_off_host, int32_t* counts, void* stream);
+size_t sga_object_partition_ws_bytes(int n_scans, int max_points, int max_slots);
+int sga_object_partition(const float* pts, const int32_t* slot, const int32_t* pt_off, const int32_t* slot_off, const int32_t* dest_off,
+                         int n_scans, int total_points, int total_slots, int max_points, int max_slots, int n_kept_points,
+                         const int32_t* pt_off_host, const int32_t* slot_off_host, const int32_t* dest_off_host, const int32_t* counts_host,
+                         int32_t* perm, float* pts_out, void* ws, size_t ws_bytes, void* stream);
+int sga_graph_complete(const int32_t* node_off, const int32_t* pair_off, const int32_t* trip_off, const int32_t* edge_off, int n_graphs,
+                       const int32_t* pairs, const int32_t* rels, int none_id, int V, const int32_t* node_off_host,
+                       const int32_t* pair_off_host, const int32_t* trip_off_host, const int32_t* edge_off_host, const int32_t* pairs_host,
+                       const int32_t* rels_host, int64_t* edges, int32_t* n_edges, int32_t* bow, void* stream);
+int sga_bow_counts(const int32_t* rows, const int32_t* cols, int n, int T, int V, const int32_t* rows_host, const int32_t* cols_host,
+                   int32_t* out, void* stream);
+
 /* Wide tables (Dp > 128) of sga_loss_neg_grad: one anchor-owner sweep writes c_ij = dL/dS_ij to a caller-owned stash (anchor-row blocks
  * sized to stash_floats; sga_loss_neg_grad_wide_floats() = everything in one block), both gradients are GEMMs on it: the K = Dp
  * similarity tile is computed once instead of 2 x ceil(Dp / 320) times.  Same results as sga_loss_neg_grad up to fp32 summation order. */

@@ -73,6 +73,14 @@ SIGNATURES = {
     'sga_frame_visibility': (I, [P, P, P, P, P, P, I, I, I, c_int64, I, I, P, P, P, P, P]),
     'sga_subscan_walk': (I, [P, P, P, P, P, P, I, I, I, c_int64, P, P, P, P, P, P, P, P]),
     'sga_subscan_object_counts': (I, [P, P, P, P, I, I, I, c_int64, I, P, I, P, I, P, P, P, P, P, P]),
+    'sga_scenegraph_lds_slots': (I, []),
+    'sga_scenegraph_tile': (I, []),
+    'sga_graph_max_nodes': (I, []),
+    'sga_object_counts': (I, [P, P, P, I, I, I, I, P, P, P, P]),
+    'sga_object_partition_ws_bytes': (c_size_t, [I, I, I]),
+    'sga_object_partition': (I, [P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, P, P, P, c_size_t, P]),
+    'sga_graph_complete': (I, [P, P, P, P, I, P, P, I, I, P, P, P, P, P, P, P, P, P, P]),
+    'sga_bow_counts': (I, [P, P, I, I, I, P, P, P, P]),
     'sga_gemm': (I, [I, I, I, I, I, P, c_long, I, P, c_long, P, c_long, P, I, P]),
     'sga_colsum': (I, [P, c_long, I, I, P, I, P]),
     'sga_gemm_bnstats': (I, [I, I, I, P, c_long, P, c_long, P, c_long, P, P, P]),

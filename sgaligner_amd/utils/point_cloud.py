@@ -92,6 +92,23 @@ def hull_candidate_mask_batch(points, offsets):
 HULL_ON_DEVICE = True          # tests flip it to cross-check the device hull against Qhull on the same candidates
 
 
+def hull_vertices_device(cand64, offsets):
+    """The device-resident form of hull_vertices_batch: cand64 [sum n, 3] float64 CUDA tensor, offsets [n_obj+1] host ints (n_obj >= 1,
+    at least one point).  Returns (is_vertex [sum n] uint8, status [n_obj] int32) CUDA tensors; nothing is downloaded."""
+    if not (isinstance(cand64, torch.Tensor) and cand64.is_cuda and cand64.dtype == torch.float64):
+        raise RuntimeError('hull_vertices_device: cand64 must be a float64 CUDA tensor (no CPU fallback)')
+    off = np.asarray(offsets, dtype=np.int64)
+    n_obj = len(off) - 1
+    d_pts = cand64.contiguous()
+    if n_obj <= 0 or off[0] != 0 or off[-1] != d_pts.shape[0] or off[-1] == 0 or (np.diff(off) < 0).any():
+        raise ValueError('offsets must be a monotone prefix array covering all points of at least one object')
+    d_off = torch.from_numpy(off.astype(np.int32)).to(d_pts.device)
+    isv = torch.zeros((int(off[-1]),), device=d_pts.device, dtype=torch.uint8)
+    status = torch.full((n_obj,), -1, device=d_pts.device, dtype=torch.int32)
+    _lib.check(_lib.lib().sga_hull_vertices(_p(d_pts), _p(d_off), n_obj, _p(isv), _p(status), _stream()), 'sga_hull_vertices')
+    return isv, status
+
+
 def hull_vertices_batch(cand64, offsets):
     """cand64 [sum n, 3] float64 numpy (objects packed back to back), offsets [n_obj+1].  Returns (is_vertex [sum n] bool numpy,
     status [n_obj] int numpy): the device gift-wrapping hull with its certificate (csrc/hull.hip, sga_hull_vertices); status != 0
@@ -100,12 +117,37 @@ def hull_vertices_batch(cand64, offsets):
     n_obj = len(off) - 1
     if n_obj <= 0 or off[-1] == 0:
         return np.zeros((int(off[-1]) if len(off) else 0,), dtype=bool), np.ones((max(n_obj, 0),), dtype=np.int32)
-    d_pts = torch.from_numpy(np.ascontiguousarray(cand64, dtype=np.float64)).cuda()
-    d_off = torch.from_numpy(off.astype(np.int32)).cuda()
-    isv = torch.zeros((int(off[-1]),), device='cuda', dtype=torch.uint8)
-    status = torch.full((n_obj,), -1, device='cuda', dtype=torch.int32)
-    _lib.check(_lib.lib().sga_hull_vertices(_p(d_pts), _p(d_off), n_obj, _p(isv), _p(status), _stream()), 'sga_hull_vertices')
+    isv, status = hull_vertices_device(torch.from_numpy(np.ascontiguousarray(cand64, dtype=np.float64)).cuda(), off)
     return isv.cpu().numpy().astype(bool), status.cpu().numpy()
+
+
+def _hull_means(cand, coff, counts, n_obj, verts, qhull_points):
+    """The tail the two barycentre functions share.  cand [sum n, 3] float64 host candidates packed by coff / counts; verts: None (no device
+    hull) or (is_vertex bool [sum n], status [n_obj]); qhull_points(i): object i's candidates in its own values, for the objects the device
+    declined.  Returns (barycentres [n_obj, 3] float64, number of objects that went to Qhull)."""
+    out = np.zeros((n_obj, 3))
+    todo = np.ones((n_obj,), dtype=bool)
+    if verts is not None:
+        isv, status = verts
+        ok = status == 0
+        if ok.any():
+            w = isv.astype(np.float64)
+            seg = np.minimum(coff[:-1], max(len(w) - 1, 0))
+            nz = counts > 0
+            nv = np.where(nz, np.add.reduceat(w, seg), 0.0)
+            for c in range(3):
+                sm = np.where(nz, np.add.reduceat(cand[:, c] * w, seg), 0.0)
+                out[ok, c] = sm[ok] / nv[ok]
+            todo = ~ok
+    n_q = 0
+    if todo.any():
+        from scipy.spatial import ConvexHull
+        for i in np.flatnonzero(todo):
+            hull = ConvexHull(qhull_points(i))
+            v = hull.points[hull.vertices]
+            out[i] = (np.mean(v[:, 0]), np.mean(v[:, 1]), np.mean(v[:, 2]))
+            n_q += 1
+    return out, n_q
 
 
 def convex_hull_barycenters_batch(point_list, return_info=False):
@@ -129,29 +171,41 @@ def convex_hull_barycenters_batch(point_list, return_info=False):
     counts = np.add.reduceat(keep.astype(np.int64), np.minimum(off[:-1], len(keep) - 1)) * (np.diff(off) > 0)
     coff = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
     cand = src[idx].astype(np.float64, copy=False)                            # exact: float32 -> float64
-    out = np.zeros((n_obj, 3))
-    todo = np.ones((n_obj,), dtype=bool)
-    if HULL_ON_DEVICE:
-        isv, status = hull_vertices_batch(cand, coff)
-        ok = status == 0
-        if ok.any():
-            w = isv.astype(np.float64)
-            seg = np.minimum(coff[:-1], max(len(w) - 1, 0))
-            nz = counts > 0
-            nv = np.where(nz, np.add.reduceat(w, seg), 0.0)
-            for c in range(3):
-                sm = np.where(nz, np.add.reduceat(cand[:, c] * w, seg), 0.0)
-                out[ok, c] = sm[ok] / nv[ok]
-            todo = ~ok
-    n_q = 0
-    if todo.any():
-        from scipy.spatial import ConvexHull
-        for i in np.flatnonzero(todo):
-            p = np.asarray(point_list[i])
-            hull = ConvexHull(p[keep[off[i]:off[i + 1]]])          # candidates in the object's own dtype / values
-            v = hull.points[hull.vertices]
-            out[i] = (np.mean(v[:, 0]), np.mean(v[:, 1]), np.mean(v[:, 2]))
-            n_q += 1
+    verts = hull_vertices_batch(cand, coff) if HULL_ON_DEVICE else None
+    # Qhull sees the candidates in the object's own dtype / values
+    out, n_q = _hull_means(cand, coff, counts, n_obj, verts, lambda i: np.asarray(point_list[i])[keep[off[i]:off[i + 1]]])
+    if return_info:
+        return out, {'device': int(n_obj - n_q), 'qhull': int(n_q)}
+    return out
+
+
+def convex_hull_barycenters_device(points, offsets, return_info=False):
+    """The device-resident form of convex_hull_barycenters_batch: points [sum N, 3] float32 CUDA tensor (objects packed back to back, e.g.
+    the output of preprocessing.scene_graphs.object_partition_batch), offsets [n_obj+1] host ints.  Same three steps and the same answers;
+    the points are never uploaded again.  Downloads: the candidates' indices (their number per object sizes the second launch), then the
+    candidates themselves with their vertex flags -- a few per cent of the points.  Objects the device hull declines go to Qhull on the
+    downloaded candidates (float32 values, the scan's own)."""
+    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32):
+        raise RuntimeError('convex_hull_barycenters_device: points must be a float32 CUDA tensor (no CPU fallback)')
+    off = np.asarray(offsets, dtype=np.int64)
+    n_obj = len(off) - 1
+    if n_obj < 0 or off[0] != 0 or off[-1] != points.shape[0] or (np.diff(off) < 0).any():
+        raise ValueError('offsets must be a monotone prefix array covering all points')
+    if off[-1] == 0:
+        return (np.zeros((n_obj, 3)), {'device': 0, 'qhull': 0}) if return_info else np.zeros((n_obj, 3))
+    pts = points.contiguous()
+    keep, _ = hull_candidate_mask_batch(pts, off)
+    d_idx = torch.nonzero(keep).reshape(-1)
+    idx = d_idx.cpu().numpy()                                                  # ascending: the candidates stay packed per object
+    coff = np.searchsorted(idx, off).astype(np.int64)
+    counts = np.diff(coff)
+    d_cand = pts[d_idx]
+    verts = None
+    if HULL_ON_DEVICE and len(idx):
+        isv, status = hull_vertices_device(d_cand.double(), coff)              # exact: float32 -> float64
+        verts = (isv.cpu().numpy().astype(bool), status.cpu().numpy())
+    cand32 = d_cand.cpu().numpy()
+    out, n_q = _hull_means(cand32.astype(np.float64), coff, counts, n_obj, verts, lambda i: cand32[coff[i]:coff[i + 1]])
     if return_info:
         return out, {'device': int(n_obj - n_q), 'qhull': int(n_q)}
     return out

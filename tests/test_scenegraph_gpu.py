@@ -1,0 +1,229 @@
+"""GPU: the scene-graph record kernels (csrc/scenegraph.hip) against the NumPy yardstick (tests/scenegraph_ref.py), exactly -- every output is
+an integer or a copied float -- and process_scans end to end against the reference's own records (tests/golden/scenegraph_cases.npz)."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import scenegraph_ref as SG  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+
+# ---- partition ---------------------------------------------------------------------------------------------------------------------------
+def _partition_scans():
+    """(points [N, 3] f32, slot [N], n_slots, dropped slots) per scan: every N of interest with every slot count, -1 points, an empty slot,
+    a slot that owns every point, dropped slots."""
+    from sgaligner_amd.preprocessing import scene_graphs as G
+    tile = G.partition_tile()
+    rng = np.random.default_rng(21)
+    sizes = [1, 63, 64, 65, tile - 1, tile, tile + 1, 4097, 20000]
+    slots = [1, 2, 37, 300]
+    scans = []
+    for k, n in enumerate(sizes):
+        ns = slots[k % 4]
+        slot = rng.integers(0, ns, n)
+        if ns > 2:
+            slot[slot == 5] = 6                              # slot 5 is empty
+            slot[rng.random(n) < 0.1] = -1                   # points of no object
+        if ns == 2:
+            slot[:] = 1                                      # slot 1 owns every point, slot 0 is empty
+        drop = set(rng.choice(ns, ns // 3, replace=False).tolist())
+        scans.append((rng.standard_normal((n, 3)).astype(np.float32), slot, ns, drop))
+    scans.append((rng.standard_normal((20000, 3)).astype(np.float32), np.sort(rng.integers(-1, 300, 20000)), 300, {7}))     # sorted by object
+    scans.append((rng.standard_normal((4097, 3)).astype(np.float32), rng.integers(0, 37, 4097), 1, set()))                  # slots outside the table
+    return scans
+
+
+def _run_partition(scans):
+    from sgaligner_amd.preprocessing import scene_graphs as G
+    L = G.SlotLayout(np.concatenate([[0], np.cumsum([len(s[0]) for s in scans])]), np.concatenate([[0], np.cumsum([s[2] for s in scans])]), device='cuda')
+    d_pts = torch.from_numpy(np.concatenate([s[0] for s in scans]).reshape(-1, 3)).cuda()
+    d_slot = torch.from_numpy(np.concatenate([s[1] for s in scans]).astype(np.int32)).cuda()
+    counts = G.object_counts_batch(d_slot, L).cpu().numpy()
+    want = np.concatenate([SG.split_ref(s[1], s[2])[0] for s in scans]) if scans else np.zeros(0)
+    assert counts.dtype == np.int32 and np.array_equal(counts, want)
+    # destinations in REVERSE slot order, so that the output order is not the order of the input
+    dest = np.full(L.total_slots, -1, dtype=np.int64)
+    pos = 0
+    for si in reversed(range(len(scans))):
+        k0 = int(L.slot_off[si])
+        for k in reversed(range(scans[si][2])):
+            if k not in scans[si][3]:
+                dest[k0 + k] = pos
+                pos += int(counts[k0 + k])
+    perm, out = G.object_partition_batch(d_pts, d_slot, L, dest, counts)
+    perm2, out2 = G.object_partition_batch(d_pts, d_slot, L, dest, counts)
+    assert torch.equal(perm, perm2) and torch.equal(out.view(torch.int32), out2.view(torch.int32))          # identical bits
+    perm, out = perm.cpu().numpy(), out.cpu().numpy()
+    assert len(perm) == pos and out.shape == (pos, 3)
+    for si, (pts, slot, ns, drop) in enumerate(scans):
+        k0 = int(L.slot_off[si])
+        for k in range(ns):
+            if k in drop:
+                continue
+            idx = np.flatnonzero(slot == k)
+            d = int(dest[k0 + k])
+            assert np.array_equal(perm[d:d + len(idx)], idx), (si, k)
+            assert np.array_equal(out[d:d + len(idx)].view(np.int32), pts[idx].view(np.int32)), (si, k)
+
+
+def test_partition_every_size_alone():
+    for scan in _partition_scans():
+        _run_partition([scan])
+
+
+def test_partition_all_sizes_as_one_batch_with_an_empty_scan():
+    scans = _partition_scans()
+    scans.insert(3, (np.zeros((0, 3), dtype=np.float32), np.zeros(0, dtype=np.int64), 4, {1}))
+    scans.insert(6, (np.ones((10, 3), dtype=np.float32), np.zeros(10, dtype=np.int64), 0, set()))           # points, but no slot at all
+    _run_partition(scans)
+
+
+# ---- completion --------------------------------------------------------------------------------------------------------------------------
+def _graphs():
+    """(N, listed pairs, listed triples' relation ids) for every N of interest and every kind of listed set."""
+    from sgaligner_amd.preprocessing import scene_graphs as G
+    rng = np.random.default_rng(22)
+    out = []
+    for n in (2, 3, 31, 32, 33, 64, 65, 200, G.graph_max_nodes()):
+        every = np.argwhere(~np.eye(n, dtype=bool))
+        kinds = [every[:1],                                                            # a single pair
+                 every[::-1] if n <= 65 else every[rng.permutation(len(every))[:3 * n]][::-1],     # reverse order (all of them for small N)
+                 np.concatenate([[[n - 1, n - 1]], every[rng.choice(len(every), min(len(every), 2 * n))], [[0, 0]]]),    # self pairs, duplicates
+                 np.zeros((0, 2), dtype=np.int64)]                                     # nothing listed
+        if n <= 33:
+            kinds.append(every)                                                        # all pairs listed: nothing to add
+        for k, pairs in enumerate(kinds):
+            extra = [0, 1, 5][k % 3]                                                   # extra triples: Tr > P
+            out.append((n, pairs, rng.integers(0, 41, len(pairs) + extra)))
+    return out
+
+
+def test_completion_every_size_in_one_launch():
+    from sgaligner_amd.preprocessing import scene_graphs as G
+    graphs = _graphs()
+    got = G.graph_complete_batch([g[0] for g in graphs], [g[1] for g in graphs], [g[2] for g in graphs], 0, 41)
+    assert len(got) == len(graphs)
+    for (n, pairs, rels), (edges, bow) in zip(graphs, got):
+        want_e, want_b = SG.complete_ref(n, pairs, rels, 0, 41)
+        assert edges.dtype == np.int64 and edges.shape == want_e.shape and np.array_equal(edges, want_e), (n, len(pairs))
+        assert bow.dtype == np.int32 and np.array_equal(bow, want_b), (n, len(pairs))
+        assert bow.sum() == len(edges)
+    # a `none` that is not column 0, and one graph alone
+    (edges, bow), = G.graph_complete_batch([5], [[[1, 2], [1, 2], [3, 3]]], [[7, 8, 9, 10]], 40, 41)
+    want_e, want_b = SG.complete_ref(5, [[1, 2], [1, 2], [3, 3]], [7, 8, 9, 10], 40, 41)
+    assert np.array_equal(edges, want_e) and np.array_equal(bow, want_b) and bow[0, 10] == 1              # edge 3 = (0, 1) reads triple 3
+    with pytest.raises(ValueError, match=f'at most {G.graph_max_nodes()}'):
+        G.graph_complete_batch([G.graph_max_nodes() + 1], [np.zeros((0, 2))], [[]], 0, 41)
+
+
+def test_bow_counts_equals_add_at():
+    from sgaligner_amd.preprocessing import scene_graphs as G
+    rng = np.random.default_rng(23)
+    rows, cols = rng.integers(0, 50, 5000), rng.integers(0, 7, 5000)                   # 350 cells, 5000 entries: every pair repeats
+    got = G.bow_counts(rows, cols, 50, 7)
+    assert got.dtype == np.int32 and np.array_equal(got, SG.bow_ref(rows, cols, 50, 7))
+    assert np.array_equal(G.bow_counts([3, 3, 3], [1, 1, 1], 4, 2), [[0, 0], [0, 0], [0, 0], [0, 3]])
+    empty = G.bow_counts([], [], 6, 164)
+    assert empty.shape == (6, 164) and not empty.any()
+    assert G.bow_counts([], [], 0, 5).shape == (0, 5)
+
+
+# ---- end to end --------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope='module')
+def fixture():
+    return SG.load_fixture()
+
+
+def _scan(c):
+    return (c['scan_id'], c['vertices'], c['objects'], c['relationships'])
+
+
+def test_process_scans_equals_the_reference_records(fixture):
+    """Every key exactly, obj_points bit for bit.  rel_trans within 2e-12 x the largest |coordinate| of the scan: it is the difference of two
+    barycentres, each of which tests/test_hull_gpu.py holds to 1e-12 of the scale against Qhull (segment sum vs np.mean: another order)."""
+    from sgaligner_amd.preprocessing import scene_graphs as G
+    cases, records, vocab = fixture
+    mine, total = [], {'hull_device': 0, 'hull_qhull': 0, 'fps': 0, 'random': 0}
+    for c in cases:
+        np.random.seed(c['seed'])
+        (rec,), info = G.process_scans([_scan(c)], SG.REL2IDX, c['resolutions'], c['min_obj_points'], return_info=True)
+        np.random.seed(c['seed'])
+        one = G.process_scan(*_scan(c), SG.REL2IDX, c['resolutions'], c['min_obj_points'])
+        SG.assert_records_equal(one, rec, what=c['scan_id'] + ' single-scan form')
+        mine.append(rec)
+        for k in total:
+            total[k] += info[k]
+    feats, my_vocab = G.bow_attr_feats(mine, SG.WORD_2_IX)
+    assert my_vocab == vocab and list(my_vocab) == list(vocab)
+    for c, m, r, f in zip(cases, mine, records, feats):
+        SG.assert_records_equal(m, r, skip=('rel_trans',), what=c['scan_id'])
+        if isinstance(r, int):
+            assert f is None
+            continue
+        assert f is m['bow_vec_object_attr_feats'] and set(m) == set(G.RECORD_KEYS) | {'bow_vec_object_edge_feats', 'bow_vec_object_attr_feats'}
+        scale = max(float(np.abs(c['vertices'][k]).max()) for k in 'xyz')
+        assert m['rel_trans'].dtype == np.float64 and m['rel_trans'].shape == r['rel_trans'].shape
+        err = float(np.abs(m['rel_trans'] - r['rel_trans']).max())
+        print(c['scan_id'], 'rel_trans error', err, 'bound', 2e-12 * scale)
+        assert err <= 2e-12 * scale, (c['scan_id'], err)
+    # the exact comparison is not vacuous: the device hull and both FPS branches served objects of the fixture
+    assert total['hull_device'] >= 1 and total['fps'] >= 1 and total['random'] >= 1, total
+
+
+def test_a_batch_equals_the_scans_one_by_one(fixture):
+    """All fixture scans in one call, with the draw sequence of the scans processed one after the other."""
+    from sgaligner_amd.preprocessing import scene_graphs as G
+    cases = fixture[0]
+    np.random.seed(31)
+    singles = [G.process_scan(*_scan(c), SG.REL2IDX, (64, 32), 50) for c in cases]
+    tail = np.random.randint(0, 2 ** 31)
+    np.random.seed(31)
+    batch = G.process_scans([_scan(c) for c in cases], SG.REL2IDX, (64, 32), 50)
+    assert np.random.randint(0, 2 ** 31) == tail                                       # the same number of draws
+    assert [isinstance(r, int) for r in batch] == [False, False, False, False, True, True, True]
+    for c, one, many in zip(cases, singles, batch):
+        SG.assert_records_equal(many, one, what=c['scan_id'])
+
+
+def test_written_records_feed_the_dataset_and_the_collate(fixture, tmp_path):
+    import json
+    from sgaligner_amd.datasets import Scan3RDataset, synthetic_scan3r as S
+    from sgaligner_amd.preprocessing import scene_graphs as G
+    cases = fixture[0][:4]
+    np.random.seed(5)
+    records = G.process_scans([_scan(c) for c in cases], SG.REL2IDX, (64, 32), 50)
+    used = {a for r in records for attrs in r['object_attributes'] for a in attrs}
+    _, vocab = G.bow_attr_feats(records, {f'w{k}': k for k in range(164 - len(used))})  # with the scans' own words: the model's 164
+    assert len(vocab) == 164
+    root = str(tmp_path)
+    assert G.write_records(records + [-1], root) == [c['scan_id'] for c in cases]
+    for c in cases:
+        os.makedirs(os.path.join(root, 'scans', c['scan_id']))
+        np.save(os.path.join(root, 'scans', c['scan_id'], 'data.npy'), c['vertices'])
+    anchors = [{'src': 'scan_a', 'ref': 'scan_b', 'overlap': 0.4, 'anchorIds': [1, 2, 3, 4, 5]},
+               {'src': 'scan_c', 'ref': 'scan_d', 'overlap': 0.2, 'anchorIds': [1, 2, 3]}]
+    for split in ('train', 'val'):
+        with open(os.path.join(root, 'files', 'orig', f'anchors_{split}.json'), 'w') as fh:
+            json.dump(anchors, fh)
+    ds = Scan3RDataset(S.make_cfg(root, pc_res=32), 'val')
+    item = ds[0]
+    n = [r['objects_count'] for r in records]
+    assert item['tot_obj_pts'].shape == (n[0] + n[1], 32, 3) and item['tot_obj_pts'].dtype == torch.float32
+    assert item['edges'].dtype == torch.int64 and item['edges'].shape == (records[0]['edges_count'] + records[1]['edges_count'], 2)
+    dd = ds.collate_fn([ds[i] for i in range(len(ds))])
+    tot = sum(n)
+    assert dd['tot_obj_pts'].shape == (tot, 32, 3) and dd['tot_obj_pts'].dtype == torch.float32
+    assert dd['tot_bow_vec_object_edge_feats'].shape == (tot, 41) and dd['tot_bow_vec_object_edge_feats'].dtype == torch.float64
+    assert dd['tot_bow_vec_object_attr_feats'].shape == (tot, 164) and dd['tot_bow_vec_object_attr_feats'].dtype == torch.float64
+    assert dd['tot_rel_pose'].shape == (tot, 3) and dd['tot_rel_pose'].dtype == torch.float64
+    assert dd['edges'].shape == (sum(r['edges_count'] for r in records), 2) and dd['edges'].dtype == torch.int64
+    assert dd['graph_per_obj_count'].tolist() == [[n[0], n[1]], [n[2], n[3]]] and dd['batch_size'] == 2
+    assert dd['e1i_count'].tolist() == [5, 3] and dd['global_obj_ids'].shape == (tot,)
+    import pickle
+    with open(os.path.join(root, 'files', 'orig', 'data', 'scan_a.pkl'), 'rb') as fh:
+        SG.assert_records_equal(pickle.load(fh), records[0], what='pickle round trip')
