@@ -18,7 +18,7 @@
 // a pure function of the input.
 #include <math.h>
 
-#include "sga_common.h"
+#include "packed.h"
 
 namespace {
 
@@ -156,14 +156,10 @@ extern "C" int sga_nn_search(const double* pts, const int32_t* offsets, int n_cl
     if (n_pairs == 0 || total_queries == 0 || max_queries == 0) return SGA_OK;               // nothing to write
     SGA_CHECK_ARG(offsets && pairs && out_offsets && out_dist && out_idx, "sga_nn_search: null pointer");
     SGA_CHECK_ARG(pts || total_points == 0, "sga_nn_search: null point array");
-    SGA_CHECK_ARG(((uintptr_t)pts % 8) == 0 && ((uintptr_t)out_dist % 8) == 0 && ((uintptr_t)workspace % 8) == 0 &&
-                  ((uintptr_t)offsets % 4) == 0 && ((uintptr_t)pairs % 4) == 0 && ((uintptr_t)out_offsets % 4) == 0 && ((uintptr_t)out_idx % 4) == 0,
+    SGA_CHECK_ARG(sga_aligned(8, pts, out_dist, workspace) && sga_aligned(4, offsets, pairs, out_offsets, out_idx),
                   "sga_nn_search: misaligned pointer (fp64 arrays need 8 bytes, int32 arrays 4)");
-    if (offsets_host) {
-        SGA_CHECK_ARG(offsets_host[0] == 0 && offsets_host[n_clouds] == total_points, "sga_nn_search: offsets must run from 0 to total_points");
-        for (int i = 0; i < n_clouds; ++i)
-            SGA_CHECK_ARG(offsets_host[i + 1] >= offsets_host[i], "sga_nn_search: offsets decrease at cloud %d", i);
-    }
+    const SgaPrefix OFFSETS{"offsets", "decrease", "cloud", "total_points", nullptr, nullptr};
+    if (int rc = sga_check_prefix("sga_nn_search", OFFSETS, offsets_host, n_clouds, total_points, SGA_ANY)) return rc;
     if (pairs_host) {
         for (int p = 0; p < n_pairs; ++p) {
             const int qc = pairs_host[2 * p], sc = pairs_host[2 * p + 1];
@@ -176,8 +172,8 @@ extern "C" int sga_nn_search(const double* pts, const int32_t* offsets, int n_cl
     }
     const long n_chunks = nn_chunks(max_support, chunk);
     const long q_tiles = ((long)max_queries + NN_QTILE - 1) / NN_QTILE, m_tiles = ((long)max_queries + NN_THREADS - 1) / NN_THREADS;
-    SGA_CHECK_ARG(q_tiles * n_chunks * n_pairs < (1L << 31) && m_tiles * n_pairs < (1L << 31),
-                  "sga_nn_search: %ld x %ld x %d workgroups exceed the grid limit; raise chunk or split the job list", q_tiles, n_chunks, n_pairs);
+    if (int rc = sga_check_grid("sga_nn_search", q_tiles, n_chunks, n_pairs, "raise chunk or split the job list")) return rc;
+    if (int rc = sga_check_grid("sga_nn_search", m_tiles, 1, n_pairs, "raise chunk or split the job list")) return rc;
     const size_t need = sga_nn_workspace_bytes(total_queries, max_support, chunk);
     if (need > 0 && (!workspace || workspace_bytes < need)) {
         sga_set_error("sga_nn_search: workspace of %zu bytes needed, %zu given", need, workspace ? workspace_bytes : (size_t)0);

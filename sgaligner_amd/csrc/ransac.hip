@@ -24,7 +24,7 @@
 // belongs to it can never disagree.
 #include <math.h>
 
-#include "sga_common.h"
+#include "packed.h"
 
 namespace {
 
@@ -465,29 +465,18 @@ extern "C" int sga_ransac_rigid(const double* corr, const int32_t* offsets, int 
     SGA_CHECK_ARG(offsets && hyp_offsets && transform && inlier_count && best_hyp && status, "sga_ransac_rigid: null pointer");
     SGA_CHECK_ARG((corr && inlier_mask) || total_rows == 0, "sga_ransac_rigid: null pointer (corr / inlier_mask with total_rows %d)", total_rows);
     SGA_CHECK_ARG((samples && hyp_count) || total_hyp == 0, "sga_ransac_rigid: null pointer (samples / hyp_count with total_hyp %d)", total_hyp);
-    SGA_CHECK_ARG(((uintptr_t)corr % 8) == 0 && ((uintptr_t)transform % 8) == 0 && ((uintptr_t)workspace % 8) == 0 &&
-                  ((uintptr_t)offsets % 4) == 0 && ((uintptr_t)samples % 4) == 0 && ((uintptr_t)hyp_offsets % 4) == 0 &&
-                  ((uintptr_t)inlier_count % 4) == 0 && ((uintptr_t)best_hyp % 4) == 0 && ((uintptr_t)status % 4) == 0 &&
-                  ((uintptr_t)hyp_count % 4) == 0,
+    SGA_CHECK_ARG(sga_aligned(8, corr, transform, workspace) && sga_aligned(4, offsets, samples, hyp_offsets, inlier_count, best_hyp, status, hyp_count),
                   "sga_ransac_rigid: misaligned pointer (fp64 arrays need 8 bytes, int32 arrays 4)");
-    if (offsets_host) {
-        SGA_CHECK_ARG(offsets_host[0] == 0 && offsets_host[n_jobs] == total_rows, "sga_ransac_rigid: offsets must run from 0 to total_rows");
-        for (int i = 0; i < n_jobs; ++i) {
-            SGA_CHECK_ARG(offsets_host[i + 1] >= offsets_host[i], "sga_ransac_rigid: offsets decrease at job %d", i);
-            SGA_CHECK_ARG(offsets_host[i + 1] - offsets_host[i] <= max_rows, "sga_ransac_rigid: job %d has more rows than max_rows %d", i, max_rows);
-        }
-    }
-    if (hyp_offsets_host) {
-        SGA_CHECK_ARG(hyp_offsets_host[0] == 0 && hyp_offsets_host[n_jobs] == total_hyp, "sga_ransac_rigid: hyp_offsets must run from 0 to total_hyp");
-        for (int i = 0; i < n_jobs; ++i) {
-            SGA_CHECK_ARG(hyp_offsets_host[i + 1] >= hyp_offsets_host[i], "sga_ransac_rigid: hyp_offsets decrease at job %d", i);
-            SGA_CHECK_ARG(hyp_offsets_host[i + 1] - hyp_offsets_host[i] <= max_hyp, "sga_ransac_rigid: job %d has more hypotheses than max_hyp %d", i, max_hyp);
-        }
-    }
+    const SgaPrefix OFFSETS{"offsets", "decrease", "job", "total_rows", "rows", "max_rows"};
+    const SgaPrefix HYP_OFFSETS{"hyp_offsets", "decrease", "job", "total_hyp", "hypotheses", "max_hyp"};
+    if (int rc = sga_check_prefix("sga_ransac_rigid", OFFSETS, offsets_host, n_jobs, total_rows, max_rows)) return rc;
+    if (int rc = sga_check_prefix("sga_ransac_rigid", HYP_OFFSETS, hyp_offsets_host, n_jobs, total_hyp, max_hyp)) return rc;
     const long n_chunks = rs_chunks(max_rows, chunk), r_chunks = rs_rchunks(max_rows);
     const long h_tiles = ((long)max_hyp + RS_HTILE - 1) / RS_HTILE, g_tiles = ((long)max_hyp + RS_THREADS - 1) / RS_THREADS;
-    SGA_CHECK_ARG(h_tiles * n_chunks * n_jobs < (1L << 31) && g_tiles * n_jobs < (1L << 31) && r_chunks * n_jobs < (1L << 31),
-                  "sga_ransac_rigid: %ld x %ld x %d workgroups exceed the grid limit; raise chunk or split the job list", h_tiles, n_chunks, n_jobs);
+    const char* advice = "raise chunk or split the job list";
+    if (int rc = sga_check_grid("sga_ransac_rigid", h_tiles, n_chunks, n_jobs, advice)) return rc;
+    if (int rc = sga_check_grid("sga_ransac_rigid", g_tiles, 1, n_jobs, advice)) return rc;
+    if (int rc = sga_check_grid("sga_ransac_rigid", r_chunks, 1, n_jobs, advice)) return rc;
     const RSLayout L = rs_layout(n_jobs, total_hyp, max_rows, chunk);
     if (!workspace || workspace_bytes < L.total) {
         sga_set_error("sga_ransac_rigid: workspace of %zu bytes needed, %zu given", L.total, workspace ? workspace_bytes : (size_t)0);

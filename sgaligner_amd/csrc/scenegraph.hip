@@ -24,7 +24,7 @@
 // idx-th entry of the TRIPLES list (listed triples, then `none`): the reference indexes the triples with the edge index
 // (preprocess.py:303-306), and the triples list is longer than the pair list whenever a pair is listed with two relations.
 // Every kernel re-derives its ranges from the device offset arrays and does nothing on a bad one.
-#include "sga_common.h"
+#include "packed.h"
 
 #include <algorithm>
 #include <vector>
@@ -193,15 +193,6 @@ __device__ __forceinline__ unsigned gc_missing(const unsigned* adj, int N, int W
     return m;
 }
 
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(GC_THREADS) void graph_complete_kernel(const int* __restrict__ node_off, const int* __restrict__ pair_off,
                                                                     const int* __restrict__ trip_off, const int* __restrict__ edge_off,
                                                                     int n_graphs, int total_nodes, int total_pairs, int total_trips,
@@ -290,15 +281,15 @@ __global__ __launch_bounds__(SG_THREADS) void bow_counts_kernel(const int* __res
     atomicAdd(&out[(size_t)r * V + c], 1);
 }
 
-int sg_check_offsets(const char* who, const char* name, const int32_t* off, int n, long long* total) {
-    SGA_CHECK_ARG(off != nullptr, "%s: %s (host copy) is null", who, name);
-    SGA_CHECK_ARG(off[0] == 0, "%s: %s must start at 0", who, name);
-    for (int i = 0; i < n; ++i) SGA_CHECK_ARG(off[i + 1] >= off[i], "%s: %s decreases at %d", who, name, i);
+// A host copy sga_graph_complete cannot do without: it is where the totals come from.
+int gc_offsets(const char* name, const int32_t* off, int n, long long* total) {
+    SGA_CHECK_ARG(off != nullptr, "sga_graph_complete: %s (host copy) is null", name);
     *total = off[n];
-    return SGA_OK;
+    return sga_check_prefix("sga_graph_complete", SgaPrefix{name, "decreases", "", nullptr, nullptr, nullptr}, off, n, SGA_ANY, SGA_ANY);
 }
 
-bool sg_aligned4(const void* p) { return ((uintptr_t)p % 4) == 0; }
+const SgaPrefix PT_OFF{"pt_off", "decreases", "scan", "total_points", nullptr, nullptr};
+const SgaPrefix SLOT_OFF{"slot_off", "decreases", "scan", "total_slots", nullptr, nullptr};
 
 }  // namespace
 
@@ -315,26 +306,18 @@ extern "C" int sga_object_counts(const int32_t* slot, const int32_t* pt_off, con
     SGA_CHECK_ARG(max_points <= total_points, "sga_object_counts: max_points %d exceeds total_points %d", max_points, total_points);
     if (n_scans == 0 || total_slots == 0) return SGA_OK;                                                     // nothing to write
     SGA_CHECK_ARG(counts && (max_points == 0 || (slot && pt_off && slot_off)), "sga_object_counts: null pointer");
-    SGA_CHECK_ARG(sg_aligned4(slot) && sg_aligned4(pt_off) && sg_aligned4(slot_off) && sg_aligned4(counts),
+    SGA_CHECK_ARG(sga_aligned(4, slot, pt_off, slot_off, counts),
                   "sga_object_counts: misaligned pointer (32-bit arrays need 4 bytes)");
-    if (pt_off_host) {
-        SGA_CHECK_ARG(pt_off_host[0] == 0 && pt_off_host[n_scans] == total_points, "sga_object_counts: pt_off must run from 0 to total_points");
-        for (int i = 0; i < n_scans; ++i) SGA_CHECK_ARG(pt_off_host[i + 1] >= pt_off_host[i], "sga_object_counts: pt_off decreases at scan %d", i);
+    if (int rc = sga_check_prefix("sga_object_counts", PT_OFF, pt_off_host, n_scans, total_points, SGA_ANY)) return rc;
+    if (pt_off_host)
         for (int i = 0; i < n_scans; ++i)
             SGA_CHECK_ARG(pt_off_host[i + 1] - pt_off_host[i] <= max_points, "sga_object_counts: scan %d is larger than max_points %d", i, max_points);
-    }
-    if (slot_off_host) {
-        SGA_CHECK_ARG(slot_off_host[0] == 0 && slot_off_host[n_scans] == total_slots, "sga_object_counts: slot_off must run from 0 to total_slots");
-        for (int i = 0; i < n_scans; ++i) SGA_CHECK_ARG(slot_off_host[i + 1] >= slot_off_host[i], "sga_object_counts: slot_off decreases at scan %d", i);
-    }
+    if (int rc = sga_check_prefix("sga_object_counts", SLOT_OFF, slot_off_host, n_scans, total_slots, SGA_ANY)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(counts, 0, (size_t)total_slots * sizeof(int32_t), st) != hipSuccess) {
-        sga_set_error("sga_object_counts: memset failed");
-        return SGA_ERR_HIP;
-    }
+    if (int rc = sga_zero("sga_object_counts", counts, (size_t)total_slots * sizeof(int32_t), st)) return rc;
     if (max_points == 0) return SGA_OK;
     const long p_tiles = ((long)max_points + SG_TILE - 1) / SG_TILE;
-    SGA_CHECK_ARG(p_tiles * n_scans < (1L << 31), "sga_object_counts: %ld x %d workgroups exceed the grid limit; split the scan list", p_tiles, n_scans);
+    if (int rc = sga_check_grid("sga_object_counts", p_tiles, 1, n_scans, "split the scan list")) return rc;
     hipLaunchKernelGGL(object_counts_kernel, dim3((unsigned)(p_tiles * n_scans)), dim3(SG_THREADS), 0, st, slot, pt_off, slot_off, n_scans,
                        total_points, total_slots, (int)p_tiles, counts);
     SGA_CHECK_LAUNCH("sga_object_counts");
@@ -359,16 +342,15 @@ extern "C" int sga_object_partition(const float* pts, const int32_t* slot, const
                   n_kept_points, total_points, total_slots);
     SGA_CHECK_ARG(max_slots <= SG_LDS_SLOTS, "sga_object_partition: %d slots in one scan, at most %d are supported", max_slots, SG_LDS_SLOTS);
     SGA_CHECK_ARG(pt_off_host && slot_off_host && dest_off_host && counts_host, "sga_object_partition: the host copies of the offsets are required");
-    SGA_CHECK_ARG(pt_off_host[0] == 0 && pt_off_host[n_scans] == total_points, "sga_object_partition: pt_off must run from 0 to total_points");
-    SGA_CHECK_ARG(slot_off_host[0] == 0 && slot_off_host[n_scans] == total_slots, "sga_object_partition: slot_off must run from 0 to total_slots");
+    if (int rc = sga_prefix_ends("sga_object_partition", PT_OFF, pt_off_host, n_scans, total_points)) return rc;
+    if (int rc = sga_prefix_ends("sga_object_partition", SLOT_OFF, slot_off_host, n_scans, total_slots)) return rc;
     for (int i = 0; i < n_scans; ++i) {
-        SGA_CHECK_ARG(pt_off_host[i + 1] >= pt_off_host[i], "sga_object_partition: pt_off decreases at scan %d", i);
-        SGA_CHECK_ARG(slot_off_host[i + 1] >= slot_off_host[i], "sga_object_partition: slot_off decreases at scan %d", i);
+        if (int rc = sga_prefix_step("sga_object_partition", PT_OFF, pt_off_host, i)) return rc;
+        if (int rc = sga_prefix_step("sga_object_partition", SLOT_OFF, slot_off_host, i)) return rc;
     }
-    for (int i = 0; i < n_scans; ++i) {
+    for (int i = 0; i < n_scans; ++i)
         SGA_CHECK_ARG(pt_off_host[i + 1] - pt_off_host[i] <= max_points && slot_off_host[i + 1] - slot_off_host[i] <= max_slots,
                       "sga_object_partition: scan %d is larger than max_points %d / max_slots %d", i, max_points, max_slots);
-    }
     {   // the kept objects' output ranges: inside [0, n_kept_points), disjoint
         std::vector<std::pair<long long, long long>> rng;
         for (int k = 0; k < total_slots; ++k) {
@@ -384,8 +366,8 @@ extern "C" int sga_object_partition(const float* pts, const int32_t* slot, const
     }
     if (n_scans == 0 || n_kept_points == 0 || max_points == 0 || max_slots == 0) return SGA_OK;              // nothing to write
     SGA_CHECK_ARG(pts && slot && pt_off && slot_off && dest_off && perm && pts_out && ws, "sga_object_partition: null pointer");
-    SGA_CHECK_ARG(sg_aligned4(pts) && sg_aligned4(slot) && sg_aligned4(pt_off) && sg_aligned4(slot_off) && sg_aligned4(dest_off) && sg_aligned4(perm) &&
-                  sg_aligned4(pts_out) && sg_aligned4(ws), "sga_object_partition: misaligned pointer (32-bit arrays need 4 bytes)");
+    SGA_CHECK_ARG(sga_aligned(4, pts, slot, pt_off, slot_off, dest_off, perm, pts_out, ws),
+                  "sga_object_partition: misaligned pointer (32-bit arrays need 4 bytes)");
     const size_t need = sga_object_partition_ws_bytes(n_scans, max_points, max_slots);
     if (ws_bytes < need) {
         sga_set_error("sga_object_partition: workspace of %zu bytes, %zu needed", ws_bytes, need);
@@ -393,7 +375,7 @@ extern "C" int sga_object_partition(const float* pts, const int32_t* slot, const
     }
     SGA_CHECK_ARG(need / sizeof(int32_t) < ((size_t)1 << 31), "sga_object_partition: the tile table exceeds 2^31 counters; split the scan list");
     const long p_tiles = ((long)max_points + SG_TILE - 1) / SG_TILE;
-    SGA_CHECK_ARG(p_tiles * n_scans < (1L << 31), "sga_object_partition: %ld x %d workgroups exceed the grid limit; split the scan list", p_tiles, n_scans);
+    if (int rc = sga_check_grid("sga_object_partition", p_tiles, 1, n_scans, "split the scan list")) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     int* w = static_cast<int*>(ws);
     const unsigned grid = (unsigned)(p_tiles * n_scans);
@@ -416,10 +398,10 @@ extern "C" int sga_graph_complete(const int32_t* node_off, const int32_t* pair_o
     SGA_CHECK_ARG(none_id >= 0 && none_id < V, "sga_graph_complete: the id of `none` (%d) is outside the vocabulary of %d", none_id, V);
     if (n_graphs == 0) return SGA_OK;
     long long tn = 0, tp = 0, tt = 0, te = 0;
-    if (int rc = sg_check_offsets("sga_graph_complete", "node_off", node_off_host, n_graphs, &tn)) return rc;
-    if (int rc = sg_check_offsets("sga_graph_complete", "pair_off", pair_off_host, n_graphs, &tp)) return rc;
-    if (int rc = sg_check_offsets("sga_graph_complete", "trip_off", trip_off_host, n_graphs, &tt)) return rc;
-    if (int rc = sg_check_offsets("sga_graph_complete", "edge_off", edge_off_host, n_graphs, &te)) return rc;
+    if (int rc = gc_offsets("node_off", node_off_host, n_graphs, &tn)) return rc;
+    if (int rc = gc_offsets("pair_off", pair_off_host, n_graphs, &tp)) return rc;
+    if (int rc = gc_offsets("trip_off", trip_off_host, n_graphs, &tt)) return rc;
+    if (int rc = gc_offsets("edge_off", edge_off_host, n_graphs, &te)) return rc;
     SGA_CHECK_ARG(tn * V < (1LL << 31), "sga_graph_complete: %lld nodes x %d words exceed 2^31 counters; split the graph list", tn, V);
     for (int g = 0; g < n_graphs; ++g) {
         const long long N = node_off_host[g + 1] - node_off_host[g], P = pair_off_host[g + 1] - pair_off_host[g],
@@ -437,14 +419,11 @@ extern "C" int sga_graph_complete(const int32_t* node_off, const int32_t* pair_o
                           rels_host[t], t, V);
     SGA_CHECK_ARG(node_off && pair_off && trip_off && edge_off && n_edges, "sga_graph_complete: null pointer");
     SGA_CHECK_ARG((pairs || tp == 0) && (rels || tt == 0) && (edges || te == 0) && (bow || tn == 0), "sga_graph_complete: null pointer");
-    SGA_CHECK_ARG(((uintptr_t)edges % 8) == 0 && sg_aligned4(node_off) && sg_aligned4(pair_off) && sg_aligned4(trip_off) && sg_aligned4(edge_off) &&
-                  sg_aligned4(pairs) && sg_aligned4(rels) && sg_aligned4(n_edges) && sg_aligned4(bow),
+    SGA_CHECK_ARG(sga_aligned(8, edges) && sga_aligned(4, node_off, pair_off, trip_off, edge_off, pairs, rels, n_edges, bow),
                   "sga_graph_complete: misaligned pointer (64-bit arrays need 8 bytes, 32-bit arrays 4)");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (tn && hipMemsetAsync(bow, 0, (size_t)tn * V * sizeof(int32_t), st) != hipSuccess) {
-        sga_set_error("sga_graph_complete: memset failed");
-        return SGA_ERR_HIP;
-    }
+    if (tn)
+        if (int rc = sga_zero("sga_graph_complete", bow, (size_t)tn * V * sizeof(int32_t), st)) return rc;
     hipLaunchKernelGGL(graph_complete_kernel, dim3((unsigned)n_graphs), dim3(GC_THREADS), 0, st, node_off, pair_off, trip_off, edge_off, n_graphs, (int)tn,
                        (int)tp, (int)tt, (int)te, pairs, rels, none_id, V, reinterpret_cast<long long*>(edges), n_edges, bow);
     SGA_CHECK_LAUNCH("sga_graph_complete");
@@ -461,12 +440,9 @@ extern "C" int sga_bow_counts(const int32_t* rows, const int32_t* cols, int n, i
     }
     if (T == 0 || V == 0) return SGA_OK;                                                                     // nothing to write
     SGA_CHECK_ARG(out && (n == 0 || (rows && cols)), "sga_bow_counts: null pointer");
-    SGA_CHECK_ARG(sg_aligned4(rows) && sg_aligned4(cols) && sg_aligned4(out), "sga_bow_counts: misaligned pointer (32-bit arrays need 4 bytes)");
+    SGA_CHECK_ARG(sga_aligned(4, rows, cols, out), "sga_bow_counts: misaligned pointer (32-bit arrays need 4 bytes)");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(out, 0, (size_t)T * V * sizeof(int32_t), st) != hipSuccess) {
-        sga_set_error("sga_bow_counts: memset failed");
-        return SGA_ERR_HIP;
-    }
+    if (int rc = sga_zero("sga_bow_counts", out, (size_t)T * V * sizeof(int32_t), st)) return rc;
     if (n == 0) return SGA_OK;
     hipLaunchKernelGGL(bow_counts_kernel, dim3((unsigned)(((long)n + SG_THREADS - 1) / SG_THREADS)), dim3(SG_THREADS), 0, st, rows, cols, n, T, V, out);
     SGA_CHECK_LAUNCH("sga_bow_counts");

@@ -22,7 +22,7 @@
 // previous row of `cum` (or nothing after a closed subscan), so `cum` may be `vis` itself.  objcount_kernel: one lane per point of a bit row,
 // a workgroup-private LDS histogram flushed with integer atomics (global integer atomics above VIS_LDS_SLOTS slots): exact, order-independent.
 // All three re-derive the scan's ranges from the device offset arrays and do nothing on a bad one.
-#include "sga_common.h"
+#include "packed.h"
 
 namespace {
 
@@ -203,14 +203,10 @@ __global__ __launch_bounds__(OC_THREADS) void objcount_kernel(const u64* __restr
 // The host copies of the offset arrays, when given: monotone, covering, and vis_off the prefix sum of F_t * ceil(N_t / 64).
 int vis_check_host(const char* who, int n_scans, int total_points, int total_frames, long long total_words, const int32_t* pt_off_host,
                    const int32_t* fr_off_host, const int64_t* vis_off_host) {
-    if (pt_off_host) {
-        SGA_CHECK_ARG(pt_off_host[0] == 0 && pt_off_host[n_scans] == total_points, "%s: pt_off must run from 0 to total_points", who);
-        for (int i = 0; i < n_scans; ++i) SGA_CHECK_ARG(pt_off_host[i + 1] >= pt_off_host[i], "%s: pt_off decreases at scan %d", who, i);
-    }
-    if (fr_off_host) {
-        SGA_CHECK_ARG(fr_off_host[0] == 0 && fr_off_host[n_scans] == total_frames, "%s: fr_off must run from 0 to total_frames", who);
-        for (int i = 0; i < n_scans; ++i) SGA_CHECK_ARG(fr_off_host[i + 1] >= fr_off_host[i], "%s: fr_off decreases at scan %d", who, i);
-    }
+    const SgaPrefix PT_OFF{"pt_off", "decreases", "scan", "total_points", nullptr, nullptr};
+    const SgaPrefix FR_OFF{"fr_off", "decreases", "scan", "total_frames", nullptr, nullptr};
+    if (int rc = sga_check_prefix(who, PT_OFF, pt_off_host, n_scans, total_points, SGA_ANY)) return rc;
+    if (int rc = sga_check_prefix(who, FR_OFF, fr_off_host, n_scans, total_frames, SGA_ANY)) return rc;
     if (vis_off_host) {
         SGA_CHECK_ARG(vis_off_host[0] == 0, "%s: vis_off must start at 0", who);
         for (int i = 0; i < n_scans; ++i) {
@@ -242,8 +238,7 @@ extern "C" int sga_frame_visibility(const float* pts, const int32_t* pt_off, con
                   max_points, max_frames, total_points, total_frames);
     if (n_scans == 0 || max_points == 0 || max_frames == 0 || total_words == 0) return SGA_OK;               // nothing to write
     SGA_CHECK_ARG(pts && pt_off && w2c && fr_off && intr && vis_off && vis, "sga_frame_visibility: null pointer");
-    SGA_CHECK_ARG(((uintptr_t)w2c % 8) == 0 && ((uintptr_t)intr % 8) == 0 && ((uintptr_t)vis_off % 8) == 0 && ((uintptr_t)vis % 8) == 0 &&
-                  ((uintptr_t)pts % 4) == 0 && ((uintptr_t)pt_off % 4) == 0 && ((uintptr_t)fr_off % 4) == 0,
+    SGA_CHECK_ARG(sga_aligned(8, w2c, intr, vis_off, vis) && sga_aligned(4, pts, pt_off, fr_off),
                   "sga_frame_visibility: misaligned pointer (64-bit arrays need 8 bytes, 32-bit arrays 4)");
     if (int rc = vis_check_host("sga_frame_visibility", n_scans, total_points, total_frames, total_words, pt_off_host, fr_off_host, vis_off_host)) return rc;
     if (pt_off_host && fr_off_host)
@@ -251,8 +246,7 @@ extern "C" int sga_frame_visibility(const float* pts, const int32_t* pt_off, con
             SGA_CHECK_ARG(pt_off_host[i + 1] - pt_off_host[i] <= max_points && fr_off_host[i + 1] - fr_off_host[i] <= max_frames,
                           "sga_frame_visibility: scan %d is larger than max_points %d / max_frames %d", i, max_points, max_frames);
     const long p_tiles = ((long)max_points + VIS_PTILE - 1) / VIS_PTILE, f_groups = ((long)max_frames + VIS_FG - 1) / VIS_FG;
-    SGA_CHECK_ARG(p_tiles * f_groups * n_scans < (1L << 31), "sga_frame_visibility: %ld x %ld x %d workgroups exceed the grid limit; split the scan list",
-                  p_tiles, f_groups, n_scans);
+    if (int rc = sga_check_grid("sga_frame_visibility", p_tiles, f_groups, n_scans, "split the scan list")) return rc;
     hipLaunchKernelGGL(vis_kernel, dim3((unsigned)(p_tiles * f_groups * n_scans)), dim3(VIS_THREADS), 0, static_cast<hipStream_t>(stream), pts, pt_off,
                        w2c, fr_off, intr, reinterpret_cast<const long long*>(vis_off), n_scans, total_points, total_frames, (long long)total_words,
                        (int)p_tiles, (int)f_groups, reinterpret_cast<u64*>(vis));
@@ -271,9 +265,7 @@ extern "C" int sga_subscan_walk(const uint64_t* vis, uint64_t* cum, const int32_
     SGA_CHECK_ARG(pt_off && fr_off && vis_off && max_pts && n_seg, "sga_subscan_walk: null pointer");
     SGA_CHECK_ARG((vis && cum) || total_words == 0, "sga_subscan_walk: null bit matrix");
     SGA_CHECK_ARG((seg_end && seg_count && frame_count) || total_frames == 0, "sga_subscan_walk: null output");
-    SGA_CHECK_ARG(((uintptr_t)vis % 8) == 0 && ((uintptr_t)cum % 8) == 0 && ((uintptr_t)vis_off % 8) == 0 && ((uintptr_t)pt_off % 4) == 0 &&
-                  ((uintptr_t)fr_off % 4) == 0 && ((uintptr_t)max_pts % 4) == 0 && ((uintptr_t)seg_end % 4) == 0 && ((uintptr_t)seg_count % 4) == 0 &&
-                  ((uintptr_t)frame_count % 4) == 0 && ((uintptr_t)n_seg % 4) == 0,
+    SGA_CHECK_ARG(sga_aligned(8, vis, cum, vis_off) && sga_aligned(4, pt_off, fr_off, max_pts, seg_end, seg_count, frame_count, n_seg),
                   "sga_subscan_walk: misaligned pointer (64-bit arrays need 8 bytes, 32-bit arrays 4)");
     if (int rc = vis_check_host("sga_subscan_walk", n_scans, total_points, total_frames, total_words, pt_off_host, fr_off_host, vis_off_host)) return rc;
     hipLaunchKernelGGL(walk_kernel, dim3((unsigned)n_scans), dim3(WALK_THREADS), 0, static_cast<hipStream_t>(stream), reinterpret_cast<const u64*>(vis),
@@ -295,8 +287,7 @@ extern "C" int sga_subscan_object_counts(const uint64_t* bits, const int32_t* pt
     const bool empty = max_points == 0 || total_words == 0;                                                  // empty scans only: all counts are 0
     SGA_CHECK_ARG(counts && (empty || (bits && pt_off && fr_off && vis_off && rows && slot)), "sga_subscan_object_counts: null pointer");
     SGA_CHECK_ARG((long)n_rows * n_slots < (1L << 31), "sga_subscan_object_counts: %d rows x %d slots exceed 2^31 counters", n_rows, n_slots);
-    SGA_CHECK_ARG(((uintptr_t)bits % 8) == 0 && ((uintptr_t)vis_off % 8) == 0 && ((uintptr_t)pt_off % 4) == 0 && ((uintptr_t)fr_off % 4) == 0 &&
-                  ((uintptr_t)rows % 4) == 0 && ((uintptr_t)slot % 4) == 0 && ((uintptr_t)counts % 4) == 0,
+    SGA_CHECK_ARG(sga_aligned(8, bits, vis_off) && sga_aligned(4, pt_off, fr_off, rows, slot, counts),
                   "sga_subscan_object_counts: misaligned pointer (64-bit arrays need 8 bytes, 32-bit arrays 4)");
     if (int rc = vis_check_host("sga_subscan_object_counts", n_scans, total_points, total_frames, total_words, pt_off_host, fr_off_host, vis_off_host))
         return rc;
@@ -311,11 +302,8 @@ extern "C" int sga_subscan_object_counts(const uint64_t* bits, const int32_t* pt
         }
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long p_tiles = ((long)max_points + OC_TILE - 1) / OC_TILE;
-    SGA_CHECK_ARG(p_tiles * n_rows < (1L << 31), "sga_subscan_object_counts: %ld x %d workgroups exceed the grid limit; split the row list", p_tiles, n_rows);
-    if (hipMemsetAsync(counts, 0, (size_t)n_rows * n_slots * sizeof(int32_t), st) != hipSuccess) {
-        sga_set_error("sga_subscan_object_counts: memset failed");
-        return SGA_ERR_HIP;
-    }
+    if (int rc = sga_check_grid("sga_subscan_object_counts", p_tiles, 1, n_rows, "split the row list")) return rc;
+    if (int rc = sga_zero("sga_subscan_object_counts", counts, (size_t)n_rows * n_slots * sizeof(int32_t), st)) return rc;
     if (empty) return SGA_OK;
     hipLaunchKernelGGL(objcount_kernel, dim3((unsigned)(p_tiles * n_rows)), dim3(OC_THREADS), 0, st, reinterpret_cast<const u64*>(bits), pt_off, fr_off,
                        reinterpret_cast<const long long*>(vis_off), n_scans, total_points, total_frames, (long long)total_words, rows, slot, n_slots,

@@ -33,8 +33,8 @@ import torch
 
 from .. import _lib
 from ..ops import _p, _stream
+from ..packed import PackedLayout, check_dtype, device_tensor, upload
 from ..utils import point_cloud as PC
-from .subscans import _aligned
 
 
 def graph_max_nodes() -> int:
@@ -52,48 +52,33 @@ def partition_max_slots() -> int:
     return int(_lib.lib().sga_scenegraph_lds_slots())
 
 
-def _offsets(a, name: str, total=None) -> np.ndarray:
-    off = np.ascontiguousarray(a.cpu() if isinstance(a, torch.Tensor) else a, dtype=np.int64).reshape(-1)
-    if len(off) < 1 or off[0] != 0 or (np.diff(off) < 0).any() or (total is not None and off[-1] != total):
-        raise ValueError(f'{name} must be a monotone prefix array starting at 0' + (f' and covering all {total} entries' if total is not None else ''))
-    if off[-1] >= 2 ** 31:
-        raise ValueError(f'{name} is indexed with int32: fewer than 2^31 entries per call')
-    return off
-
-
-class SlotLayout:
-    """Point and slot offsets of a list of scans packed back to back, on the host and (int32) on the device.  `meta`, when given, is an int32
-    device tensor that already holds host_meta() (a caller can fold the offsets into a larger upload)."""
+class SlotLayout(PackedLayout):
+    """Point and slot offsets of a list of scans: pt_off / slot_off [S + 1] (h_pt / h_slot int32 on the host, d_pt / d_slot on the device)."""
 
     def __init__(self, pt_off, slot_off, device=None, meta=None):
-        self.pt_off, self.slot_off = _offsets(pt_off, 'pt_off'), _offsets(slot_off, 'slot_off')
-        self.n_scans = len(self.pt_off) - 1
-        if len(self.slot_off) != self.n_scans + 1:
-            raise ValueError(f'pt_off names {self.n_scans} scans, slot_off {len(self.slot_off) - 1}')
-        self.total_points, self.total_slots = int(self.pt_off[-1]), int(self.slot_off[-1])
-        self.max_points = int(np.diff(self.pt_off).max()) if self.n_scans else 0
-        self.max_slots = int(np.diff(self.slot_off).max()) if self.n_scans else 0
-        self.h_pt, self.h_slot = self.pt_off.astype(np.int32), self.slot_off.astype(np.int32)
-        if meta is None and device is not None:
-            meta = torch.from_numpy(self.host_meta()).to(device)                      # one small upload
-        if meta is not None:
-            n = self.n_scans + 1
-            self.d_pt, self.d_slot = meta[:n], meta[n:2 * n]
+        super().__init__(pt_off)
+        self.slot_off, self.h_slot, self.total_slots, self.max_slots = self._second(slot_off, 'slot_off')
+        views = self._device_views(device, meta)
+        if views:
+            self.d_pt, self.d_slot = views
 
-    def host_meta(self) -> np.ndarray:
-        return np.concatenate([self.h_pt, self.h_slot])
+    def host_parts(self):
+        return [self.h_pt, self.h_slot]
+
+    def host_args(self):
+        return self.h_pt.ctypes.data, self.h_slot.ctypes.data
 
 
 def object_counts_batch(slot, layout: SlotLayout):
     """sga_object_counts: slot [sum N] int32 device tensor (each point's dense object slot within its scan; a value outside the scan's slot
     range, e.g. -1, belongs to no object).  Returns counts [sum slots] int32 device tensor.  Exact: integer atomics."""
-    sl = PC._device_tensor(slot, 'slot', torch.int32)
+    sl = device_tensor(slot, 'slot', torch.int32)
     if tuple(sl.shape) != (layout.total_points,):
         raise ValueError(f'slot must be [{layout.total_points}], got {tuple(sl.shape)}')
     counts = torch.empty((layout.total_slots,), device=sl.device, dtype=torch.int32)
     if layout.n_scans and layout.total_slots:
         rc = _lib.lib().sga_object_counts(_p(sl), _p(layout.d_pt), _p(layout.d_slot), layout.n_scans, layout.total_points, layout.total_slots,
-                                          layout.max_points, layout.h_pt.ctypes.data, layout.h_slot.ctypes.data, _p(counts), _stream())
+                                          layout.max_points, *layout.host_args(), _p(counts), _stream())
         _lib.check(rc, 'sga_object_counts')
     return counts
 
@@ -104,8 +89,7 @@ def object_partition_batch(points, slot, layout: SlotLayout, dest_off, counts):
     Returns (perm [n_kept] int32, pts_out [n_kept, 3] float32) device tensors, n_kept = the kept slots' points:
     perm[dest_off[k] : dest_off[k] + counts[k]] == np.flatnonzero(slot_s == k), scan-local, ascending.  A pure function of the input."""
     for t, name, dt in ((points, 'points', torch.float32), (slot, 'slot', torch.int32)):
-        if isinstance(t, torch.Tensor) and t.dtype != dt:
-            raise RuntimeError(f'sgaligner_amd: `{name}` must be {dt} (got {t.dtype})')
+        check_dtype(t, name, dt)
     h_dest = np.ascontiguousarray(dest_off, dtype=np.int64).reshape(-1)
     h_cnt = np.ascontiguousarray(counts.cpu() if isinstance(counts, torch.Tensor) else counts, dtype=np.int64).reshape(-1)
     if len(h_dest) != layout.total_slots or len(h_cnt) != layout.total_slots:
@@ -122,8 +106,8 @@ def object_partition_batch(points, slot, layout: SlotLayout, dest_off, counts):
         lo, hi = h_dest[full][order], (h_dest[full] + h_cnt[full])[order]
         if hi.max() > n_kept or (lo[1:] < hi[:-1]).any():
             raise ValueError('dest_off must give the kept objects disjoint ranges that tile [0, kept points)')
-    pts = PC._device_tensor(points, 'points', torch.float32)
-    sl = PC._device_tensor(slot, 'slot', torch.int32)
+    pts = device_tensor(points, 'points', torch.float32)
+    sl = device_tensor(slot, 'slot', torch.int32)
     if tuple(pts.shape) != (layout.total_points, 3) or tuple(sl.shape) != (layout.total_points,):
         raise ValueError(f'points / slot must be [{layout.total_points}, 3] / [{layout.total_points}], got {tuple(pts.shape)} / {tuple(sl.shape)}')
     perm = torch.empty((n_kept,), device=pts.device, dtype=torch.int32)
@@ -135,8 +119,8 @@ def object_partition_batch(points, slot, layout: SlotLayout, dest_off, counts):
         ws_bytes = int(L.sga_object_partition_ws_bytes(layout.n_scans, layout.max_points, layout.max_slots))
         ws = torch.empty((max((ws_bytes + 3) // 4, 1),), device=pts.device, dtype=torch.int32)
         rc = L.sga_object_partition(_p(pts), _p(sl), _p(layout.d_pt), _p(layout.d_slot), _p(d_dest), layout.n_scans, layout.total_points,
-                                    layout.total_slots, layout.max_points, layout.max_slots, n_kept, layout.h_pt.ctypes.data, layout.h_slot.ctypes.data,
-                                    h_dest32.ctypes.data, h_cnt32.ctypes.data, _p(perm), _p(out), _p(ws), ws_bytes, _stream())
+                                    layout.total_slots, layout.max_points, layout.max_slots, n_kept, *layout.host_args(), h_dest32.ctypes.data,
+                                    h_cnt32.ctypes.data, _p(perm), _p(out), _p(ws), ws_bytes, _stream())
         _lib.check(rc, 'sga_object_partition')
     return perm, out
 
@@ -180,14 +164,11 @@ def graph_complete_batch(n_nodes, pairs, rels, none_id: int, vocab: int, device=
     h_off = np.concatenate([node_off, pair_off, trip_off, edge_off]).astype(np.int32)
     h_pr = (np.concatenate(h_pairs) if G else np.zeros((0, 2))).astype(np.int32).reshape(-1)
     h_rl = np.concatenate(h_rels).astype(np.int32)
-    buf, spans = _aligned([h_off, h_pr, h_rl])
-    d_buf = torch.from_numpy(buf).to(device)                                           # the one upload
-    view = lambda i: d_buf[spans[i][0]:spans[i][0] + spans[i][1]].view(torch.int32)
-    d_off, d_pr, d_rl = view(0), view(1), view(2)
+    d_off, d_pr, d_rl = upload([h_off, h_pr, h_rl], device)                            # the one upload
     n = G + 1
     te, tn = int(edge_off[-1]), int(node_off[-1])
     # one output buffer, one download: edges (int64) | bow | n_edges (int32)
-    out = torch.empty((te * 2 + (tn * vocab + G + 1) // 2 + 1,), device=d_buf.device, dtype=torch.int64)
+    out = torch.empty((te * 2 + (tn * vocab + G + 1) // 2 + 1,), device=d_off.device, dtype=torch.int64)
     d_edges = out[:te * 2]
     tail = out[te * 2:].view(torch.int32)
     d_bow, d_ne = tail[:tn * vocab], tail[tn * vocab:tn * vocab + G]
@@ -318,11 +299,9 @@ def process_scans(scans, rel2idx, pc_resolutions=(512,), min_obj_points=50, retu
 
     # 1. one packed upload
     L = SlotLayout(np.concatenate([[0], np.cumsum([len(s[2]) for s in live])]), np.concatenate([[0], np.cumsum([len(s[4]) for s in live])]))
-    buf, spans = _aligned([L.host_meta(), np.concatenate([s[3] for s in live]), np.concatenate([s[2] for s in live]).reshape(-1)])
-    d_buf = torch.from_numpy(buf).cuda()
-    view = lambda k, dt: d_buf[spans[k][0]:spans[k][0] + spans[k][1]].view(dt)
-    L = SlotLayout(L.pt_off, L.slot_off, meta=view(0, torch.int32))
-    d_slot, d_pts = view(1, torch.int32), view(2, torch.float32).view(-1, 3)
+    d_meta, d_slot, d_pts = upload([L.host_meta(), np.concatenate([s[3] for s in live]), np.concatenate([s[2] for s in live])], 'cuda')
+    L = SlotLayout(L.pt_off, L.slot_off, meta=d_meta)
+    d_pts = d_pts.view(-1, 3)
     # 2. counts
     counts = object_counts_batch(d_slot, L).cpu().numpy().astype(np.int64)
 

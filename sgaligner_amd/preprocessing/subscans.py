@@ -15,6 +15,7 @@ import torch
 
 from .. import _lib
 from ..ops import _p, _stream
+from ..packed import device_tensor, upload
 from ..utils import point_cloud as PC
 
 # dtype of a subscan's `pcl` entry (the reference's utils/scan3r.py:143-144)
@@ -39,7 +40,7 @@ def subscan_walk_batch(vis, layout: PC.ScanLayout, max_pts, in_place: bool = Tru
     int32 device tensor [3 * total_frames + S] = seg_end | seg_count | frame_count (each [total_frames], scan s's entries from fr_off[s],
     seg_end scan-local) | n_seg [S] -- split_walk_output() slices it.  Entries past n_seg[s] are unspecified."""
     vis = PC._bit_matrix(vis, 'vis', layout.total_words)
-    mp = PC._device_tensor(max_pts, 'max_pts', torch.int32)
+    mp = device_tensor(max_pts, 'max_pts', torch.int32)
     if tuple(mp.shape) != (layout.n_scans,):
         raise ValueError(f'max_pts must be [{layout.n_scans}], got {tuple(mp.shape)}')
     cum = vis if in_place else torch.empty_like(vis)
@@ -71,7 +72,7 @@ def object_counts_batch(bits, layout: PC.ScanLayout, rows, slot, n_slots: int):
     object slot of every point, np.unique(objectId, return_inverse=True)[1]).  Returns counts [n_rows, n_slots] int32 device tensor: the number
     of set bits of each row per slot.  Exact: integer atomics."""
     bits = PC._bit_matrix(bits, 'bits', layout.total_words)
-    sl = PC._device_tensor(slot, 'slot', torch.int32)
+    sl = device_tensor(slot, 'slot', torch.int32)
     if tuple(sl.shape) != (layout.total_points,):
         raise ValueError(f'slot must be [{layout.total_points}], got {tuple(sl.shape)}')
     h_rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 2)
@@ -89,18 +90,6 @@ def object_counts_batch(bits, layout: PC.ScanLayout, rows, slot, n_slots: int):
                                                   *layout.host_args(), h_rows.ctypes.data, _p(counts), _stream())
         _lib.check(rc, 'sga_subscan_object_counts')
     return counts
-
-
-def _aligned(parts):
-    """Concatenate host arrays into one byte buffer, every part starting at a multiple of 8 bytes.  -> (buffer uint8, [(offset, nbytes)])."""
-    spans, pos = [], 0
-    for a in parts:
-        spans.append((pos, a.nbytes))
-        pos += (a.nbytes + 7) // 8 * 8
-    buf = np.zeros(max(pos, 8), dtype=np.uint8)
-    for a, (o, n) in zip(parts, spans):
-        buf[o:o + n] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-    return buf, spans
 
 
 def _run(scans, max_pts, slots=None, n_slots=0):
@@ -129,20 +118,17 @@ def _run(scans, max_pts, slots=None, n_slots=0):
     parts = [np.concatenate(w2c).reshape(-1), np.stack(intr).reshape(-1), L.host_meta(), max_pts.astype(np.int32), np.concatenate(pts).reshape(-1)]
     if slots is not None:
         parts.append(np.ascontiguousarray(slots, dtype=np.int32))
-    buf, spans = _aligned(parts)
-    d_buf = torch.from_numpy(buf).cuda()                                               # the one upload
-    view = lambda i, dt: d_buf[spans[i][0]:spans[i][0] + spans[i][1]].view(dt)
-    d_w2c, d_intr, d_pts = view(0, torch.float64).view(-1, 12), view(1, torch.float64).view(-1, 6), view(4, torch.float32).view(-1, 3)
-    L = PC.ScanLayout(pt_off, fr_off, L.total_points, L.total_frames, meta=view(2, torch.int32))
-    vis, _ = PC.visible_masks_batch(d_pts, None, d_w2c, None, d_intr, layout=L)
-    cum, walk = subscan_walk_batch(vis, L, view(3, torch.int32), in_place=True)
+    d_w2c, d_intr, d_meta, d_max, d_pts, *d_slot = upload(parts, 'cuda')               # the one upload
+    L = PC.ScanLayout(pt_off, fr_off, L.total_points, L.total_frames, meta=d_meta)
+    vis, _ = PC.visible_masks_batch(d_pts.view(-1, 3), None, d_w2c.view(-1, 12), None, d_intr.view(-1, 6), layout=L)
+    cum, walk = subscan_walk_batch(vis, L, d_max, in_place=True)
     segs = split_walk_output(walk.cpu().numpy(), L)                                    # small: 3 ints per frame; decides which rows are subscans
     rows = [(s, int(f)) for s in range(n_scans) for f in segs[s][0]]
     pieces = [cum[int(L.vis_off[s]) + f * int(L.words[s]):int(L.vis_off[s]) + (f + 1) * int(L.words[s])] for s, f in rows]
     n_words = sum(int(p.numel()) for p in pieces)
     counts = None
     if slots is not None and rows:
-        counts = object_counts_batch(cum, L, rows, view(5, torch.int32), n_slots)
+        counts = object_counts_batch(cum, L, rows, d_slot[0], n_slots)
         flat = counts.reshape(-1)
         if flat.numel() % 2:
             flat = torch.cat([flat, flat.new_zeros(1)])

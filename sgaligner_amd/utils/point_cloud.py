@@ -19,6 +19,7 @@ import torch
 
 from .. import _lib
 from ..ops import _p, _stream
+from ..packed import PackedLayout, check_dtype, device_tensor, prefix_offsets, upload
 
 SMALL_MAX, MID_MAX = 2048, 8192          # register-resident kernel variants (8 / 32 points per lane)
 
@@ -26,16 +27,12 @@ SMALL_MAX, MID_MAX = 2048, 8192          # register-resident kernel variants (8 
 def farthest_point_sample_batch(points, offsets, npoint: int, start) -> torch.Tensor:
     """points [sum N, 3] float32 CUDA tensor (objects packed back to back), offsets [n_obj+1] (host ints or tensor),
     start [n_obj] first sample per object.  Returns idx [n_obj, npoint] int32 (object-local), on the GPU."""
-    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32):
-        raise RuntimeError('farthest_point_sample_batch: points must be a float32 CUDA tensor (no CPU fallback)')
-    pts = points.contiguous()
+    pts = device_tensor(points, 'points', torch.float32)
     if pts.dim() != 2 or pts.shape[1] != 3:
         raise ValueError(f'points must be [N,3], got {tuple(pts.shape)}')
-    off = np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets, dtype=np.int64)
+    off = prefix_offsets(offsets, 'offsets', pts.shape[0])
     n_obj = len(off) - 1
     sizes = np.diff(off)
-    if n_obj < 0 or off[0] != 0 or off[-1] != pts.shape[0] or (sizes < 0).any():
-        raise ValueError('offsets must be a monotone prefix array covering all points')
     if (sizes < npoint).any():
         raise ValueError('every object needs N >= npoint (the N < npoint branch is a host-side random draw)')
     st = np.asarray(start.cpu() if isinstance(start, torch.Tensor) else start, dtype=np.int64)
@@ -75,13 +72,9 @@ def pcl_farthest_sample(point, npoint, return_idxs=False):
 def hull_candidate_mask_batch(points, offsets):
     """points [sum N, 3] float32 CUDA tensor (objects packed back to back), offsets [n_obj+1] host ints.  Returns
     (keep [sum N] bool CUDA tensor, n_planes [n_obj] int32 CUDA tensor): points that can be hull vertices (csrc/hull.hip)."""
-    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32):
-        raise RuntimeError('hull_candidate_mask_batch: points must be a float32 CUDA tensor (no CPU fallback)')
-    pts = points.contiguous()
-    off = np.asarray(offsets, dtype=np.int64)
+    pts = device_tensor(points, 'points', torch.float32)
+    off = prefix_offsets(offsets, 'offsets', pts.shape[0])
     n_obj = len(off) - 1
-    if n_obj < 0 or off[0] != 0 or off[-1] != pts.shape[0] or (np.diff(off) < 0).any():
-        raise ValueError('offsets must be a monotone prefix array covering all points')
     d_off = torch.from_numpy(off.astype(np.int32)).to(pts.device)
     keep = torch.empty((max(int(pts.shape[0]), 1),), device=pts.device, dtype=torch.uint8)
     npl = torch.zeros((max(n_obj, 1),), device=pts.device, dtype=torch.int32)
@@ -95,13 +88,11 @@ HULL_ON_DEVICE = True          # tests flip it to cross-check the device hull ag
 def hull_vertices_device(cand64, offsets):
     """The device-resident form of hull_vertices_batch: cand64 [sum n, 3] float64 CUDA tensor, offsets [n_obj+1] host ints (n_obj >= 1,
     at least one point).  Returns (is_vertex [sum n] uint8, status [n_obj] int32) CUDA tensors; nothing is downloaded."""
-    if not (isinstance(cand64, torch.Tensor) and cand64.is_cuda and cand64.dtype == torch.float64):
-        raise RuntimeError('hull_vertices_device: cand64 must be a float64 CUDA tensor (no CPU fallback)')
-    off = np.asarray(offsets, dtype=np.int64)
+    d_pts = device_tensor(cand64, 'cand64', torch.float64)
+    off = prefix_offsets(offsets, 'offsets', d_pts.shape[0])
     n_obj = len(off) - 1
-    d_pts = cand64.contiguous()
-    if n_obj <= 0 or off[0] != 0 or off[-1] != d_pts.shape[0] or off[-1] == 0 or (np.diff(off) < 0).any():
-        raise ValueError('offsets must be a monotone prefix array covering all points of at least one object')
+    if n_obj <= 0 or off[-1] == 0:
+        raise ValueError('offsets must cover the points of at least one object')
     d_off = torch.from_numpy(off.astype(np.int32)).to(d_pts.device)
     isv = torch.zeros((int(off[-1]),), device=d_pts.device, dtype=torch.uint8)
     status = torch.full((n_obj,), -1, device=d_pts.device, dtype=torch.int32)
@@ -185,15 +176,11 @@ def convex_hull_barycenters_device(points, offsets, return_info=False):
     the points are never uploaded again.  Downloads: the candidates' indices (their number per object sizes the second launch), then the
     candidates themselves with their vertex flags -- a few per cent of the points.  Objects the device hull declines go to Qhull on the
     downloaded candidates (float32 values, the scan's own)."""
-    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32):
-        raise RuntimeError('convex_hull_barycenters_device: points must be a float32 CUDA tensor (no CPU fallback)')
-    off = np.asarray(offsets, dtype=np.int64)
+    pts = device_tensor(points, 'points', torch.float32)
+    off = prefix_offsets(offsets, 'offsets', pts.shape[0])
     n_obj = len(off) - 1
-    if n_obj < 0 or off[0] != 0 or off[-1] != points.shape[0] or (np.diff(off) < 0).any():
-        raise ValueError('offsets must be a monotone prefix array covering all points')
     if off[-1] == 0:
         return (np.zeros((n_obj, 3)), {'device': 0, 'qhull': 0}) if return_info else np.zeros((n_obj, 3))
-    pts = points.contiguous()
     keep, _ = hull_candidate_mask_batch(pts, off)
     d_idx = torch.nonzero(keep).reshape(-1)
     idx = d_idx.cpu().numpy()                                                  # ascending: the candidates stay packed per object
@@ -240,18 +227,11 @@ def nearest_neighbor_batch(points, offsets, pairs, chunk=None, squared=False):
     [n_pairs+1] int64 numpy): job p's results are dist[out_offsets[p]:out_offsets[p+1]]; idx is support-cloud-local, the LOWEST index among
     exactly equal minima; an empty support gives (+inf, -1).  dist is the correctly rounded sqrt of (dx*dx + dy*dy) + dz*dz (bit-identical
     to cKDTree(s).query(q)[0]); squared=True returns that sum itself."""
-    if not isinstance(points, torch.Tensor) or not points.is_cuda:
-        raise RuntimeError(f'sgaligner_amd: `points` must be a HIP device tensor (got '
-                           f'{points.device if isinstance(points, torch.Tensor) else type(points)}); there is no CPU path')
-    if points.dtype != torch.float64:
-        raise RuntimeError(f'sgaligner_amd: `points` must be torch.float64 (got {points.dtype})')
-    pts = points.contiguous()
+    pts = device_tensor(points, 'points', torch.float64)
     if pts.dim() != 2 or pts.shape[1] != 3:
         raise ValueError(f'points must be [N,3], got {tuple(pts.shape)}')
-    off = np.ascontiguousarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets, dtype=np.int64).reshape(-1)
+    off = prefix_offsets(offsets, 'offsets', pts.shape[0])
     n_clouds = len(off) - 1
-    if n_clouds < 0 or off[0] != 0 or off[-1] != pts.shape[0] or (np.diff(off) < 0).any():
-        raise ValueError('offsets must be a monotone prefix array covering all points')
     pr = np.ascontiguousarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
     if pr.size and (pr.min() < 0 or pr.max() >= n_clouds):
         raise ValueError(f'pairs must name clouds in [0, {n_clouds})')
@@ -259,8 +239,8 @@ def nearest_neighbor_batch(points, offsets, pairs, chunk=None, squared=False):
     nq, ns = sizes[pr[:, 0]], sizes[pr[:, 1]]
     out_off = np.concatenate([[0], np.cumsum(nq)]).astype(np.int64)
     total_q = int(out_off[-1])
-    if pts.shape[0] >= 2 ** 31 or total_q >= 2 ** 31:
-        raise ValueError('nearest_neighbor_batch indexes with int32: fewer than 2^31 points and 2^31 queries per call')
+    if total_q >= 2 ** 31:
+        raise ValueError('nearest_neighbor_batch indexes with int32: fewer than 2^31 queries per call')
     from .. import ops
     if ops.VALIDATE and pts.numel() and not bool(torch.isfinite(pts).all()):
         raise RuntimeError('sgaligner_amd: `points` holds NaN or infinite coordinates')
@@ -274,8 +254,7 @@ def nearest_neighbor_batch(points, offsets, pairs, chunk=None, squared=False):
         raise ValueError(f'chunk must be >= 1, got {chunk}')
     L = _lib.lib()
     h_off, h_pr, h_oo = off.astype(np.int32), np.ascontiguousarray(pr, dtype=np.int32), out_off[:-1].astype(np.int32)
-    meta = torch.from_numpy(np.concatenate([h_off, h_pr.reshape(-1), h_oo])).to(dev)          # one small upload
-    d_off, d_pr, d_oo = meta[:len(h_off)], meta[len(h_off):len(h_off) + h_pr.size], meta[len(h_off) + h_pr.size:]
+    d_off, d_pr, d_oo = upload([h_off, h_pr, h_oo], dev)                                      # one small upload
     ws_bytes = int(L.sga_nn_workspace_bytes(total_q, int(ns.max()), chunk))
     ws = torch.empty((max((ws_bytes + 7) // 8, 1),), device=dev, dtype=torch.float64)
     rc = L.sga_nn_search(_p(pts), _p(d_off), n_clouds, int(pts.shape[0]), _p(d_pr), len(pr), _p(d_oo), total_q, int(nq.max()), int(ns.max()),
@@ -394,56 +373,28 @@ def visibility_offsets(pt_off, fr_off):
     return words, np.concatenate([[0], np.cumsum(np.diff(fr_off) * words)]).astype(np.int64)
 
 
-def _host_offsets(a, name: str, total: int):
-    off = np.ascontiguousarray(a.cpu() if isinstance(a, torch.Tensor) else a, dtype=np.int64).reshape(-1)
-    if len(off) < 1 or off[0] != 0 or off[-1] != total or (np.diff(off) < 0).any():
-        raise ValueError(f'{name} must be a monotone prefix array covering all {total} rows')
-    return off
-
-
-def _device_tensor(t, name: str, dtype):
-    if isinstance(t, torch.Tensor) and t.dtype != dtype:
-        raise RuntimeError(f'sgaligner_amd: `{name}` must be {dtype} (got {t.dtype})')
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f'sgaligner_amd: `{name}` must be a HIP device tensor (got '
-                           f'{t.device if isinstance(t, torch.Tensor) else type(t)}); there is no CPU path')
-    return t.contiguous()
-
-
-class ScanLayout:
-    """Offsets of a list of scans packed back to back, on the host and on the device: pt_off / fr_off [S + 1] (int32 on the device),
-    words per bit-matrix row W [S], vis_off [S + 1] int64.  `meta`, when given, is an int32 device tensor that already holds
-    `host_meta()` (so that a caller can fold the offsets into a larger upload); otherwise the layout uploads it itself."""
+class ScanLayout(PackedLayout):
+    """Point and frame offsets of a list of scans: pt_off / fr_off [S + 1] (h_pt / h_fr int32 on the host, d_pt / d_fr on the device), words
+    per bit-matrix row W [S], vis_off [S + 1] int64 (d_vis on the device, as int32 pairs)."""
 
     def __init__(self, pt_off, fr_off, total_points: int, total_frames: int, device=None, meta=None):
-        self.pt_off, self.fr_off = _host_offsets(pt_off, 'pt_off', total_points), _host_offsets(fr_off, 'fr_off', total_frames)
-        self.n_scans = len(self.pt_off) - 1
-        if len(self.fr_off) != self.n_scans + 1:
-            raise ValueError(f'pt_off names {self.n_scans} scans, fr_off {len(self.fr_off) - 1}')
-        if total_points >= 2 ** 31 or total_frames >= 2 ** 31:
-            raise ValueError('scans are indexed with int32: fewer than 2^31 points and frames per call')
-        self.total_points, self.total_frames = int(total_points), int(total_frames)
+        super().__init__(pt_off, total_points)
+        self.fr_off, self.h_fr, self.total_frames, self.max_frames = self._second(fr_off, 'fr_off', total_frames)
         self.words, self.vis_off = visibility_offsets(self.pt_off, self.fr_off)
         self.total_words = int(self.vis_off[-1])
-        self.max_points = int(np.diff(self.pt_off).max()) if self.n_scans else 0
-        self.max_frames = int(np.diff(self.fr_off).max()) if self.n_scans else 0
-        self.h_pt, self.h_fr = self.pt_off.astype(np.int32), self.fr_off.astype(np.int32)
-        if meta is None and device is not None:
-            meta = torch.from_numpy(self.host_meta()).to(device)                      # one small upload
-        if meta is not None:
-            n = self.n_scans + 1
-            self.d_vis, self.d_pt, self.d_fr = meta[:2 * n], meta[2 * n:3 * n], meta[3 * n:4 * n]
+        views = self._device_views(device, meta)
+        if views:
+            self.d_vis, self.d_pt, self.d_fr = views
 
-    def host_meta(self) -> np.ndarray:
-        """vis_off (int64, viewed as int32 pairs; first, for its alignment) | pt_off | fr_off as one int32 array of 4 (S + 1) entries."""
-        return np.concatenate([self.vis_off.view(np.int32), self.h_pt, self.h_fr])
+    def host_parts(self):
+        return [self.vis_off, self.h_pt, self.h_fr]
 
     def host_args(self):
         return self.h_pt.ctypes.data, self.h_fr.ctypes.data, self.vis_off.ctypes.data
 
 
 def _bit_matrix(t, name: str, total_words: int):
-    t = _device_tensor(t, name, torch.int64)
+    t = device_tensor(t, name, torch.int64)
     if t.dim() != 1 or t.numel() < total_words:
         raise ValueError(f'{name} must be a flat int64 tensor of at least {total_words} words, got {tuple(t.shape)}')
     return t
@@ -456,11 +407,8 @@ def visible_masks_batch(points, pt_off, w2c, fr_off, intr, out=None, layout=None
     scan s's F_s rows of W_s = ceil(N_s / 64) words start at vis_off[s] (int64 numpy, [S + 1]); bit p % 64 of word p / 64 of a row is point
     p, padding bits 0."""
     for t, name, dt in ((points, 'points', torch.float32), (w2c, 'w2c', torch.float64), (intr, 'intr', torch.float64)):
-        if isinstance(t, torch.Tensor) and t.dtype != dt:                     # every dtype before any device: told apart without a device
-            raise RuntimeError(f'sgaligner_amd: `{name}` must be {dt} (got {t.dtype})')
-    pts = _device_tensor(points, 'points', torch.float32)
-    m = _device_tensor(w2c, 'w2c', torch.float64)
-    k = _device_tensor(intr, 'intr', torch.float64)
+        check_dtype(t, name, dt)                                              # every dtype before any device: told apart without a device
+    pts, m, k = device_tensor(points, 'points', torch.float32), device_tensor(w2c, 'w2c', torch.float64), device_tensor(intr, 'intr', torch.float64)
     if pts.dim() != 2 or pts.shape[1] != 3:
         raise ValueError(f'points must be [N, 3], got {tuple(pts.shape)}')
     if m.dim() != 2 or m.shape[1] != 12:

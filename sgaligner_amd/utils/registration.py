@@ -11,6 +11,7 @@ import torch
 
 from .. import _lib
 from ..ops import _p, _stream
+from ..packed import device_tensor, prefix_offsets, upload
 from .point_cloud import _cloud64, _need_device, _nn_numpy, apply_transform, get_nearest_neighbor
 
 
@@ -108,13 +109,6 @@ def _ransac_chunk(sizes_n, sizes_h) -> int:
     return max(RANSAC_MIN_CHUNK, -(-n_max // n_chunks))
 
 
-def _prefix(a, name, total):
-    off = np.ascontiguousarray(a.cpu() if isinstance(a, torch.Tensor) else a, dtype=np.int64).reshape(-1)
-    if len(off) < 1 or off[0] != 0 or off[-1] != total or (np.diff(off) < 0).any():
-        raise ValueError(f'{name} must be a monotone prefix array from 0 to {total}')
-    return off
-
-
 def find_rigid_transform_batch(corr, offsets, samples, hyp_offsets, threshold, refine_rounds=2, chunk=None):
     """corr [sum n, 6] float64 HIP tensor (jobs packed back to back; a row = source xyz | reference xyz), offsets [n_jobs+1] host ints,
     samples [sum H, 3] int32 HIP tensor of job-local row indices, hyp_offsets [n_jobs+1] host ints.  One launch set for all jobs, no shift,
@@ -122,19 +116,14 @@ def find_rigid_transform_batch(corr, offsets, samples, hyp_offsets, threshold, r
     (column-vector convention: apply_transform(src, T) ~ ref), inlier_count / best_hyp / status [n_jobs] int32 (status 1 = no model: identity,
     count 0, best_hyp -1), inlier_mask [sum n] uint8, hyp_count [sum H] int32 (the inlier count of every hypothesis).  refine_rounds = -1
     stops after the scoring: only hyp_count is meaningful then (score_hypotheses_batch)."""
-    if not isinstance(corr, torch.Tensor) or not corr.is_cuda:
-        raise RuntimeError(f'sgaligner_amd: `corr` must be a HIP device tensor (got '
-                           f'{corr.device if isinstance(corr, torch.Tensor) else type(corr)}); there is no CPU path')
-    if corr.dtype != torch.float64:
-        raise RuntimeError(f'sgaligner_amd: `corr` must be torch.float64 (got {corr.dtype})')
-    cr = corr.contiguous()
+    cr = device_tensor(corr, 'corr', torch.float64)
     if cr.dim() != 2 or cr.shape[1] != 6:
         raise ValueError(f'corr must be [N,6], got {tuple(cr.shape)}')
     dev = cr.device
     sm = samples if isinstance(samples, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(samples, dtype=np.int32))
     sm = sm.to(device=dev, dtype=torch.int32).contiguous().reshape(-1, 3)
-    off = _prefix(offsets, 'offsets', int(cr.shape[0]))
-    hoff = _prefix(hyp_offsets, 'hyp_offsets', int(sm.shape[0]))
+    off = prefix_offsets(offsets, 'offsets', int(cr.shape[0]))
+    hoff = prefix_offsets(hyp_offsets, 'hyp_offsets', int(sm.shape[0]))
     n_jobs = len(off) - 1
     if len(hoff) != n_jobs + 1:
         raise ValueError(f'offsets names {n_jobs} jobs, hyp_offsets {len(hoff) - 1}')
@@ -163,8 +152,7 @@ def find_rigid_transform_batch(corr, offsets, samples, hyp_offsets, threshold, r
         raise ValueError(f'chunk must be >= 1, got {chunk}')
     L = _lib.lib()
     h_off, h_hoff = off.astype(np.int32), hoff.astype(np.int32)
-    meta = torch.from_numpy(np.concatenate([h_off, h_hoff])).to(dev)          # one small upload
-    d_off, d_hoff = meta[:n_jobs + 1], meta[n_jobs + 1:]
+    d_off, d_hoff = upload([h_off, h_hoff], dev)                              # one small upload
     max_n, max_h = int(sizes_n.max()), int(sizes_h.max())
     ws_bytes = int(L.sga_ransac_workspace_bytes(n_jobs, total_h, max_n, chunk))
     ws = torch.empty((max((ws_bytes + 7) // 8, 1),), device=dev, dtype=torch.float64)

@@ -100,6 +100,11 @@ def test_abi_has_the_entry_points_and_refuses_bad_arguments_without_a_device():
     counts = i32(10, 20, 70, 25, 5)
     assert part(i32(0, 131, 130), so, i32(0, 10, -1, 30, 55), counts) != 0 and b'pt_off decreases at scan 1' in err()
     assert part(pt, i32(0, 4, 3), i32(0, 10, -1, 30, 55), counts) != 0 and b'slot_off' in err()
+    # wrong in both arrays: both ends are checked before either array's order, and the orders scan by scan
+    assert part(i32(0, 131, 130), i32(0, 3, 4), i32(0, 10, -1, 30, 55), counts) != 0 and b'slot_off must run from 0 to total_slots' in err()
+    assert part(i32(0, 131, 130), i32(1, 0, 5), i32(0, 10, -1, 30, 55), counts) != 0 and b'slot_off must run' in err()
+    assert part(i32(0, 131, 130), i32(0, 6, 5), i32(0, 10, -1, 30, 55), counts) != 0 and b'pt_off decreases at scan 1' in err()
+    assert part(i32(0, 100, 130), i32(0, 6, 5), i32(0, 10, -1, 30, 55), counts) != 0 and b'slot_off decreases at scan 1' in err()
     assert part(pt, so, i32(0, 5, -1, 30, 55), counts) != 0 and b'dest_off ranges overlap at output position 5' in err()
     assert part(pt, so, i32(0, 10, -1, 30, 56), counts) != 0 and b'slot 4 writes [56, 61) of 60 kept points' in err()
     assert part(pt, so, i32(0, 10, -1, 30, 55), counts, ms=2) != 0 and b'larger than max_points 100 / max_slots 2' in err()

@@ -83,6 +83,28 @@ def test_partition_all_sizes_as_one_batch_with_an_empty_scan():
     _run_partition(scans)
 
 
+def test_object_counts_at_and_above_the_lds_bound():
+    """One call, two scans: lds_slots slots (the LDS histogram at its bound) and lds_slots + 1 slots (global atomics; the partition refuses
+    such a scan, so only object_counts_batch reaches this branch) over two full tiles and a one-point tile.  Exact against np.bincount."""
+    from sgaligner_amd.preprocessing import scene_graphs as G
+    lds, tile = G.partition_max_slots(), G.partition_tile()
+    rng = np.random.default_rng(24)
+    slots, want = [], []
+    for n, ns in ((2 * tile - 3, lds), (2 * tile + 1, lds + 1)):
+        slot = rng.integers(0, ns, n)
+        slot[slot == 5] = 6                                  # slot 5 is empty
+        slot[::3] = rng.integers(ns - 40, ns, len(slot[::3]))        # a crowded top of the table, its last slot included
+        slot[rng.random(n) < 0.1] = -1                       # points of no object
+        slot[rng.random(n) < 0.1] = ns                       # the first value past the scan's table
+        inside = slot[(slot >= 0) & (slot < ns)]
+        slots.append(slot)
+        want.append(np.bincount(inside, minlength=ns))
+        assert (slot == -1).any() and (slot == ns).any() and want[-1][5] == 0 and want[-1][ns - 1] > 0 and want[-1].max() > 1
+    L = G.SlotLayout([0, len(slots[0]), len(slots[0]) + len(slots[1])], [0, lds, 2 * lds + 1], device='cuda')
+    got = G.object_counts_batch(torch.from_numpy(np.concatenate(slots).astype(np.int32)).cuda(), L).cpu().numpy()
+    assert got.dtype == np.int32 and np.array_equal(got, np.concatenate(want))
+
+
 # ---- completion --------------------------------------------------------------------------------------------------------------------------
 def _graphs():
     """(N, listed pairs, listed triples' relation ids) for every N of interest and every kind of listed set."""
