@@ -13,6 +13,13 @@ def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
+def _oracle_at(O, x, ws, am):
+    """The oracle's post-ReLU value of channel c at point am[t,c] of object t: x [T,P,3], am [T,C3] -> [T,C3] (every point as an object of its own)."""
+    T, P, _ = x.shape
+    per_point = O.pointnet_feat(x.reshape(T * P, 3, 1), *ws).reshape(T, P, -1)
+    return torch.gather(per_point, 1, am.long()[:, None, :])[:, 0, :]
+
+
 @pytest.mark.parametrize('tag', ['small', 'ragged'])
 def test_pointnet_fwd_golden(tag):
     from sgaligner_amd import ops
@@ -47,6 +54,8 @@ def test_pointnet_fwd_oracle(T, P):
     assert am.min() >= 0 and am.max() < P
     agree = (am == io) | (yo <= 0)
     assert agree.float().mean() > 0.999
+    # ... and EVERY returned index is a maximiser up to the bound y itself is held to
+    assert (_oracle_at(O, x, ws, am) - yo).abs().max() < 2e-5
 
 
 @pytest.mark.parametrize('mode', ['bf16x6', 'f32'])
@@ -76,6 +85,8 @@ def test_pointnet_fwd_out_sizes_and_modes_vs_oracle(mode, C3, T, P):
     assert (y.cpu().double() - yo).abs().max() < 2e-5
     agree = (am.cpu().long() == io) | (yo <= 0)
     assert agree.float().mean() > 0.999
+    assert am.min() >= 0 and am.max() < P
+    assert (_oracle_at(O, x.double(), [w.double() for w in ws], am.cpu()) - yo).abs().max() < 2e-5      # every index a maximiser within y's own bound
     n = T * P
     s = sums.cpu()
     mean2, var2 = s[9:137] / n, (s[137:265] / n - (s[9:137] / n) ** 2) * n / (n - 1)
@@ -87,15 +98,21 @@ def test_pointnet_fwd_out_sizes_and_modes_vs_oracle(mode, C3, T, P):
     assert (m - x.double().reshape(-1, 3).mean(0)).abs().max() < 1e-9
 
 
+@pytest.mark.parametrize('mode', ['bf16x6', 'f32'])
 @pytest.mark.parametrize('tag', ['small', 'ragged'])
-def test_pointnet_bwd_golden(tag):
+def test_pointnet_bwd_golden(tag, mode):
+    """Both backward kernels (three bf16 planes: the default; fp32 MFMA) against the reference's golden gradients."""
     from sgaligner_amd import ops
     g = load_golden('pointnet_' + tag)
     x = _dev(g['x'].transpose(0, 2, 1))
     w = [_dev(g[k]).requires_grad_(True) for k in ('w1', 'b1', 'w2', 'b2', 'w3', 'b3')]
-    y = ops.pointnet(x, *w)
-    (y * _dev(g['cot'])).sum().backward()
-    torch.cuda.synchronize()
+    old = ops.set_mfma_mode(mode)
+    try:
+        y = ops.pointnet(x, *w)
+        (y * _dev(g['cot'])).sum().backward()
+        torch.cuda.synchronize()
+    finally:
+        ops.set_mfma_mode(old)
     assert np.abs(y.detach().cpu().numpy() - g['y']).max() < 2e-5
     for t, k in zip(w, ('gw1', 'gb1', 'gw2', 'gb2', 'gw3', 'gb3')):
         ref = g[k]
@@ -103,8 +120,9 @@ def test_pointnet_bwd_golden(tag):
         assert err < 1e-4 * max(1.0, np.abs(ref).max()), (k, err, np.abs(ref).max())
 
 
+@pytest.mark.parametrize('mode', ['bf16x6', 'f32'])
 @pytest.mark.parametrize('T,P', [(1, 5), (300, 64), (40, 512), (1000, 33)])
-def test_pointnet_bwd_oracle(T, P):
+def test_pointnet_bwd_oracle(T, P, mode):
     from oracle import sga_oracle as O
     from sgaligner_amd import ops
     torch.manual_seed(T + P)
@@ -118,9 +136,13 @@ def test_pointnet_bwd_oracle(T, P):
     yo = O.pointnet_feat(x.double().permute(0, 2, 1), *wr)
     (yo * cot.double()).sum().backward()
     wd = [w.clone().contiguous().cuda().requires_grad_(True) for w in ws]
-    y = ops.pointnet(x.cuda(), *wd)
-    (y * cot.cuda()).sum().backward()
-    torch.cuda.synchronize()
+    old = ops.set_mfma_mode(mode)
+    try:
+        y = ops.pointnet(x.cuda(), *wd)
+        (y * cot.cuda()).sum().backward()
+        torch.cuda.synchronize()
+    finally:
+        ops.set_mfma_mode(old)
     for a, b, name in zip(wd, wr, ('w1', 'b1', 'w2', 'b2', 'w3', 'b3')):
         ref = b.grad
         err = (a.grad.cpu().double() - ref).abs().max().item()
