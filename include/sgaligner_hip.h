@@ -119,6 +119,12 @@ int sga_fusion_fwd(const float* const* embs, int M, const float* weight, float* 
 size_t sga_fusion_bwd_workspace_bytes(int M);
 int sga_fusion_bwd(const float* const* embs, int M, const float* weight, const float* gjoint, float* const* gembs,
                    float* gweight, int T, int D, void* workspace, size_t workspace_bytes, void* stream);
+/* The same for tables of DIFFERENT widths (the EVA baseline's 400 / 200 / 100 / 100 columns, src/aligner/eva.py:88-94): widths is a HOST
+ * array of M column counts (each >= 1), embs[m] is [T, widths[m]], joint [T, sum widths] holds table m at column offset sum(widths[:m]).
+ * Same arithmetic per table and row, same workspace (sga_fusion_bwd_workspace_bytes). */
+int sga_fusion_var_fwd(const float* const* embs, int M, const int32_t* widths, const float* weight, float* joint, int T, void* stream);
+int sga_fusion_var_bwd(const float* const* embs, int M, const int32_t* widths, const float* weight, const float* gjoint,
+                       float* const* gembs, float* gweight, int T, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- GAT structure encoder --------------------------------------------------------------------------
  * replaces torch_geometric.nn.GATConv (2.2.0, un-vendored) as used by src/aligner/networks/gat.py:36-37,44,
@@ -145,6 +151,44 @@ int sga_gat_attn_bwd(const float* H, const float* dO, const float* att_src, cons
                      float* d_att_dst, const uint8_t* complete, void* stream);
 int sga_elu_fwd(const float* x, float* y, size_t n, void* stream);                    /* F.elu, gat.py:45-46 */
 int sga_elu_bwd(const float* x, const float* gy, float* gx, size_t n, void* stream);
+
+/* ---- GCN structure encoder (EVA baseline) -----------------------------------------------------------
+ * replaces torch_geometric.nn.GCNConv(in, out, cached=False) as src/aligner/networks/gat.py:6-25 (MultiGCN) stacks it, for all graphs of a
+ * batch in one launch.  H [T,C] = x W^T (any C >= 1), bias [C] or NULL; edges / node_off / edge_off / nmax / status as for the GAT kernels
+ * above (graph-local ids, endpoints out of range dropped, at most 256 nodes per graph -- more is SGA_ERR_ARG --, 8-bit multiplicities
+ * with bit 0 of *status set beyond 255 copies of one pair).  Input self loops are removed, every node gets one self loop of weight 1,
+ * deg_i = 1 + #{listed j -> i, j != i} (duplicates counted), dinv = deg^-1/2 correctly rounded to fp32, and
+ *   transpose == 0:  out[i] = sum_{j -> i} dinv_i dinv_j H[j] + bias      (relu != 0: max(., 0) on top)
+ *   transpose != 0:  out[j] = sum_{j -> i} dinv_i dinv_j H[i]             (the backward of the line above; bias NULL, relu 0)
+ * duplicates as separate terms, the self loop included.  No floating-point atomics: the output is a pure function of the input.
+ * out must not alias H.  sga_relu_bwd: gx = gy [y > 0] for y = relu(.). */
+int sga_gcn_aggregate(const float* H, int C, const float* bias, const int64_t* edges, const int32_t* node_off, const int32_t* edge_off,
+                      int G, int nmax, int transpose, int relu, float* out, int32_t* status, void* stream);
+int sga_relu_bwd(const float* y, const float* gy, float* gx, size_t n, void* stream);
+
+/* ---- NCA loss (EVA baseline) --------------------------------------------------------------------------
+ * replaces NCALoss.forward, src/aligner/losses.py:161-173, and its autograd, over row blocks of the score matrix s = Z1 Z2^T of the A
+ * anchor pairs (Z from sga_loss_gather; the caller forms the block with sga_gemm).  S [h, lds >= A]: rows row0 .. row0 + h of s.
+ *   S_ij = exp(alpha (s_ij - ep)) off the diagonal, 0 on it;  r_i = sum_j S_ij;  c_j = sum_i S_ij
+ *   loss = mean_j log(1 + c_j) / alpha + mean_i log(1 + r_i) / alpha - beta mean_j log(1 + relu(s_jj))
+ * sga_nca_block_sums: rsum[row0 .. row0 + h) (complete: a block holds whole rows), diag[row0 ..) = s_ii, and cpart [ceil(h / R), A]: the
+ *   column sums over each group of R = sga_nca_row_group() consecutive rows of the block.  S is left as it is.
+ * sga_nca_loss: cpart [ngroups, A] = the partials of ALL blocks stacked in block order -> csum [A], invr = 1 / (1 + r), invc = 1 / (1 + c)
+ *   (fp32, [A]) and loss[0] (fp64).
+ * sga_nca_coef: G [h, ldg >= A] := gout[0] * dloss/ds (G may be S itself, with ldg == lds: in place; a separate G leaves S untouched, so a
+ *   kept block serves a second backward over the same graph),
+ *     S_ij / A (invc_j + invr_i) off the diagonal,  -beta / A [s_jj > 0] / (1 + s_jj) on it,
+ *   and GT [A, ldt >= h] := its transpose, columns h .. min(ldt, h rounded up to 4) zeroed (dZ1[block] = G Z2 and dZ2 += GT Z1[block]
+ *   then need no transposed GEMM operand, and K may be taken as a multiple of 4).  Columns A .. ldg of G are left as they are.
+ * Every sum is folded in a fixed order (fp32 within 256 columns of a row / 32 rows of a column, fp64 beyond): no floating-point atomics,
+ * results bitwise repeatable. */
+int sga_nca_row_group(void);
+int sga_nca_block_sums(const float* S, long lds, int h, int A, int row0, float alpha, float ep, double* rsum, float* diag, double* cpart,
+                       void* stream);
+int sga_nca_loss(const double* rsum, const double* cpart, int ngroups, const float* diag, int A, float alpha, float beta, double* csum,
+                 float* invr, float* invc, double* loss, void* stream);
+int sga_nca_coef(const float* S, long lds, float* G, long ldg, float* GT, long ldt, int h, int A, int row0, float alpha, float beta, float ep,
+                 const float* invr, const float* invc, const double* gout, void* stream);
 
 /* ---- contrastive (ICL) / alignment (IAL) loss ---------------------------------------------------------
  * replace src/aligner/losses.py: calculate_prob_dist :5-15, ICLLoss.forward :43-58, IALLoss.forward :68-97.

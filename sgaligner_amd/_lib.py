@@ -124,6 +124,14 @@ SIGNATURES = {
     'sga_fusion_fwd': (I, [P, I, P, P, I, I, P]),
     'sga_fusion_bwd_workspace_bytes': (c_size_t, [I]),
     'sga_fusion_bwd': (I, [P, I, P, P, P, P, I, I, P, c_size_t, P]),
+    'sga_fusion_var_fwd': (I, [P, I, P, P, P, I, P]),
+    'sga_fusion_var_bwd': (I, [P, I, P, P, P, P, P, I, P, c_size_t, P]),
+    'sga_gcn_aggregate': (I, [P, I, P, P, P, P, I, I, I, I, P, P, P]),
+    'sga_relu_bwd': (I, [P, P, P, c_size_t, P]),
+    'sga_nca_row_group': (I, []),
+    'sga_nca_block_sums': (I, [P, c_long, I, I, I, F, F, P, P, P, P]),
+    'sga_nca_loss': (I, [P, P, I, P, I, F, F, P, P, P, P, P]),
+    'sga_nca_coef': (I, [P, c_long, P, c_long, P, c_long, I, I, I, F, F, F, P, P, P, P]),
 }
 
 # enum sga_gemm_route, in the header's order (sga_gemm_plan's `route`)

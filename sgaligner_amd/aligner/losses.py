@@ -1,5 +1,5 @@
 """Contrastive (ICL) + alignment (IAL) losses -- drop-in for reference src/aligner/losses.py
-(CustomMultiLossLayer :17-34, ICLLoss :36-58, IALLoss :60-97, OverallLoss :99-152) on the tiled HIP
+(CustomMultiLossLayer :17-34, ICLLoss :36-58, IALLoss :60-97, OverallLoss :99-152, NCALoss :154-173, OverallNCALoss :175-205) on the tiled HIP
 loss kernels (csrc/contrastive.hip, loss_anchor.hip, loss_pertable.hip).  The heavy op is ops.contrastive_terms, which returns the raw
 double-summed terms; what remains here is the reference's scalar arithmetic on 1-element tensors."""
 import torch
@@ -179,3 +179,41 @@ class OverallLoss(nn.Module):
             icl_uni = (out[:, 0] / (gr.na * gr.na)).sum()
             loss = icl_uni
         return {'loss': loss, 'icl_loss_unimodal': icl_uni, 'icl_loss_multimodal': icl_multi, 'ial_loss': total_align_loss}
+
+
+class NCALoss(nn.Module):
+    """losses.py:154-173 on csrc/nca.hip (ops.nca_loss).  The reference's forward takes the two gathered, normalised row sets; gathering
+    and normalising are part of the kernels here, so `forward(emb, data_dict)` takes the raw table and the batch's e1i / e2i."""
+
+    def __init__(self, alpha, beta, ep):
+        super().__init__()
+        self.alpha = alpha
+        self.beta = beta
+        self.ep = ep
+
+    def forward(self, emb, data_dict):
+        return ops.nca_loss(emb, data_dict, alpha=self.alpha, beta=self.beta, ep=self.ep)
+
+
+class OverallNCALoss(nn.Module):
+    """losses.py:175-205: NCALoss(1, 1, 0) on every table of output_dict ('joint' included), the per-key losses and their sum."""
+
+    def __init__(self, modules, device):
+        super().__init__()
+        self.device = device
+        self.criterion_dict = {}
+        for module in modules:
+            self.criterion_dict[module] = NCALoss(alpha=1, beta=1, ep=0.0)
+        self.criterion_dict['joint'] = NCALoss(alpha=1, beta=1, ep=0.0)
+
+    def forward(self, output_dict, data_dict):
+        if isinstance(data_dict, dict) and data_dict.get('_sga_shard') is not None:
+            raise RuntimeError('sgaligner_amd.OverallNCALoss: multi-GPU sharding of the NCA loss is not implemented (`_sga_shard` in data_dict)')
+        loss_dict = {}
+        for module in output_dict.keys():
+            loss_dict[module] = self.criterion_dict[module](output_dict[module], data_dict)
+        loss_sum = 0
+        for module in loss_dict.keys():
+            loss_sum = loss_sum + loss_dict[module]
+        loss_dict['loss'] = loss_sum
+        return loss_dict

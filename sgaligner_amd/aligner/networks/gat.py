@@ -1,6 +1,7 @@
 """GAT structure encoder -- drop-in for reference src/aligner/networks/gat.py:27-48 (`MultiGAT`) and
 for the torch_geometric.nn.GATConv layers it stacks (PyG 2.2.0 parameter names, so released
-checkpoints load with strict=True: lin_src.weight / lin_dst.weight (aliased), att_src, att_dst, bias)."""
+checkpoints load with strict=True: lin_src.weight / lin_dst.weight (aliased), att_src, att_dst, bias).
+`MultiGCN` (gat.py:6-25, the EVA baseline's structure encoder) and its GCNConv layers (lin.weight, bias) likewise."""
 import math
 
 import numpy as np
@@ -52,6 +53,45 @@ class MultiGAT(nn.Module):
 
     def forward(self, x, edges):
         """Reference signature (gat.py:40): one graph, x [N,F], edges [2,E] (row 0 source, row 1 target)."""
+        e = edges.t().to(torch.int64).contiguous()
+        gb = ops.GraphBatch(np.asarray([x.shape[0]]), np.asarray([e.shape[0]]), e)
+        return self.forward_batched(x, gb)
+
+
+class GCNConv(nn.Module):
+    """Parameter holder with PyG-2.2.0 GCNConv names / shapes / init: lin.weight [out, in] glorot (the linear has no bias), bias zeros."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.lin = nn.Linear(in_channels, out_channels, bias=False)
+        self.bias = nn.Parameter(torch.zeros(out_channels))
+        a = math.sqrt(6.0 / (in_channels + out_channels))
+        nn.init.uniform_(self.lin.weight, -a, a)
+
+    def params(self):
+        return (self.lin.weight, self.bias)
+
+
+class MultiGCN(nn.Module):
+    """gat.py:6-25: GCNConv, ReLU, GCNConv (dropout 0)."""
+
+    def __init__(self, n_units=[17, 128, 100], dropout=0.0):
+        super().__init__()
+        self.num_layers = len(n_units) - 1
+        self.dropout = dropout
+        if dropout != 0.0:
+            raise NotImplementedError('sgaligner_amd MultiGCN: dropout must be 0.0 (reference default, eva.py:10)')
+        if self.num_layers != 2:
+            raise NotImplementedError('sgaligner_amd MultiGCN: the HIP path implements two layers, n_units=[F, C0, C1] (eva.py:10)')
+        self.layer_stack = nn.ModuleList([GCNConv(n_units[i], n_units[i + 1]) for i in range(self.num_layers)])     # gat.py:13-15
+
+    def forward_batched(self, x, graph_batch):
+        """All graphs of a batch in one launch per layer and direction (x [T,F], graph_batch: ops.GraphBatch)."""
+        return ops.multi_gcn(graph_batch, x, self.layer_stack[0].params(), self.layer_stack[1].params())
+
+    def forward(self, x, edges):
+        """Reference signature (gat.py:17): one graph, x [N,F], edges [2,E] (row 0 source, row 1 target)."""
         e = edges.t().to(torch.int64).contiguous()
         gb = ops.GraphBatch(np.asarray([x.shape[0]]), np.asarray([e.shape[0]]), e)
         return self.forward_batched(x, gb)

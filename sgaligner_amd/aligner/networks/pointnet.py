@@ -54,11 +54,24 @@ class PointNetfeat(BaseNetwork):
         if not xt.is_contiguous():
             xt = xt.contiguous()
         side = self.training and self.use_batch_norm and self.update_bn_running_stats and xt.shape[0] * xt.shape[1] > 0
+        # The kernels serve C3 in {64, 128, 256}.  Another out_size up to 256 (the EVA baseline's 200, eva.py:27) runs on the next one: conv3
+        # gets zero rows on the device, the extra channels (all relu(0) = 0) and their statistics are cut off again, and autograd through
+        # the pad and the slice hands conv3 its gradients.
+        c3 = self.out_size
+        c3k = next((c for c in (64, 128, 256) if c >= c3), c3)
+        w3, b3 = self.conv3.weight, self.conv3.bias
+        if c3k != c3:
+            w3 = torch.cat([w3, w3.new_zeros((c3k - c3,) + tuple(w3.shape[1:]))])
+            b3 = torch.cat([b3, b3.new_zeros(c3k - c3)])
         bn_sums = None
-        if side and ops.pointnet_bn_fusable() and self.out_size in (64, 128, 256):
-            bn_sums = torch.empty((265 + 2 * self.out_size,), device=xt.device, dtype=torch.float64)
+        if side and ops.pointnet_bn_fusable() and c3k in (64, 128, 256):
+            bn_sums = torch.empty((265 + 2 * c3k,), device=xt.device, dtype=torch.float64)
         y = ops.pointnet(xt.float() if xt.dtype != torch.float32 else xt, self.conv1.weight, self.conv1.bias,
-                         self.conv2.weight, self.conv2.bias, self.conv3.weight, self.conv3.bias, bn_sums=bn_sums)
+                         self.conv2.weight, self.conv2.bias, w3, b3, bn_sums=bn_sums)
+        if c3k != c3:
+            y = y[:, :c3]
+            if bn_sums is not None:
+                bn_sums = torch.cat([bn_sums[:265 + c3], bn_sums[265 + c3k:265 + c3k + c3]])
         if bn_sums is not None:
             self._fold_bn_sums(bn_sums, xt.shape[0] * xt.shape[1])
         elif side:

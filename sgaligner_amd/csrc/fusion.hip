@@ -95,6 +95,70 @@ __global__ void fusion_weight_grad_kernel(const float* __restrict__ weight, cons
     }
 }
 
+// Tables of DIFFERENT widths (the EVA baseline fuses 400 / 200 / 100 / 100 columns, reference src/aligner/eva.py:88-94): the same arithmetic
+// per table and row, table m's columns at offset off[m] of a joint row of dtot columns.
+struct FusionDims { int d[FU_MAXM]; int off[FU_MAXM]; int dtot; };
+
+__global__ void fusion_var_fwd_kernel(FusionPtrs embs, FusionDims dims, const float* __restrict__ weight, float* __restrict__ joint,
+                                      int T, int M) {
+    float w[FU_MAXM];
+    softmax_weights(weight, M, w);
+    const int lane = threadIdx.x & 63;
+    const int wpb = blockDim.x >> 6;
+    for (int t = blockIdx.x * wpb + (threadIdx.x >> 6); t < T; t += gridDim.x * wpb) {
+#pragma unroll
+        for (int m = 0; m < FU_MAXM; ++m) {
+            if (m >= M) break;
+            const int D = dims.d[m];
+            const float* x = embs.p[m] + (size_t)t * D;
+            float ss = 0.f;
+            for (int d = lane; d < D; d += 64) { const float v = x[d]; ss += v * v; }
+            ss = wave_sum(ss);
+            const float scale = w[m] / fmaxf(sqrtf(ss), 1e-12f);
+            float* o = joint + (size_t)t * dims.dtot + dims.off[m];
+            for (int d = lane; d < D; d += 64) o[d] = x[d] * scale;
+        }
+    }
+}
+
+__global__ void fusion_var_bwd_kernel(FusionPtrs embs, FusionDims dims, const float* __restrict__ weight, const float* __restrict__ gjoint,
+                                      FusionOutPtrs gembs, double* __restrict__ a_accum, int T, int M) {
+    float w[FU_MAXM];
+    softmax_weights(weight, M, w);
+    const int lane = threadIdx.x & 63;
+    const int wpb = blockDim.x >> 6;
+    double a_loc[FU_MAXM];
+#pragma unroll
+    for (int m = 0; m < FU_MAXM; ++m) a_loc[m] = 0.0;
+    for (int t = blockIdx.x * wpb + (threadIdx.x >> 6); t < T; t += gridDim.x * wpb) {
+#pragma unroll
+        for (int m = 0; m < FU_MAXM; ++m) {
+            if (m >= M) break;
+            const int D = dims.d[m];
+            const float* x = embs.p[m] + (size_t)t * D;
+            const float* g = gjoint + (size_t)t * dims.dtot + dims.off[m];
+            float ss = 0.f, xg = 0.f;
+            for (int d = lane; d < D; d += 64) { const float v = x[d]; ss += v * v; xg += v * g[d]; }
+            ss = wave_sum(ss);
+            xg = wave_sum(xg);
+            const float nrm = sqrtf(ss);
+            const bool clamped = nrm < 1e-12f;
+            const float inv = 1.f / fmaxf(nrm, 1e-12f);
+            const float dot = xg * inv;                      // g . xhat
+            a_loc[m] += (double)dot;
+            float* gx = gembs.p[m] + (size_t)t * D;
+            const float c1 = w[m] * inv;
+            const float c2 = clamped ? 0.f : w[m] * dot * inv * inv;   // xhat * dot / n = x * dot / n^2
+            for (int d = lane; d < D; d += 64) gx[d] = c1 * g[d] - c2 * x[d];
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int m = 0; m < FU_MAXM; ++m)
+            if (m < M && a_loc[m] != 0.0) atomicAdd(a_accum + m, a_loc[m]);
+    }
+}
+
 int grid_for_rows(int T, int wpb) {
     int g = (T + wpb - 1) / wpb;
     const int cap = sga_num_cus() * 8;
@@ -136,5 +200,60 @@ extern "C" int sga_fusion_bwd(const float* const* embs, int M, const float* weig
     if (T > 0) hipLaunchKernelGGL(fusion_bwd_kernel, dim3(grid_for_rows(T, 4)), dim3(256), 0, s, p, weight, gjoint, q, acc, T, D, M);
     hipLaunchKernelGGL(fusion_weight_grad_kernel, dim3(1), dim3(64), 0, s, weight, acc, gweight, M, 0);
     SGA_CHECK_LAUNCH("sga_fusion_bwd");
+    return SGA_OK;
+}
+
+static int fusion_var_dims(const char* who, int M, const int32_t* widths, FusionDims* dims) {
+    SGA_CHECK_ARG(M >= 1 && M <= FU_MAXM, "%s: modal_num %d outside [1,%d]", who, M, FU_MAXM);
+    SGA_CHECK_ARG(widths, "%s: null width array", who);
+    long off = 0;
+    for (int m = 0; m < M; ++m) {
+        SGA_CHECK_ARG(widths[m] >= 1, "%s: table %d has width %d < 1", who, m, (int)widths[m]);
+        dims->d[m] = widths[m];
+        dims->off[m] = (int)off;
+        off += widths[m];
+        SGA_CHECK_ARG(off < (1L << 30), "%s: joint row too wide", who);
+    }
+    dims->dtot = (int)off;
+    return SGA_OK;
+}
+
+extern "C" int sga_fusion_var_fwd(const float* const* embs, int M, const int32_t* widths, const float* weight, float* joint, int T,
+                                  void* stream) {
+    FusionDims dims{};
+    const int rc = fusion_var_dims("sga_fusion_var_fwd", M, widths, &dims);
+    if (rc) return rc;
+    SGA_CHECK_ARG(embs && weight && (joint || T == 0) && T >= 0, "sga_fusion_var_fwd: bad argument");
+    if (T == 0) return SGA_OK;
+    FusionPtrs p{};
+    for (int m = 0; m < M; ++m) { SGA_CHECK_ARG(embs[m], "sga_fusion_var_fwd: null table %d", m); p.p[m] = embs[m]; }
+    hipLaunchKernelGGL(fusion_var_fwd_kernel, dim3(grid_for_rows(T, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), p, dims, weight,
+                       joint, T, M);
+    SGA_CHECK_LAUNCH("sga_fusion_var_fwd");
+    return SGA_OK;
+}
+
+extern "C" int sga_fusion_var_bwd(const float* const* embs, int M, const int32_t* widths, const float* weight, const float* gjoint,
+                                  float* const* gembs, float* gweight, int T, void* workspace, size_t workspace_bytes, void* stream) {
+    FusionDims dims{};
+    const int rc = fusion_var_dims("sga_fusion_var_bwd", M, widths, &dims);
+    if (rc) return rc;
+    SGA_CHECK_ARG(embs && weight && (gjoint || T == 0) && gembs && gweight && T >= 0, "sga_fusion_var_bwd: bad argument");
+    if (workspace_bytes < sga_fusion_bwd_workspace_bytes(M) || !workspace) {
+        sga_set_error("sga_fusion_var_bwd: workspace too small");
+        return SGA_ERR_WORKSPACE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FusionPtrs p{};
+    FusionOutPtrs q{};
+    for (int m = 0; m < M; ++m) {
+        SGA_CHECK_ARG(T == 0 || (embs[m] && gembs[m]), "sga_fusion_var_bwd: null table %d", m);
+        p.p[m] = embs[m]; q.p[m] = gembs[m];
+    }
+    double* acc = static_cast<double*>(workspace);
+    if (hipMemsetAsync(acc, 0, sizeof(double) * M, s) != hipSuccess) { sga_set_error("sga_fusion_var_bwd: memset failed"); return SGA_ERR_HIP; }
+    if (T > 0) hipLaunchKernelGGL(fusion_var_bwd_kernel, dim3(grid_for_rows(T, 4)), dim3(256), 0, s, p, dims, weight, gjoint, q, acc, T, M);
+    hipLaunchKernelGGL(fusion_weight_grad_kernel, dim3(1), dim3(64), 0, s, weight, acc, gweight, M, 0);
+    SGA_CHECK_LAUNCH("sga_fusion_var_bwd");
     return SGA_OK;
 }

@@ -238,7 +238,47 @@ class FusionFn(torch.autograd.Function):
         return (gw, *gembs)
 
 
+class FusionVarFn(torch.autograd.Function):
+    """MultiModalFusion.forward over tables of DIFFERENT widths (reference eva.py:88-94: 400 / 200 / 100 / 100 columns)."""
+
+    @staticmethod
+    def forward(ctx, weight, *embs):
+        m = len(embs)
+        embs = [_req(e.contiguous(), f'embs[{i}]') for i, e in enumerate(embs)]
+        w = _req(weight.contiguous(), 'fusion.weight')
+        t = embs[0].shape[0]
+        for e in embs:
+            if e.dim() != 2 or e.shape[0] != t:
+                raise RuntimeError('sgaligner_amd.FusionVarFn: all modality tables must have the same number of rows')
+        widths = (_ct.c_int32 * m)(*[int(e.shape[1]) for e in embs])
+        joint = torch.empty((t, sum(widths)), device=w.device, dtype=torch.float32)
+        ev = _ev_start()
+        _lib.check(_lib.lib().sga_fusion_var_fwd(_ptr_array(embs), m, widths, _p(w), _p(joint), t, _stream()), 'sga_fusion_var_fwd')
+        _ev_stop(ev, 'fusion_var_fwd', (t, tuple(widths), m))
+        ctx.save_for_backward(w, *embs)
+        return joint
+
+    @staticmethod
+    def backward(ctx, gj):
+        w, *embs = ctx.saved_tensors
+        m = len(embs)
+        t = embs[0].shape[0]
+        gj = gj.contiguous()
+        widths = (_ct.c_int32 * m)(*[int(e.shape[1]) for e in embs])
+        gembs = [torch.empty_like(e) for e in embs]
+        gw = torch.empty_like(w)
+        nb = _lib.lib().sga_fusion_bwd_workspace_bytes(m)
+        ws = torch.empty((nb,), device=w.device, dtype=torch.uint8)
+        ev = _ev_start()
+        _lib.check(_lib.lib().sga_fusion_var_bwd(_ptr_array(embs), m, widths, _p(w), _p(gj), _ptr_array(gembs), _p(gw), t,
+                                                 _p(ws), nb, _stream()), 'sga_fusion_var_bwd')
+        _ev_stop(ev, 'fusion_var_bwd', (t, tuple(widths), m))
+        return (gw, *gembs)
+
+
 def fusion(weight, embs):
+    if len({int(e.shape[-1]) for e in embs}) > 1:          # only tables of different widths take the new route
+        return FusionVarFn.apply(weight, *embs)
     return FusionFn.apply(weight, *embs)
 
 
@@ -464,6 +504,8 @@ _REEXPORT = {
                  'contrastive_terms', 'LossHeadFn', 'LossGroups', 'GroupedContrastiveFn', 'grouped_contrastive_terms', 'group_data_dicts',
                  '_allreduce_sum', 'FusedContrastiveFn', 'fused_contrastive_terms'),
     'gat_ops': ('GraphBatch', '_attn_fwd', '_attn_bwd', '_elu', 'MultiGATFn', 'multi_gat'),
+    'gcn_ops': ('gcn_aggregate', 'MultiGCNFn', 'multi_gcn'),
+    'nca_ops': ('NCAFn', 'nca_loss'),
     'rank_ops': ('PairLayout', 'QueryBlocks', 'simrank', 'pair_metrics'),
 }
 _WHERE = {name: mod for mod, names in _REEXPORT.items() for name in names}

@@ -2,6 +2,7 @@
 signatures (src/engine/epoch_based_trainer.py:56-60, src/engine/single_tester.py:52-63,
 src/trainers/trainval_sgaligner.py:71-79, src/inference/sgaligner/inference_align_reg.py:74-76,98-143),
 so the reference's EpochBasedTrainer / SingleTester loops can call them unchanged.
+`EVASteps` is the same for the EVA baseline (src/trainers/trainval_eva.py:16-62), single device.
 Multi-GPU: one process per GPU, pairs sharded, tables all-gathered for the batch-global loss."""
 from __future__ import annotations
 
@@ -12,7 +13,8 @@ import torch.distributed as dist
 from . import dist as sdist
 from . import ops
 from .aligner import losses
-from .aligner.losses import CustomMultiLossLayer, OverallLoss
+from .aligner.eva import EVA
+from .aligner.losses import CustomMultiLossLayer, OverallLoss, OverallNCALoss
 from .aligner.sg_aligner import MultiModalEncoder
 from .utils import alignment
 
@@ -180,3 +182,50 @@ class AlignerSteps:
         gdd['_sga_shard'] = (cuts[rank], cuts[rank + 1], cuts, rank)
         gdd['_sga_reduce'] = _reduce
         return self.loss_func(gathered, gdd)
+
+
+class EVASteps:
+    """trainval_eva.py:16-62: the EVA model, OverallNCALoss, Adam over the model parameters (the loss has none), and the step hooks.
+    Single device: the NCA loss is not sharded."""
+
+    def __init__(self, modules, rel_dim=41, attr_dim=164, device='cuda', seed=42, lr=1e-3, weight_decay=0.0):
+        if not torch.cuda.is_available() and str(device).startswith('cuda'):
+            raise RuntimeError('sgaligner_amd.EVASteps: no HIP device; the product path has no CPU fallback')
+        self.modules = list(modules)
+        self.device = torch.device(device)
+        torch.manual_seed(seed)
+        self.model = EVA(modules=self.modules, rel_dim=rel_dim, attr_dim=attr_dim).to(self.device)       # :48-52
+        self.loss_func = OverallNCALoss(modules=self.modules, device=self.device)                       # :40
+        self.params = list(self.model.parameters())                                                      # :41
+        self.optimizer = torch.optim.Adam([{'params': self.params}], lr=lr, weight_decay=weight_decay)   # :44
+
+    def train_step(self, epoch, iteration, data_dict):
+        if dist.is_initialized() and dist.get_world_size() > 1:
+            raise RuntimeError('sgaligner_amd.EVASteps: the EVA baseline runs on one device (multi-GPU NCA loss is not implemented)')
+        output_dict = self.model(data_dict)
+        loss_dict = self.loss_func(output_dict, data_dict)
+        return output_dict, loss_dict
+
+    val_step = train_step
+
+    def test_step(self, iteration, data_dict):
+        with torch.no_grad():
+            return self.model(data_dict)
+
+    def eval_step(self, iteration, data_dict, output_dict, all_k=(1, 2, 3, 4, 5), reg_k=0):
+        """src/inference/eva/inference_align.py's eval_step: the arithmetic of the rank ops (utils.alignment.evaluate_batch)."""
+        emb = output_dict['joint'] if len(self.modules) > 1 else output_dict[self.modules[0]]
+        return alignment.evaluate_batch(emb.detach(), data_dict, all_k=all_k, reg_k=reg_k)
+
+    def zero_grad(self):
+        for p in self.params:
+            p.grad = None
+
+    def forward_backward(self, data_dict):
+        self.zero_grad()
+        output_dict, loss_dict = self.train_step(0, 0, data_dict)
+        loss_dict['loss'].backward()
+        return output_dict, loss_dict
+
+    def optimizer_step(self):
+        self.optimizer.step()
