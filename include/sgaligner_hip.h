@@ -149,6 +149,21 @@ int sga_gat_attn_fwd(const float* H, const float* att_src, const float* att_dst,
 int sga_gat_attn_bwd(const float* H, const float* dO, const float* att_src, const float* att_dst, const int64_t* edges,
                      const int32_t* node_off, const int32_t* edge_off, int G, int nmax, float* dH, float* d_att_src,
                      float* d_att_dst, const uint8_t* complete, void* stream);
+/* The same two for any GATConv(in, channels, heads) the reference's MultiGAT can stack (gat.py:35-37): heads >= 1 heads of 1 <= channels <= 256
+ * channels each.  H / dO / out / dH [T, heads*channels] head-major, att_src / att_dst / bias / d_att_src / d_att_dst [heads*channels];
+ * everything else -- edges, offsets, nmax <= 256, status, complete, the arithmetic and its order, the limits above -- as for sga_gat_attn_fwd /
+ * sga_gat_attn_bwd, which remain the route of the 2 x 128 layers.  One workgroup per (graph, head); lanes span the channels in
+ * ceil(channels / 64) slots, the last one masked.  A head's features [N, channels] (and, backward, their gradient's) are kept in LDS, row stride
+ * channels | 1, while they fit the 160 KiB of a CU beside the multiplicity matrix: sga_gat_lds_nodes(channels, bwd) is the largest nmax for which
+ * they do (bwd != 0: the backward kernel's two copies); above it the rows are read from global memory.
+ * heads < 1, channels < 1 or channels > 256 is SGA_ERR_ARG (sga_gat_lds_nodes: -1), before any device call. */
+int sga_gat_attn_fwd_hc(const float* H, int heads, int channels, const float* att_src, const float* att_dst, const float* bias,
+                        const int64_t* edges, const int32_t* node_off, const int32_t* edge_off, int G, int nmax,
+                        float* out, int32_t* status, const uint8_t* complete, void* stream);
+int sga_gat_attn_bwd_hc(const float* H, const float* dO, int heads, int channels, const float* att_src, const float* att_dst,
+                        const int64_t* edges, const int32_t* node_off, const int32_t* edge_off, int G, int nmax, float* dH,
+                        float* d_att_src, float* d_att_dst, const uint8_t* complete, void* stream);
+int sga_gat_lds_nodes(int channels, int bwd);
 int sga_elu_fwd(const float* x, float* y, size_t n, void* stream);                    /* F.elu, gat.py:45-46 */
 int sga_elu_bwd(const float* x, const float* gy, float* gx, size_t n, void* stream);
 

@@ -39,6 +39,9 @@ SIGNATURES = {
     'sga_gat_complete_flags': (I, [P, P, P, I, P, P]),
     'sga_gat_attn_fwd': (I, [P, P, P, P, P, P, P, I, I, P, P, P, P]),
     'sga_gat_attn_bwd': (I, [P, P, P, P, P, P, P, I, I, P, P, P, P, P]),
+    'sga_gat_attn_fwd_hc': (I, [P, I, I, P, P, P, P, P, P, I, I, P, P, P, P]),
+    'sga_gat_attn_bwd_hc': (I, [P, P, I, I, P, P, P, P, P, I, I, P, P, P, P, P]),
+    'sga_gat_lds_nodes': (I, [I, I]),
     'sga_elu_fwd': (I, [P, P, c_size_t, P]),
     'sga_elu_bwd': (I, [P, P, P, c_size_t, P]),
     'sga_simrank_workspace_bytes': (c_size_t, [I]),

@@ -32,24 +32,39 @@ class GATConv(nn.Module):
 
 
 class MultiGAT(nn.Module):
+    """gat.py:27-48: GATConv layers of any depth, head count and width (at most MAX_CHANNELS channels per head), dropout on every layer's
+    input, ELU between layers.  The reference's own model -- n_units=[F,128,128], n_heads=[2,2], no dropout -- runs on the kernels
+    specialised for it; every other stack on the general ones (ops.multi_gat_layers)."""
+    MAX_CHANNELS = 256
+
     def __init__(self, n_units=[17, 128, 100], n_heads=[2, 2], dropout=0.0):
         super().__init__()
         self.num_layers = len(n_units) - 1
         self.dropout = dropout
-        if dropout != 0.0:
-            raise NotImplementedError('sgaligner_amd MultiGAT: dropout must be 0.0 (reference default, sg_aligner.py:39)')
-        if self.num_layers != 2 or list(n_units[1:]) != [128, 128] or list(n_heads) != [2, 2]:
-            raise NotImplementedError('sgaligner_amd MultiGAT: the HIP path implements n_units=[F,128,128], n_heads=[2,2] '
-                                      '(hard-coded in the reference, sg_aligner.py:38,66)')
+        if self.num_layers < 1 or len(n_heads) != self.num_layers:
+            raise ValueError(f'sgaligner_amd MultiGAT: n_units {list(n_units)} needs at least two entries and one head count per layer, '
+                             f'got n_heads {list(n_heads)}')
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError(f'sgaligner_amd MultiGAT: dropout must be in [0, 1), got {dropout}')
+        if any(int(h) < 1 for h in n_heads) or any(int(c) < 1 for c in n_units):
+            raise ValueError(f'sgaligner_amd MultiGAT: widths and head counts must be positive, got {list(n_units)} / {list(n_heads)}')
+        if max(n_units[1:]) > self.MAX_CHANNELS:
+            raise NotImplementedError(f'sgaligner_amd MultiGAT: the HIP attention kernels hold at most {self.MAX_CHANNELS} channels per head, '
+                                      f'n_units={list(n_units)} asks for {max(n_units[1:])}')
         layers = []
         for i in range(self.num_layers):                                    # gat.py:34-37
             in_c = n_units[i] * n_heads[i - 1] if i else n_units[i]
             layers.append(GATConv(in_c, n_units[i + 1], n_heads[i]))
         self.layer_stack = nn.ModuleList(layers)
+        self._canonical = self.num_layers == 2 and list(n_units[1:]) == [128, 128] and list(n_heads) == [2, 2]
 
-    def forward_batched(self, x, graph_batch):
-        """All graphs of a batch in one launch per layer (x [T,F], graph_batch: ops.GraphBatch)."""
-        return ops.multi_gat(graph_batch, x, self.layer_stack[0].params(), self.layer_stack[1].params())
+    def forward_batched(self, x, graph_batch, masks=None):
+        """All graphs of a batch in one launch per layer (x [T,F], graph_batch: ops.GraphBatch).  masks: one [T, in_width] tensor per layer,
+        already scaled by 1 / (1 - p), used INSTEAD of drawing (parity with a recorded run); without them F.dropout draws in train mode."""
+        drop = self.training and self.dropout > 0.0
+        if self._canonical and masks is None and not drop:
+            return ops.multi_gat(graph_batch, x, self.layer_stack[0].params(), self.layer_stack[1].params())
+        return ops.multi_gat_layers(graph_batch, x, [l.params() for l in self.layer_stack], p=self.dropout, training=self.training, masks=masks)
 
     def forward(self, x, edges):
         """Reference signature (gat.py:40): one graph, x [N,F], edges [2,E] (row 0 source, row 1 target)."""

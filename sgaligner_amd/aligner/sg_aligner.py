@@ -103,6 +103,10 @@ class MultiModalEncoder(nn.Module):
                 # all 2B graphs in one launch per layer (reference: 2B sequential GATConv calls, :86-110)
                 gb = ops.GraphBatch.of(data_dict)
                 emb = self.structure_encoder.forward_batched(data_dict['tot_rel_pose'], gb)
+                if emb.shape[1] != self.structure_embedding.in_features:
+                    # the reference hard-codes nn.Linear(256, emb_dim) (:67) and fails here too, with a shape error
+                    raise RuntimeError(f'sgaligner_amd.MultiModalEncoder: the GAT stack hidden_units={list(self.hidden_units)}, heads={list(self.heads)} '
+                                       f'ends {emb.shape[1]} wide but structure_embedding takes {self.structure_embedding.in_features}')
                 emb = self.structure_embedding(emb)
             elif module in ('point', 'pct'):
                 emb = self.object_encoder(pts.permute(0, 2, 1))         # :72,:115

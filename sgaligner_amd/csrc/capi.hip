@@ -13,5 +13,5 @@ void sga_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* sga_last_error(void) { return g_err; }
-extern "C" int sga_version(void) { return 101; }  // 0.1.1: + GCN aggregation, NCA loss, fusion over tables of different widths
+extern "C" int sga_version(void) { return 102; }  // 0.1.2: + GAT attention for any head count and width (sga_gat_attn_*_hc)
 extern "C" int sga_device_cus(void) { return sga_num_cus(); }

@@ -455,3 +455,405 @@ extern "C" int sga_elu_bwd(const float* x, const float* gy, float* gx, size_t n,
     SGA_CHECK_LAUNCH("sga_elu_bwd");
     return SGA_OK;
 }
+
+// ---- the general form: GATConv(in, C, heads) for any heads >= 1 and 1 <= C <= 256 (every stack reference gat.py:34-37 can build) ----
+// Same algorithm, arithmetic and order as the kernels above, which remain the route of the 2 x 128 layers.  heads and C are run-time values
+// (grid y, row stride heads * C); lanes span the channels in CJ = ceil(C / 64) slots (channel c = lane + 64 k), a template parameter.  Only
+// the LAST slot can be ragged: its lanes past C read channel C - 1 again (a valid address, no branch in the inner loops), enter every dot
+// product with weight 0 and are never written.  The LDS row stride is C | 1: odd for every C, so lanes walking down a column (backward
+// phase 1: one source row per lane) and lanes walking along a row both hit 64 different banks.  NJ (source slots per lane) follows the
+// node count as above; whether the head's feature rows live in LDS (LDSF) is decided on the host, per launch, from C, nmax and the
+// 160 KiB of LDS a CU has -- so NJ = 4 with resident features exists here (narrow heads), and NJ = 2 without (wide heads, backward).
+namespace {
+
+constexpr int GAT_CMAX = 256;                      // channels per head (CJ <= 4)
+constexpr size_t GAT_LDS_BUDGET = 160 * 1024;      // LDS of one CU (gfx950): one workgroup may have all of it
+
+inline int gat_hs(int C) { return C | 1; }
+inline int gat_nj(int nmax) { return nmax <= GAT_MAXN ? 2 : 4; }
+
+inline size_t gat_lds_bytes_hc(int nmax, bool bwd, int C, bool ldsf) {
+    const int npad = (nmax + 3) & ~3;
+    return sizeof(float) * ((ldsf ? (size_t)nmax * gat_hs(C) * (bwd ? 2 : 1) : 0) + 6 * (size_t)gat_nj(nmax) * 64) + (size_t)nmax * npad;
+}
+
+inline bool gat_fits_lds(int nmax, bool bwd, int C) { return gat_lds_bytes_hc(nmax, bwd, C, true) <= GAT_LDS_BUDGET; }
+
+template <int NJ, bool LDSF>
+__device__ __forceinline__ GatLds carve_hc(float* base, int nmax, int hs, bool bwd) {
+    constexpr int MAXN = NJ * 64;
+    GatLds l;
+    float* p = base;
+    l.hs = p; if (LDSF) p += nmax * hs;
+    l.dos = p; if (LDSF && bwd) p += nmax * hs;
+    l.as = p; p += MAXN;
+    l.ad = p; p += MAXN;
+    l.mx = p; p += MAXN;
+    l.den = p; p += MAXN;
+    l.das = p; p += MAXN;
+    l.dad = p; p += MAXN;
+    l.cnt = reinterpret_cast<unsigned*>(p);
+    return l;
+}
+
+// N rows of C channels, global (row stride ld) -> LDS (row stride hs): one wave per row, lanes along the row
+template <int CJ>
+__device__ __forceinline__ void rows_to_lds(float* dst, int hs, const float* __restrict__ src, int ld, int N, int C) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int j = wave; j < N; j += GAT_THREADS / 64)
+#pragma unroll
+        for (int k = 0; k < CJ; ++k) {
+            const int c = lane + 64 * k;
+            if (c < C) dst[j * hs + c] = src[(size_t)j * ld + c];
+        }
+}
+
+// common prologue (gat_prologue for run-time heads / C): features (LDSF), the logits' node parts, the multiplicity matrix
+template <int NJ, int CJ, bool LDSF>
+__device__ __forceinline__ Rows gat_prologue_hc(const GatLds& l, const float* __restrict__ H, const float* __restrict__ att_s,
+                                                const float* __restrict__ att_d, const long long* __restrict__ edges,
+                                                int n0, int N, int e0, int E, int hd, int heads, int C, int hs, int npad,
+                                                int* status, bool complete) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int HC = heads * C;
+    const float* Hg = H + (size_t)n0 * HC + hd * C;
+    if (LDSF) rows_to_lds<CJ>(l.hs, hs, Hg, HC, N, C);
+    if (complete) {                                        // every multiplicity is 1: the edge list is never touched
+        for (int e = tid; e < N * (npad >> 2); e += GAT_THREADS) {
+            const int j4 = (e % (npad >> 2)) * 4;
+            l.cnt[e] = (j4 + 0 < N ? 1u : 0u) | (j4 + 1 < N ? 0x100u : 0u) | (j4 + 2 < N ? 0x10000u : 0u) | (j4 + 3 < N ? 0x1000000u : 0u);
+        }
+    } else {
+        for (int e = tid; e < N * (npad >> 2); e += GAT_THREADS) l.cnt[e] = 0u;
+    }
+    __syncthreads();
+    const Rows hr = LDSF ? Rows{l.hs, hs} : Rows{Hg, HC};
+    float sv[CJ], dv[CJ];
+    int cc[CJ];
+#pragma unroll
+    for (int k = 0; k < CJ; ++k) {
+        const int c = lane + 64 * k;
+        cc[k] = min(c, C - 1);
+        sv[k] = c < C ? att_s[hd * C + c] : 0.f;
+        dv[k] = c < C ? att_d[hd * C + c] : 0.f;
+    }
+    for (int j = wave; j < N; j += GAT_THREADS / 64) {
+        float ps = 0.f, pd = 0.f;
+#pragma unroll
+        for (int k = 0; k < CJ; ++k) {
+            const float h = hr.p[(size_t)j * hr.stride + cc[k]];
+            ps = fmaf(h, sv[k], ps);
+            pd = fmaf(h, dv[k], pd);
+        }
+        const float vs = wave_sum(ps), vd = wave_sum(pd);
+        if (lane == 0) { l.as[j] = vs; l.ad[j] = vd; }
+    }
+    // edge list -> multiplicities (self loops dropped, out-of-range ids ignored, counts saturate at 255: reported through `status`)
+    for (int e = tid; e < (complete ? 0 : E); e += GAT_THREADS) {
+        const long long sj = edges[(size_t)(e0 + e) * 2 + 0], di = edges[(size_t)(e0 + e) * 2 + 1];
+        if (sj != di && sj >= 0 && sj < N && di >= 0 && di < N) {
+            const int idx = (int)di * npad + (int)sj;
+            const unsigned sh = 8u * (idx & 3);
+            const unsigned old = atomicAdd(&l.cnt[idx >> 2], 1u << sh);
+            if (((old >> sh) & 255u) == 255u) {
+                atomicSub(&l.cnt[idx >> 2], 1u << sh);
+                if (status) atomicOr(status, 1);
+            }
+        }
+    }
+    __syncthreads();
+    unsigned char* cb = reinterpret_cast<unsigned char*>(l.cnt);
+    for (int i = tid; i < N; i += GAT_THREADS) cb[i * npad + i] = 1;       // exactly one self loop per node
+    __syncthreads();
+    return hr;
+}
+
+template <int NJ, int CJ, bool LDSF>
+__global__ __launch_bounds__(GAT_THREADS) void gat_attn_fwd_hc_kernel(
+    const float* __restrict__ H, const float* __restrict__ att_s, const float* __restrict__ att_d,
+    const float* __restrict__ bias, const long long* __restrict__ edges, const int* __restrict__ node_off,
+    const int* __restrict__ edge_off, float* __restrict__ out, int nmax, int C, int* __restrict__ status,
+    const unsigned char* __restrict__ complete) {
+    extern __shared__ __attribute__((aligned(16))) float lds_raw[];
+    const int hs = C | 1, heads = gridDim.y, HC = heads * C;
+    const GatLds l = carve_hc<NJ, LDSF>(lds_raw, nmax, hs, false);
+    const int g = blockIdx.x, hd = blockIdx.y;
+    const int n0 = node_off[g], N = node_off[g + 1] - n0, e0 = edge_off[g], E = edge_off[g + 1] - e0;
+    const int npad = (nmax + 3) & ~3;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (N <= 0) return;
+    const Rows hr = gat_prologue_hc<NJ, CJ, LDSF>(l, H, att_s, att_d, edges, n0, N, e0, E, hd, heads, C, hs, npad, status, complete && complete[g]);
+    int cc[CJ];
+    float bv[CJ];
+#pragma unroll
+    for (int k = 0; k < CJ; ++k) { cc[k] = min(lane + 64 * k, C - 1); bv[k] = bias[hd * C + cc[k]]; }
+    for (int ib = wave * GAT_TB; ib < N; ib += (GAT_THREADS / 64) * GAT_TB) {
+        float al[GAT_TB][NJ], acc[GAT_TB][CJ];
+#pragma unroll
+        for (int u = 0; u < GAT_TB; ++u) {
+            float pre[NJ], m, den;
+#pragma unroll
+            for (int q = 0; q < CJ; ++q) acc[u][q] = 0.f;
+#pragma unroll
+            for (int k = 0; k < NJ; ++k) al[u][k] = 0.f;
+            if (ib + u < N) softmax_row<NJ>(l, ib + u, N, npad, lane, al[u], pre, m, den);
+        }
+#pragma unroll
+        for (int k = 0; k < NJ; ++k)
+            for (int jj = 0; jj < 64 && 64 * k + jj < N; ++jj) {
+                const int j = 64 * k + jj;
+                float h[CJ];
+#pragma unroll
+                for (int q = 0; q < CJ; ++q) h[q] = hr.p[(size_t)j * hr.stride + cc[q]];
+#pragma unroll
+                for (int u = 0; u < GAT_TB; ++u) {
+                    const float a = __shfl(al[u][k], jj, 64);
+#pragma unroll
+                    for (int q = 0; q < CJ; ++q) acc[u][q] = fmaf(a, h[q], acc[u][q]);
+                }
+            }
+#pragma unroll
+        for (int u = 0; u < GAT_TB; ++u)
+            if (ib + u < N) {
+                float* o = out + (size_t)(n0 + ib + u) * HC + hd * C;
+#pragma unroll
+                for (int q = 0; q < CJ; ++q)
+                    if (lane + 64 * q < C) o[lane + 64 * q] = acc[u][q] + bv[q];
+            }
+    }
+}
+
+template <int NJ, int CJ, bool LDSF>
+__global__ __launch_bounds__(GAT_THREADS) void gat_attn_bwd_hc_kernel(
+    const float* __restrict__ H, const float* __restrict__ dO, const float* __restrict__ att_s,
+    const float* __restrict__ att_d, const long long* __restrict__ edges, const int* __restrict__ node_off,
+    const int* __restrict__ edge_off, float* __restrict__ dH, float* __restrict__ d_att_s,
+    float* __restrict__ d_att_d, int nmax, int C, const unsigned char* __restrict__ complete) {
+    constexpr int MAXN = NJ * 64;
+    extern __shared__ __attribute__((aligned(16))) float lds_raw[];
+    const int hs = C | 1, heads = gridDim.y, HC = heads * C;
+    const GatLds l = carve_hc<NJ, LDSF>(lds_raw, nmax, hs, true);
+    const int g = blockIdx.x, hd = blockIdx.y;
+    const int n0 = node_off[g], N = node_off[g + 1] - n0, e0 = edge_off[g], E = edge_off[g + 1] - e0;
+    const int npad = (nmax + 3) & ~3;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (N <= 0) return;
+    const float* Dg = dO + (size_t)n0 * HC + hd * C;
+    if (LDSF) rows_to_lds<CJ>(l.dos, hs, Dg, HC, N, C);
+    for (int j = tid; j < MAXN; j += GAT_THREADS) l.das[j] = 0.f;
+    const Rows hr = gat_prologue_hc<NJ, CJ, LDSF>(l, H, att_s, att_d, edges, n0, N, e0, E, hd, heads, C, hs, npad, nullptr, complete && complete[g]);
+    const Rows dr = LDSF ? Rows{l.dos, hs} : Rows{Dg, HC};
+
+    // ---- phase 1: per target row i -> d a_d[i], partial d a_s[j], row max / denom
+    float das[NJ];
+    int js[NJ];
+#pragma unroll
+    for (int k = 0; k < NJ; ++k) { das[k] = 0.f; js[k] = lane + 64 * k < N ? lane + 64 * k : 0; }
+    for (int ib = wave * GAT_TB; ib < N; ib += (GAT_THREADS / 64) * GAT_TB) {
+        float al[GAT_TB][NJ], pre[GAT_TB][NJ], m[GAT_TB], den[GAT_TB], da[GAT_TB][NJ];
+#pragma unroll
+        for (int u = 0; u < GAT_TB; ++u) {
+            m[u] = 0.f; den[u] = 1.f;
+#pragma unroll
+            for (int k = 0; k < NJ; ++k) { al[u][k] = 0.f; pre[u][k] = 0.f; da[u][k] = 0.f; }
+            if (ib + u < N) softmax_row<NJ>(l, ib + u, N, npad, lane, al[u], pre[u], m[u], den[u]);
+        }
+        // d alpha_ij = <dO[i], h[j]> for GAT_TB targets i at once: the h reads per channel are shared
+        for (int c = 0; c < C; ++c) {
+            float hv[NJ];
+#pragma unroll
+            for (int k = 0; k < NJ; ++k) hv[k] = hr.p[(size_t)js[k] * hr.stride + c];
+#pragma unroll
+            for (int u = 0; u < GAT_TB; ++u) {
+                const float d = dr.p[(size_t)min(ib + u, N - 1) * dr.stride + c];
+#pragma unroll
+                for (int k = 0; k < NJ; ++k) da[u][k] = fmaf(d, hv[k], da[u][k]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < GAT_TB; ++u) {
+            if (ib + u >= N) continue;
+            float dot = 0.f;
+#pragma unroll
+            for (int k = 0; k < NJ; ++k) dot = fmaf(al[u][k], da[u][k], dot);
+            const float s = wave_sum(dot);
+            float dsum = 0.f;
+#pragma unroll
+            for (int k = 0; k < NJ; ++k) {
+                const float ds = al[u][k] * (da[u][k] - s) * (pre[u][k] > 0.f ? 1.f : GAT_SLOPE);
+                das[k] += ds;
+                dsum += ds;
+            }
+            const float dd = wave_sum(dsum);
+            if (lane == 0) { l.dad[ib + u] = dd; l.mx[ib + u] = m[u]; l.den[ib + u] = den[u]; }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NJ; ++k)
+        if (lane + 64 * k < N) atomicAdd(&l.das[lane + 64 * k], das[k]);
+    __syncthreads();
+
+    // ---- phase 2: per source j -> dH[j] = sum_i alpha_ij dO[i] + d a_s[j] att_s + d a_d[j] att_d ; d att
+    const unsigned char* cb = reinterpret_cast<const unsigned char*>(l.cnt);
+    int cc[CJ];
+    float sv[CJ], dv[CJ], gs[CJ], gd[CJ];
+#pragma unroll
+    for (int q = 0; q < CJ; ++q) {
+        cc[q] = min(lane + 64 * q, C - 1);
+        sv[q] = att_s[hd * C + cc[q]];
+        dv[q] = att_d[hd * C + cc[q]];
+        gs[q] = 0.f; gd[q] = 0.f;
+    }
+    for (int jb = wave * GAT_TB; jb < N; jb += (GAT_THREADS / 64) * GAT_TB) {
+        float al[GAT_TB][NJ], acc[GAT_TB][CJ];
+#pragma unroll
+        for (int u = 0; u < GAT_TB; ++u) {
+#pragma unroll
+            for (int q = 0; q < CJ; ++q) acc[u][q] = 0.f;
+            const int j = jb + u;
+            const float asj = j < N ? l.as[j] : 0.f;
+#pragma unroll
+            for (int k = 0; k < NJ; ++k) {
+                al[u][k] = 0.f;
+                const int i = lane + 64 * k;
+                if (j < N && i < N) {
+                    const float c = (float)cb[i * npad + j];
+                    if (c > 0.f) al[u][k] = c * __expf(lrelu(asj + l.ad[i]) - l.mx[i]) / l.den[i];
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NJ; ++k)
+            for (int ii = 0; ii < 64 && 64 * k + ii < N; ++ii) {
+                const int i = 64 * k + ii;
+                float gv[CJ];
+#pragma unroll
+                for (int q = 0; q < CJ; ++q) gv[q] = dr.p[(size_t)i * dr.stride + cc[q]];
+#pragma unroll
+                for (int u = 0; u < GAT_TB; ++u) {
+                    const float a = __shfl(al[u][k], ii, 64);
+#pragma unroll
+                    for (int q = 0; q < CJ; ++q) acc[u][q] = fmaf(a, gv[q], acc[u][q]);
+                }
+            }
+#pragma unroll
+        for (int u = 0; u < GAT_TB; ++u) {
+            const int j = jb + u;
+            if (j >= N) continue;
+            const float dasj = l.das[j], dadj = l.dad[j];
+            float* o = dH + (size_t)(n0 + j) * HC + hd * C;
+#pragma unroll
+            for (int q = 0; q < CJ; ++q) {
+                if (lane + 64 * q < C) o[lane + 64 * q] = acc[u][q] + dasj * sv[q] + dadj * dv[q];
+                const float h = hr.p[(size_t)j * hr.stride + cc[q]];
+                gs[q] = fmaf(dasj, h, gs[q]);
+                gd[q] = fmaf(dadj, h, gd[q]);
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < CJ; ++q)
+        if (lane + 64 * q < C) {
+            atomicAdd(d_att_s + hd * C + lane + 64 * q, gs[q]);
+            atomicAdd(d_att_d + hd * C + lane + 64 * q, gd[q]);
+        }
+}
+
+int check_hc(int heads, int channels, const char* who) {
+    if (heads < 1) { sga_set_error("%s: heads %d < 1", who, heads); return SGA_ERR_ARG; }
+    if (channels < 1 || channels > GAT_CMAX) {
+        sga_set_error("%s: channels %d outside 1 .. %d per head", who, channels, GAT_CMAX);
+        return SGA_ERR_ARG;
+    }
+    return SGA_OK;
+}
+
+template <int NJ, int CJ, bool LDSF>
+void launch_fwd_hc(size_t lds, int G, int heads, hipStream_t s, const float* H, const float* att_s, const float* att_d, const float* bias,
+                   const long long* edges, const int* node_off, const int* edge_off, float* out, int nmax, int C, int* status,
+                   const unsigned char* complete) {
+    auto k = gat_attn_fwd_hc_kernel<NJ, CJ, LDSF>;
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k, dim3(G, heads), dim3(GAT_THREADS), lds, s, H, att_s, att_d, bias, edges, node_off, edge_off, out, nmax, C, status, complete);
+}
+
+template <int NJ, int CJ, bool LDSF>
+void launch_bwd_hc(size_t lds, int G, int heads, hipStream_t s, const float* H, const float* dO, const float* att_s, const float* att_d,
+                   const long long* edges, const int* node_off, const int* edge_off, float* dH, float* d_att_s, float* d_att_d, int nmax,
+                   int C, const unsigned char* complete) {
+    auto k = gat_attn_bwd_hc_kernel<NJ, CJ, LDSF>;
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k, dim3(G, heads), dim3(GAT_THREADS), lds, s, H, dO, att_s, att_d, edges, node_off, edge_off, dH, d_att_s, d_att_d, nmax, C, complete);
+}
+
+// FN<NJ, CJ, LDSF>(...) for the run-time (nj in {2, 4}, cj in 1 .. 4, ldsf)
+#define GAT_HC_CJ(FN, NJ, LDSF, ...)                         \
+    switch (cj) {                                            \
+        case 1: FN<NJ, 1, LDSF>(__VA_ARGS__); break;         \
+        case 2: FN<NJ, 2, LDSF>(__VA_ARGS__); break;         \
+        case 3: FN<NJ, 3, LDSF>(__VA_ARGS__); break;         \
+        default: FN<NJ, 4, LDSF>(__VA_ARGS__); break;        \
+    }
+#define GAT_HC_DISPATCH(FN, ...)                                                \
+    do {                                                                        \
+        if (nj == 2 && ldsf) { GAT_HC_CJ(FN, 2, true, __VA_ARGS__) }            \
+        else if (nj == 2) { GAT_HC_CJ(FN, 2, false, __VA_ARGS__) }              \
+        else if (ldsf) { GAT_HC_CJ(FN, 4, true, __VA_ARGS__) }                  \
+        else { GAT_HC_CJ(FN, 4, false, __VA_ARGS__) }                           \
+    } while (0)
+
+}  // namespace
+
+extern "C" int sga_gat_lds_nodes(int channels, int bwd) {
+    if (channels < 1 || channels > GAT_CMAX) {
+        sga_set_error("sga_gat_lds_nodes: channels %d outside 1 .. %d per head", channels, GAT_CMAX);
+        return -1;
+    }
+    int n = 0;
+    while (n < GAT_MAXN_BIG && gat_fits_lds(n + 1, bwd != 0, channels)) ++n;      // the byte count grows with the node count
+    return n;
+}
+
+extern "C" int sga_gat_attn_fwd_hc(const float* H, int heads, int channels, const float* att_src, const float* att_dst, const float* bias,
+                                   const int64_t* edges, const int32_t* node_off, const int32_t* edge_off, int G, int nmax,
+                                   float* out, int32_t* status, const uint8_t* complete, void* stream) {
+    int rc = check_hc(heads, channels, "sga_gat_attn_fwd_hc");
+    if (rc) return rc;
+    rc = check_common(G, nmax, "sga_gat_attn_fwd_hc");
+    if (rc) return rc;
+    if (G == 0 || nmax == 0) return SGA_OK;
+    SGA_CHECK_ARG(H && att_src && att_dst && bias && node_off && edge_off && out, "sga_gat_attn_fwd_hc: null pointer");
+    const int nj = gat_nj(nmax), cj = (channels + 63) / 64;
+    const bool ldsf = gat_fits_lds(nmax, false, channels);
+    const size_t lds = gat_lds_bytes_hc(nmax, false, channels, ldsf);
+    GAT_HC_DISPATCH(launch_fwd_hc, lds, G, heads, static_cast<hipStream_t>(stream), H, att_src, att_dst, bias,
+                    reinterpret_cast<const long long*>(edges), node_off, edge_off, out, nmax, channels, status, complete);
+    SGA_CHECK_LAUNCH("sga_gat_attn_fwd_hc");
+    return SGA_OK;
+}
+
+extern "C" int sga_gat_attn_bwd_hc(const float* H, const float* dO, int heads, int channels, const float* att_src, const float* att_dst,
+                                   const int64_t* edges, const int32_t* node_off, const int32_t* edge_off, int G, int nmax, float* dH,
+                                   float* d_att_src, float* d_att_dst, const uint8_t* complete, void* stream) {
+    int rc = check_hc(heads, channels, "sga_gat_attn_bwd_hc");
+    if (rc) return rc;
+    rc = check_common(G, nmax, "sga_gat_attn_bwd_hc");
+    if (rc) return rc;
+    SGA_CHECK_ARG(((G == 0 || nmax == 0) || (H && dO && node_off && edge_off && dH)) && att_src && att_dst && d_att_src && d_att_dst, "sga_gat_attn_bwd_hc: null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t hc = (size_t)heads * channels;
+    if (d_att_dst == d_att_src + hc) {                                // one flat buffer: one launch
+        hipMemsetAsync(d_att_src, 0, 2 * hc * sizeof(float), s);
+    } else {
+        hipMemsetAsync(d_att_src, 0, hc * sizeof(float), s);
+        hipMemsetAsync(d_att_dst, 0, hc * sizeof(float), s);
+    }
+    if (G == 0 || nmax == 0) return SGA_OK;
+    const int nj = gat_nj(nmax), cj = (channels + 63) / 64;
+    const bool ldsf = gat_fits_lds(nmax, true, channels);
+    const size_t lds = gat_lds_bytes_hc(nmax, true, channels, ldsf);
+    GAT_HC_DISPATCH(launch_bwd_hc, lds, G, heads, s, H, dO, att_src, att_dst, reinterpret_cast<const long long*>(edges), node_off, edge_off,
+                    dH, d_att_src, d_att_dst, nmax, channels, complete);
+    SGA_CHECK_LAUNCH("sga_gat_attn_bwd_hc");
+    return SGA_OK;
+}

@@ -171,3 +171,121 @@ class MultiGATFn(torch.autograd.Function):
 def multi_gat(gb, x, layer0, layer1):
     """layer = (lin_weight, att_src, att_dst, bias)."""
     return MultiGATFn.apply(gb, x, *layer0, *layer1)
+
+
+# ------------------------------------------------------------------------------------------ GAT, any stack
+def gat_lds_nodes(channels, bwd=False):
+    """Largest nodes-per-graph for which a head's [N, channels] features stay LDS-resident in the general attention kernels."""
+    n = _lib.lib().sga_gat_lds_nodes(int(channels), int(bool(bwd)))
+    if n < 0:
+        _lib.check(1, 'sga_gat_lds_nodes')
+    return n
+
+
+def _attn_fwd_hc(h, heads, channels, att_s, att_d, bias, gb, check_status=False):
+    """_attn_fwd for `heads` heads of `channels` channels (h [T, heads * channels], head-major) on the general kernels."""
+    out = torch.empty_like(h)
+    st = None
+    if check_status and _o.VALIDATE:
+        st = torch.zeros((1,), device=h.device, dtype=torch.int32)
+    complete = getattr(gb, 'complete', None)
+    ev = _ev_start()
+    _lib.check(_lib.lib().sga_gat_attn_fwd_hc(_p(h), heads, channels, _p(att_s), _p(att_d), _p(bias), _p(gb.edges), _p(gb.node_off),
+                                              _p(gb.edge_off), gb.G, gb.nmax, _p(out), _p(st), _p(complete), _stream()), 'sga_gat_attn_fwd_hc')
+    _ev_stop(ev, 'gat_attn_fwd_hc', (int(h.shape[0]), int(gb.edges.shape[0]), heads, channels, complete is not None))
+    if st is not None:
+        DEFERRED_CHECKS.submit_fn(st, _gat_status_verdict)
+    return out
+
+
+def _attn_bwd_hc(h, d_o, heads, channels, att_s, att_d, gb):
+    dh = torch.empty_like(h)
+    dboth = torch.empty((2,) + tuple(att_s.shape), device=att_s.device, dtype=att_s.dtype)      # adjacent: zeroed in one launch
+    das, dad = dboth[0], dboth[1]
+    complete = getattr(gb, 'complete', None)
+    ev = _ev_start()
+    _lib.check(_lib.lib().sga_gat_attn_bwd_hc(_p(h), _p(d_o), heads, channels, _p(att_s), _p(att_d), _p(gb.edges), _p(gb.node_off),
+                                              _p(gb.edge_off), gb.G, gb.nmax, _p(dh), _p(das), _p(dad), _p(complete), _stream()),
+               'sga_gat_attn_bwd_hc')
+    _ev_stop(ev, 'gat_attn_bwd_hc', (int(h.shape[0]), int(gb.edges.shape[0]), heads, channels, complete is not None))
+    return dh, das, dad
+
+
+class GATLayerFn(torch.autograd.Function):
+    """One GATConv(in, channels, heads) over ALL graphs of a batch: the projection on the GEMM, then the general attention kernels.
+    att_src / att_dst are PyG's [1, heads, channels].  The input gets a gradient only where it asks for one (not the first layer's)."""
+
+    @staticmethod
+    def forward(ctx, gb, x, w, att_s, att_d, bias, check_status):
+        if not x.is_cuda:
+            raise RuntimeError('sgaligner_amd.GATLayerFn: HIP device tensor required; there is no CPU path')
+        if att_s.dim() != 3 or att_s.shape != att_d.shape:
+            raise RuntimeError(f'sgaligner_amd: att_src / att_dst must be [1, heads, channels], got {tuple(att_s.shape)} / {tuple(att_d.shape)}')
+        heads, channels = int(att_s.shape[1]), int(att_s.shape[2])
+        hc = heads * channels
+        x = _req(x.contiguous(), 'gat.x')
+        w, asf, adf, bias = [_req(t.contiguous(), n) for t, n in ((w, 'gat.lin'), (att_s.reshape(-1), 'gat.att_src'),
+                                                                  (att_d.reshape(-1), 'gat.att_dst'), (bias, 'gat.bias'))]
+        t, f = int(x.shape[0]), int(x.shape[1])
+        if t != gb.T:
+            raise RuntimeError(f'sgaligner_amd: the GAT input has {t} rows but the graphs hold {gb.T} nodes')
+        if tuple(w.shape) != (hc, f) or bias.numel() != hc:
+            raise RuntimeError(f'sgaligner_amd: GATConv({f}, {channels}, heads={heads}) needs lin [{hc}, {f}] and bias [{hc}], '
+                               f'got {tuple(w.shape)} and {tuple(bias.shape)}')
+        h = gemm(x, w, False, True, t, hc, f)
+        out = _attn_fwd_hc(h, heads, channels, asf, adf, bias, gb, check_status=check_status)
+        ctx.gb, ctx.hc, ctx.att_shape = gb, (heads, channels), tuple(att_s.shape)
+        ctx.save_for_backward(x, h, w, asf, adf)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_o):
+        x, h, w, asf, adf = ctx.saved_tensors
+        heads, channels = ctx.hc
+        hc, (t, f) = heads * channels, x.shape
+        d_o = d_o.contiguous()
+        dh, das, dad = _attn_bwd_hc(h, d_o, heads, channels, asf, adf, ctx.gb)
+        db = colsum(d_o)
+        dw = gemm(dh, x, True, False, hc, f, t)
+        dx = gemm(dh, w, False, False, t, f, hc) if ctx.needs_input_grad[1] else None
+        return None, dx, dw, das.reshape(ctx.att_shape), dad.reshape(ctx.att_shape), db, None
+
+
+class EluFn(torch.autograd.Function):
+    """F.elu between the layers (gat.py:45-46) on sga_elu_fwd / sga_elu_bwd."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        ctx.save_for_backward(x)
+        return _elu(x)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, = ctx.saved_tensors
+        gy = gy.contiguous()
+        gx = torch.empty_like(x)
+        _lib.check(_lib.lib().sga_elu_bwd(_p(x), _p(gy), _p(gx), x.numel(), _stream()), 'sga_elu_bwd')
+        return gx
+
+
+def multi_gat_layers(gb, x, layers, p=0.0, training=False, masks=None):
+    """MultiGAT.forward (gat.py:40-48) for a stack of any depth: dropout on the input of every layer, GATConv, ELU between layers.
+    layers: (lin_weight, att_src [1, H, C], att_dst, bias) per layer.  masks: one [T, in_width] tensor per layer, already scaled by
+    1 / (1 - p) -- it replaces the draw; otherwise, training with p > 0, torch.nn.functional.dropout draws once per layer in layer order."""
+    if not x.is_cuda:
+        raise RuntimeError('sgaligner_amd.multi_gat_layers: HIP device tensor required; there is no CPU path')
+    if x.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f'sgaligner_amd.multi_gat_layers: tot_rel_pose must be float32 or float64, got {x.dtype}')
+    if masks is not None and len(masks) != len(layers):
+        raise RuntimeError(f'sgaligner_amd.multi_gat_layers: {len(masks)} dropout masks for {len(layers)} layers')
+    x = cast_f32(x.contiguous())
+    for i, layer in enumerate(layers):
+        if masks is not None:
+            x = x * masks[i]
+        elif training and p > 0.0:
+            x = torch.nn.functional.dropout(x, p, True)
+        x = GATLayerFn.apply(gb, x, *layer, i == 0)          # every layer sees the same edge list: one multiplicity check per batch
+        if i + 1 < len(layers):
+            x = EluFn.apply(x)
+    return x
