@@ -248,6 +248,30 @@ struct TArgs {
     double* gamma;                   // GRAD out [M] (+ slots)
 };
 
+// S3_PAIR (default 1): the S phase runs its 2 M sub-steps in PAIRS whose 40 MFMAs strictly alternate between the two sub-steps, each sub-step
+// accumulating its 20 products into ONE chain (same products, same order: tails | l h | m m | m h | h l | h m | h h).  Consecutive MFMAs
+// still never share an accumulator -- which is all the two chains per sub-step of the earlier form were for -- but nothing has to be read
+// out of a second chain and merged: per sub-step four accumulator reads and four v_add_f32 less.  -DS3_PAIR=0 builds the two-chain form
+// (timing and bisecting); -DS3_PAIR=2 pairs every instantiation that fits its register budget, whatever the per-form defaults below.
+#ifndef S3_PAIR
+#define S3_PAIR 1
+#endif
+// The gaps of pair p of the paired stream (gap P = behind MFMA P, 0 .. 39) that may carry a coefficient step: not a copy's gap (pairs
+// 0 .. M - 2 carry the next tile's copies, one every 20 / PER gaps), not the first three (gap 0 and gap 2 read the finished pair's similarities).
+// slot[p][P] = running index of the free gap, -1 = not free.
+template <int M, int PER> struct S3PairGaps {
+    int slot[M][40];
+    constexpr S3PairGaps() : slot{} {
+        for (int p = 0; p < M; ++p) {
+            int n = 0;
+            for (int P = 0; P < 40; ++P) {
+                const bool copy = p < M - 1 && P % (20 / PER) == 1 && P / (20 / PER) < 2 * PER;
+                slot[p][P] = (P >= 3 && !copy) ? n++ : -1;
+            }
+        }
+    }
+};
+
 // WV: waves per workgroup, each owning 16 owner rows.  8: two waves per SIMD (<= 256 registers), operands requested at the top of a
 // sub-step and covered by the partner wave.  4: one wave per SIMD (<= 512 registers), PIPE: operands requested a group of MFMAs ahead.
 // MG (gradient sweep): the number of tables whose owner gradient THIS launch accumulates -- the first MG of the M tables; the others only
@@ -288,6 +312,16 @@ __device__ __forceinline__ void sweep3_body(const TArgs& a, const int g) {
     // two sub-steps; the own part of the LAST sub-step runs under the first table's gradient MFMAs.  Left between the phases: the joint
     // coefficient of half 1 and the first table's split.
     constexpr bool SPREAD = OWN_IN_S && S3_SPREAD && !FOLD;      // (FOLD, M = 4: the register file is full)
+    // PAIR: see S3_PAIR.  Not the full (all six products) M = 3 forward sums: two waves per SIMD, 223 registers with one operand set, and a
+    // pair needs both sub-steps' operands at once (+40) -- it keeps two chains per sub-step.
+    constexpr bool PAIR_FITS = !(!GRAD && WV == 8 && M == 3 && !LITE);
+    // Per-form default (S3_PAIR = 1), each form measured on its own.  Not the M = 2 gradient sweep: measured within the noise of
+    // the two-chain form.  (A reading of the listing, not a measurement: its last pair holds table 0's second half, whose own coefficient
+    // part the first table's split needs at once, so it runs between the phases and may spend what the loop saves, 32 VALU.)  Nor the full
+    // M = 4 forward sums (one wave per SIMD, operands already requested a sub-step ahead): within the noise as well.  Those two paired forms
+    // are built by -DS3_PAIR=2 only and the default library's tests do not run them.
+    constexpr bool PAIR_DEFAULT = !(GRAD && M == 2) && !(!GRAD && M == 4 && !LITE);
+    constexpr bool PAIR = PAIR_FITS && (S3_PAIR == 2 || (S3_PAIR == 1 && PAIR_DEFAULT));
     extern __shared__ __attribute__((aligned(16))) unsigned char lds3[];      // [2][M][S3_BLOCK]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g4 = lane >> 4, l15 = lane & 15;
@@ -532,7 +566,7 @@ __device__ __forceinline__ void sweep3_body(const TArgs& a, const int g) {
             auto substep_wait = [&](int ss) {
                 if (ss > 0) { __builtin_amdgcn_s_waitcnt(0xc07f); __builtin_amdgcn_sched_barrier(0); }
             };
-            constexpr int NSET = PIPE ? 2 : 1;
+            constexpr int NSET = (PIPE || PAIR) ? 2 : 1;       // (PAIR: a pair reads both sets, sub-step a = set 0, b = set 1)
             u32x4 at[NSET], ap[NSET][3][3];                    // ap[.][0]: h, [1]: m, [2]: l
             auto ld_one = [&](int ss, int idx) {               // idx 0: the tail image; 1 + 3 p' + q: plane l, m, h (p' = 0, 1, 2) K step q
                 const int e = ss % NSET;
@@ -546,10 +580,106 @@ __device__ __forceinline__ void sweep3_body(const TArgs& a, const int g) {
             };
             if (PIPE) {
                 ld_set(0);
+                if (PAIR) ld_set(1);
                 __builtin_amdgcn_s_waitcnt(0xc07f);            // lgkmcnt(0) HERE, not behind the requests of set 1 (see above)
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if constexpr (SPREAD) {
+            // lgkmcnt(n): every LDS read but the youngest n has arrived (LDS reads return in order; the copies count on vmcnt)
+            auto lgkm_wait = [&](int n) {                      // (the builtin takes a literal: lgkmcnt = bits 8 .. 11)
+                if (n == 0) __builtin_amdgcn_s_waitcnt(0xc07f);
+                else if (n == 6) __builtin_amdgcn_s_waitcnt(0xc67f);
+                else if (n == 8) __builtin_amdgcn_s_waitcnt(0xc87f);
+                else __builtin_amdgcn_s_waitcnt(0xce7f);       // 14
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            if constexpr (SPREAD && PAIR) {
+                // The paired stream, positions P = 0 .. 39 of pair p: sub-step a = 2 p on the even, b = 2 p + 1 on the odd positions (half-major
+                // order as below: sub-step ss = (half ss / M, table ss % M); for M = 3 pair 1 straddles the two halves), product x = P / 2.
+                // Operand registers: a reads set 0, b set 1; each operand of the NEXT pair is requested behind the last MFMA of this pair that reads
+                // its register -- the tail image in gaps 2, 3, the l planes in 4 .. 9, m in 16 .. 21, h in 34 .. 39: >= 20 MFMAs before its first
+                // reader.  Two waits per pair, each where the youngest request it retires is >= 19 MFMAs old: at the top everything but the
+                // six h requests, in front of position 22 (the first h product) those six -- the 14 requests of gaps 2 .. 21 stay in flight.
+                // Gaps: the next tile's copies every 20 / PER gaps of the first M - 1 pairs; gap 0 / gap 2 read the similarities of the finished
+                // pair's a / b (four registers each, once); from gap 3 on the free gaps carry, one step each and at most one transcendental per
+                // gap, the finished pair's own coefficient parts (r = 0 .. 3: a's three steps, then b's) and, in the last pair, the joint coefficient
+                // of half 0 in every third free gap (its M similarities are sub-steps 0 .. M - 1 <= 2 M - 3: read by gap 2 of the last pair).
+                // Left behind the loop: the last pair's similarities, whose own parts run under the first table's gradient MFMAs (own_last).
+                constexpr int NDS = 2 * M - 2, PER = (M * KMAX + NDS - 1) / NDS, CS = 20 / PER;
+                static_assert(2 * PER * CS <= 40 && (M - 1) * 2 * PER >= M * KMAX, "paired S stream: the copies' gaps");
+                constexpr int PA[6] = {2, 1, 1, 0, 0, 0}, PB[6] = {0, 1, 0, 2, 1, 0};
+                constexpr S3PairGaps<M, PER> GAPS{};
+                f32x4 accq[2][2];                              // [pair parity][a, b]: ONE chain per sub-step
+                float ot0 = 0.f, ot1 = 0.f, sjt = 0.f, ce0 = 0.f, ce1 = 0.f;
+                auto own_step = [&](int ss, int r, int k) {
+                    const int mm = ss % M, hh = ss / M;
+                    if (mm >= MG) return;
+                    const float sv = sacc[mm][hh][r];
+                    if (k == 0) ot0 = fexp2(sv * ka);
+                    else if (k == 1) ot1 = fexp2(sv);
+                    else own[mm][hh][r] = fmaf(c0[mm], ot0, c1[mm] * ot1);
+                };
+                auto cj_step = [&](int hh, int r, int k) {
+                    if (k == 0) {
+                        sjt = 0.f;
+#pragma unroll
+                        for (int mm = 0; mm < M; ++mm) sjt = fmaf(beta[mm], sacc[mm][hh][r], sjt);
+                    } else if (k == 1) ce0 = fexp2(sjt * ka);
+                    else if (k == 2) ce1 = fexp2(sjt);
+                    else cj[hh][r] = c0[M] * ce0 + c1[M] * ce1;
+                };
+                auto read_s = [&](int ss, const f32x4& acc) {  // a finished chain -> the similarities' registers, HERE (one read per value)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float v = acc[r];
+                        asm volatile("" : "+v"(v));
+                        sacc[ss % M][ss / M][r] = v;
+                    }
+                };
+#pragma unroll
+                for (int p = 0; p < M; ++p) {
+                    const int pp = p & 1;
+                    const bool nxt = p + 1 < M;
+                    accq[pp][0] = f32x4{0.f, 0.f, 0.f, 0.f}; accq[pp][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (p > 0) lgkm_wait(6);
+#pragma unroll
+                    for (int P = 0; P < 40; ++P) {
+                        const int x = P >> 1, s = P & 1, m = (2 * p + s) % M;
+                        if (x == 0) accq[pp][s] = mfma_b(at[s], otl[m][1], accq[pp][s]);
+                        else if (x == 1) accq[pp][s] = mfma_b(at[s], otl[m][0], accq[pp][s]);
+                        else accq[pp][s] = mfma_b(ap[s][PA[(x - 2) / 3]][(x - 2) % 3], opl[m][PB[(x - 2) / 3]][(x - 2) % 3], accq[pp][s]);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (nxt) {
+                            const int sn = 2 * p + 2 + s;
+                            if (P >= 2 && P < 4) ld_one(sn, 0);
+                            else if (P >= 4 && P < 10) ld_one(sn, 1 + (P - 4) / 2);
+                            else if (P >= 16 && P < 22) ld_one(sn, 4 + (P - 16) / 2);
+                            else if (P >= 34) ld_one(sn, 7 + (P - 34) / 2);
+                        }
+                        if (p < M - 1 && (P % CS) == 1 && P / CS < 2 * PER) issue_slots(p * 2 * PER + P / CS, p * 2 * PER + P / CS + 1);
+                        if (p > 0) {
+                            if (P == 0) read_s(2 * p - 2, accq[pp ^ 1][0]);
+                            if (P == 2) read_s(2 * p - 1, accq[pp ^ 1][1]);
+                            const int fs = GAPS.slot[p][P];
+                            if (fs >= 0) {
+                                // own steps t = 0 .. 23: (r, a / b, k) = (t / 6, (t / 3) % 2, t % 3); last pair: two own steps, then one joint step
+                                const int t = nxt ? fs : (fs % 3 < 2 ? 2 * (fs / 3) + fs % 3 : -1);
+                                const int qq = (!nxt && fs % 3 == 2) ? fs / 3 : -1;
+                                if (t >= 0 && t < 24) own_step(2 * p - 2 + ((t / 3) & 1), t / 6, t % 3);
+                                if (qq >= 0 && qq < 12) {
+                                    const int r = qq / 3, k = qq % 3;
+                                    if (k == 0) { if (r > 0) cj_step(0, r - 1, 3); cj_step(0, r, 0); }
+                                    else cj_step(0, r, k);
+                                }
+                            }
+                            if (P == 21) lgkm_wait(nxt ? 14 : 0);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+                read_s(2 * M - 2, accq[(M - 1) & 1][0]);
+                read_s(2 * M - 1, accq[(M - 1) & 1][1]);
+                cj_step(0, 3, 3);
+            } else if constexpr (SPREAD) {
                 constexpr int NDS = 2 * M - 2, PER = (M * KMAX + NDS - 1) / NDS;
                 constexpr int PA[6] = {2, 1, 1, 0, 0, 0}, PB[6] = {0, 1, 0, 2, 1, 0};
                 f32x4 accp[2][2];                              // a sub-step's two chains; added up in the NEXT sub-step's first gaps (behind the MFMAs' latency)
@@ -614,6 +744,59 @@ __device__ __forceinline__ void sweep3_body(const TArgs& a, const int g) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) sacc[M - 1][1][r] = accp[(2 * M - 1) & 1][0][r] + accp[(2 * M - 1) & 1][1][r];
                 cj_step(0, 3, 3);
+            } else if constexpr (PAIR) {
+                // Table-major order: a pair = the two halves of ONE table (sub-steps 2 m, 2 m + 1: the same owner operands), positions and
+                // operand requests as in the SPREAD form above.  Two waves per SIMD (!PIPE): both sub-steps' operands are requested at the
+                // top of the pair (two register sets instead of one) and the compiler counts the waits.
+                constexpr int NDS = GRAD ? (2 * M - 2) : 2 * M, PER = (M * KMAX + NDS - 1) / NDS, CS = 20 / PER;
+                static_assert(!PIPE || (2 * PER * CS <= 40 && (NDS / 2) * 2 * PER >= M * KMAX), "paired S stream: the copies' gaps");
+                constexpr int PA[6] = {2, 1, 1, 0, 0, 0}, PB[6] = {0, 1, 0, 2, 1, 0};
+#pragma unroll
+                for (int m = 0; m < M; ++m) {
+                    const bool nxt = m + 1 < M;
+                    if (!PIPE) { ld_set(2 * m); ld_set(2 * m + 1); }
+                    if (PIPE && m > 0) lgkm_wait(6);
+                    f32x4 accq[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};     // ONE chain per sub-step
+                    float ownt[2] = {0.f, 0.f};
+#pragma unroll
+                    for (int P = 0; P < 40; ++P) {
+                        const int x = P >> 1, s = P & 1;
+                        // LITE: h h + h m + m h and the K tail only (see the two-chain form below)
+                        const bool skip = LITE && x >= 2 && (PA[(x - 2) / 3] == 2 || PB[(x - 2) / 3] == 2 || (PA[(x - 2) / 3] == 1 && PB[(x - 2) / 3] == 1));
+                        if (skip) {}
+                        else if (x == 0) accq[s] = mfma_b(at[s], otl[m][1], accq[s]);
+                        else if (x == 1) accq[s] = mfma_b(at[s], otl[m][0], accq[s]);
+                        else accq[s] = mfma_b(ap[s][PA[(x - 2) / 3]][(x - 2) % 3], opl[m][PB[(x - 2) / 3]][(x - 2) % 3], accq[s]);
+                        if (PIPE) {
+                            __builtin_amdgcn_sched_barrier(0);
+                            if (nxt) {
+                                const int sn = 2 * m + 2 + s;
+                                if (P >= 2 && P < 4) ld_one(sn, 0);
+                                else if (P >= 4 && P < 10) { if (!LITE) ld_one(sn, 1 + (P - 4) / 2); }
+                                else if (P >= 16 && P < 22) ld_one(sn, 4 + (P - 16) / 2);
+                                else if (P >= 34) ld_one(sn, 7 + (P - 34) / 2);
+                            }
+                            if (m < NDS / 2 && (P % CS) == 1 && P / CS < 2 * PER) issue_slots(m * 2 * PER + P / CS, m * 2 * PER + P / CS + 1);
+                            // the previous table's own coefficient part (both halves) under this table's MFMAs: three VALU per gap 22 .. 37
+                            if (OWN_IN_S && m > 0 && m - 1 < MG && P >= 22 && P < 38) {
+                                const int r8 = (P - 22) >> 1;
+                                const float sv = sacc[m - 1][r8 >> 2][r8 & 3];
+                                if (((P - 22) & 1) == 0) {
+                                    ownt[0] = fexp2(sv * ka);
+                                    ownt[1] = fexp2(sv);
+                                } else {
+                                    own[m - 1][r8 >> 2][r8 & 3] = fmaf(c0[m - 1], ownt[0], c1[m - 1] * ownt[1]);
+                                }
+                            }
+                            if (m > 0 && P == 21) lgkm_wait(nxt ? (LITE ? 8 : 14) : 0);
+                            __builtin_amdgcn_sched_barrier(0);
+                        } else if (P == 1 && m < NDS / 2) {
+                            issue_slots(2 * m * PER, (2 * m + 2) * PER);
+                        }
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { sacc[m][0][r] = accq[0][r]; sacc[m][1][r] = accq[1][r]; }
+                }
             } else {
 #pragma unroll
             for (int ss = 0; ss < 2 * M; ++ss) {
@@ -724,13 +907,21 @@ __device__ __forceinline__ void sweep3_body(const TArgs& a, const int g) {
                     }
                 };
                 // own coefficient parts not computed under the S phase's MFMAs: the last table's (PIPE), all of them otherwise
-                auto own_last = [&]() {                         // SPREAD: the last sub-step's own part (table M - 1, half 1) -- under the first table's gradient MFMAs
+                // SPREAD: the own parts the S phase left over -- the last sub-step's (table M - 1, half 1); PAIR: the last PAIR's (tables M - 2 and
+                // M - 1, half 1) -- under the first table's gradient MFMAs.  (PAIR, M = 2: table 0's is needed by the first split: between the phases.)
+                constexpr int OWN_LAST0 = (SPREAD && PAIR) ? (M > 2 ? M - 2 : 1) : M - 1;
+                auto own_late = [&](int mm) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const float sv = sacc[M - 1][1][r];
-                        own[M - 1][1][r] = fmaf(c0[M - 1], fexp2(sv * ka), c1[M - 1] * fexp2(sv));
+                        const float sv = sacc[mm][1][r];
+                        own[mm][1][r] = fmaf(c0[mm], fexp2(sv * ka), c1[mm] * fexp2(sv));
                     }
                 };
+                auto own_last = [&]() {
+#pragma unroll
+                    for (int mm = OWN_LAST0; mm < M; ++mm) if (mm < MG) own_late(mm);
+                };
+                if (SPREAD && PAIR && M == 2) own_late(0);
 #pragma unroll
                 for (int m = SPREAD ? M : OWN_IN_S ? M - 1 : 0; m < MG; ++m)
 #pragma unroll
@@ -824,7 +1015,7 @@ __device__ __forceinline__ void sweep3_body(const TArgs& a, const int g) {
 #pragma unroll
                     for (int g4i = 0; g4i < 4 * MG; ++g4i) {
                         const int m = g4i >> 2, ct0 = (g4i & 3) * 2, n = (g4i & 3) == 3 ? 1 : 2, k0_ = NCT * m + ct0;
-                        if (SPREAD && g4i == 0 && M - 1 < MG && M > 1) own_last();
+                        if (SPREAD && g4i == 0 && OWN_LAST0 < MG && M > 1) own_last();
                         if ((g4i & 3) == 0 && m + 1 < MG) planes(m + 1);       // source order only: spread under this table's MFMAs below
                         if (GAM && !FOLD && g4i == (MG > 1 ? 4 : 0)) gamma_acc();   // ... and Gamma under the second table's (the first carries planes(1))
                         if (FOLD && g4i >= 2) fold_group(g4i - 2);             // (its MFMAs finished a group ago)
