@@ -2,7 +2,12 @@
 
 Part of the autograd layer over the C-ABI HIP kernels (see ops.py, which re-exports everything here: `sgaligner_amd.ops.<name>` keeps
 working).  The run-time switches live in ops.py and are read through the module at call time (`_o.FLAG`), so `ops.FLAG = value` set by a
-caller or a test takes effect here."""
+caller or a test takes effect here.
+
+FusedContrastiveFn runs in one of three arithmetic tiers, and a tier is defined in ONE place, its class in TIERS: the table images, the entry
+points and operands of the five stages that differ (images, forward sums, stash products, gradient sweep, scatter) and what backward needs
+saved.  forward(), backward() and _aa_walk only call its methods, and tests/loss_gate.py launches through the same object.  A new tier is one
+more class and one more name where forward() chooses; a new anchors x anchors kernel is a change to the stash() of the tier it serves."""
 from __future__ import annotations
 
 import ctypes as _ct
@@ -458,7 +463,115 @@ def _allreduce_sum(t, group_reduce):
     return t
 
 
-def _aa_walk(s, zs, zbs, zcs, tier, beta, sums, alpha, coef, dzs, walk, sym, out=None):
+def _call(name, *args):
+    """One launch at the C ABI on torch's current stream, checked under the entry point's own name."""
+    _lib.check(getattr(_lib.lib(), name)(*args, _stream()), name)
+
+
+class PlainTier:
+    """Tier 'plain': fp32 MFMA over the packed tables zs [R + 32, 104] themselves, for tables wider than 100 columns.  No images; the
+    gradient of the unit rows comes in one part.  Also the base of the other tiers: a tier is its images (plain attributes, one tensor per
+    table), the entry points of its stages and their operands; every stage takes its output buffers as arguments."""
+    images, FILL = (), None                       # names of the image lists, as FILL's outputs and saved() order them | the entry point that fills them
+    sweep_on, stash_on = 'zs', 'zs'               # the tables the sweeps read | the B operand of the fp32 stash products
+    SUMS, GRAD = ('sga_loss_multi_sums', 'loss_multi_sums'), ('sga_loss_multi_grad', 'loss_multi_grad')      # (entry point, ops.KERNEL_EVENTS key)
+
+    def __init__(self, s, zs, dmax, saved=None):
+        """dmax: the tables' real width (the K step that only covers zero padding is skipped).  saved: ctx.saved_tensors from saved()'s
+        first tensor on, in backward, in place of fresh image buffers."""
+        self.s, self.zs, self.dmax, self.M, self.geom = s, list(zs), dmax, len(zs), (s.A, s.J1, s.J2)
+        if saved is None:
+            self.alloc()
+        else:
+            for i, name in enumerate(self.images):
+                setattr(self, name, list(saved[i * self.M:(i + 1) * self.M]))
+
+    def saved(self):
+        return [t for name in self.images for t in getattr(self, name)]
+
+    def alloc(self):
+        """The image buffers, their slack rows zeroed."""
+
+    def prepare(self):
+        """Fill the images from zs: once per step."""
+        for k, z in enumerate(self.zs if self.FILL else ()):
+            _call(self.FILL, _p(z), *self.geom, *(_p(getattr(self, name)[k]) for name in self.images))
+
+    def _sweep(self, entry, event, beta, io, a_lo, a_hi, *tail):
+        width = (self.dmax,) if self.sweep_on == 'zs' else ()          # only the packed tables carry zero padding to skip
+        ev = _ev_start()
+        _call(entry, _ptr_array(getattr(self, self.sweep_on)), self.M, *width, _p(beta), *self.geom, TAU_ICL, TAU_IAL, *io, a_lo, a_hi, *tail)
+        _ev_stop(ev, event, (a_hi - a_lo, *self.geom, self.M, *map(bool, tail)))
+
+    def sums(self, beta, sums, a_lo, a_hi):
+        """The global sums over the anchors [a_lo, a_hi) x all negatives, into sums [slots, M + 1, 8]."""
+        self._sweep(*self.SUMS, beta, (_p(sums),), a_lo, a_hi)
+
+    def grad(self, beta, gs, dzs, gam_neg, a_lo, a_hi):
+        """The negatives' gradient sweep: dL/dZ added into dzs[m], dL/dbeta through the negatives into gam_neg [slots, M]."""
+        self._sweep(*self.GRAD, beta, (_p(gs), _ptr_array(dzs), _p(gam_neg)), a_lo, a_hi)
+
+    def stash(self, k, m1, m2, dz, job, sym):
+        """Table k's stash products of one launch job = (lo, hi, j_lo, j_hi, mir) of the A x A walk, added into dz:
+        dX1[i] = sum_j G[i,j] X2[j]  (M1 = G^T),  dX2[j] = sum_i G[i,j] X1[i].  m2: a symmetric launch's mirrored stash, or None."""
+        b = _p(getattr(self, self.stash_on)[k])
+        if sym:
+            _call('sga_loss_stash_grad_symx', _p(m1), _p(m2), b, self.s.A, 104, _p(dz), *job)
+        else:
+            _call('sga_loss_stash_grad', _p(m1), b, self.s.A, 104, _p(dz), *job[:2])
+
+    def scatter(self, k, dz, nrm, d, de):
+        """dE [T, d] of table k from the gradient dz of its unit rows."""
+        _call('sga_loss_scatter', _p(dz), _p(self.zs[k]), _p(nrm), _p(self.s.idx), self.s.R, d, 104, _p(de))
+
+
+class CentredTier(PlainTier):
+    """Tier 'centred' (mode 'f32'): fp32 MFMA over the centred fp32 tables zc = (z - zbar | b | 1), with a statistics block per table.  The
+    gradient comes in two parts (sum c (z - zbar) | sum c), as in the three-plane tier; the bookkeeping sits in columns 100 and 101."""
+    images, FILL, sweep_on, stash_on = ('zc', 'stat'), 'sga_loss_centre_tables', 'zc', 'zc'
+    SUMS, GRAD = ('sga_loss_multi_sums_centred', 'loss_multi_sums'), ('sga_loss_multi_grad_centred', 'loss_multi_grad')
+
+    def alloc(self):
+        dev, nst = self.zs[0].device, int(_lib.lib().sga_loss_centre_bytes())
+        self.stat = [torch.empty((nst,), device=dev, dtype=torch.uint8) for _ in self.zs]
+        self.zc = [torch.empty((self.s.R + 32, 104), device=dev, dtype=torch.float32) for _ in self.zs]
+        for zc in self.zc:
+            zc[self.s.R:].zero_()
+
+    def scatter(self, k, dz, nrm, d, de):
+        _call('sga_loss_scatter_tangent_stat', _p(dz), _p(self.zs[k]), _p(nrm), _p(self.s.idx), self.s.R, d, _p(self.stat[k]), _p(de))
+
+
+class PlanesTier(PlainTier):
+    """Tier 'planes' (mode 'bf16x6', the default): three exact bf16 planes per table (csrc/sweep3.hip), the blocked h / m / l planes of the
+    centred rows, + the anchor rows as fp32 z - zbar with a ones column, zc: the fp32 stash products' B operand (gradient in two parts)."""
+    images, FILL, sweep_on, stash_on = ('planes', 'zc'), 'sga_loss_split3_tables', 'planes', 'zc'
+    SUMS, GRAD = ('sga_loss_multi_sums_bf16x6', 'loss_multi_sums_bf16x6'), ('sga_loss_multi_grad_bf16x6', 'loss_multi_grad_bf16x6')
+
+    def alloc(self):
+        dev, nb = self.zs[0].device, _lib.lib().sga_loss_split3_bytes(*self.geom)
+        self.planes = [torch.empty((nb,), device=dev, dtype=torch.uint8) for _ in self.zs]
+        self.zc = [torch.empty((2 * self.s.A + 32, 104), device=dev, dtype=torch.float32) for _ in self.zs]
+        for zc in self.zc:
+            zc[2 * self.s.A:].zero_()
+
+    def sums(self, beta, sums, a_lo, a_hi):
+        self._sweep(*self.SUMS, beta, (_p(sums),), a_lo, a_hi, 1 if _sums_lite(a_hi - a_lo, *self.geom[1:]) else 0)
+
+    def stash(self, k, m1, m2, dz, job, sym):
+        if not _o.BF16X6_STASH:
+            return super().stash(k, m1, m2, dz, job, sym)
+        # the four stash products on the sweeps' three exact bf16 planes (csrc/sweep3.hip: stash3_kernel), on ordered walks too
+        _call('sga_loss_stash_grad_symx_bf16x6', _p(m1), _p(m2), _p(self.planes[k]), *self.geom, _p(dz), *job)
+
+    def scatter(self, k, dz, nrm, d, de):            # the two parts are projected without forming their sum
+        _call('sga_loss_scatter_tangent', _p(dz), _p(self.zs[k]), _p(nrm), _p(self.s.idx), *self.geom, d, _p(self.planes[k]), _p(de))
+
+
+TIERS = {'plain': PlainTier, 'centred': CentredTier, 'planes': PlanesTier}
+
+
+def _aa_walk(s, tier, beta, sums, alpha, coef, dzs, walk, sym, out=None):
     """The anchors x anchors backward of FusedContrastiveFn, one anchor-row block at a time: the kernel writes the block's transposed
     coefficient stashes (dL/dS_m + beta_m dL/dS_J, no joint stash), the tier's stash products add dL/dZ into dzs[m], the next block reuses
     the buffers -- memory O(A*D + _o.STASH_BYTES), never A x A (nothing of that size at configs[2]).  walk: _sym_jobs launches
@@ -466,8 +579,8 @@ def _aa_walk(s, zs, zbs, zcs, tier, beta, sums, alpha, coef, dzs, walk, sym, out
     _anchor_chunks blocks (lo, hi).  out: the launch's term buffer when the term values are wanted from the same launches (one-pass forward).
     Returns (terms, gs, gamma) summed over the blocks; terms is empty without `out`."""
     L = _lib.lib()
-    M, A, nt = len(zs), s.A, len(zs) + 1
-    dev, st = sums.device, _stream()
+    M, A, nt = tier.M, s.A, tier.M + 1
+    dev = sums.device
     slots = 1 + L.sga_loss_slots()
     n_terms = nt + 2 * M if out is not None else 0
     zz = torch.zeros((n_terms + nt * 8 + M,), device=dev, dtype=torch.float64)      # terms | gs | gamma: one fill
@@ -479,34 +592,23 @@ def _aa_walk(s, zs, zbs, zcs, tier, beta, sums, alpha, coef, dzs, walk, sym, out
     gam2 = torch.empty((slots, M), device=dev, dtype=torch.float64)
     fl = max(((jh - jl) + max(0, jh - mir)) * (hi - lo) for lo, hi, jl, jh, mir in jobs)
     buf = [torch.empty((fl,), device=dev, dtype=torch.float32) for _ in range(M)]
-    zarr = _ptr_array(zs)
-    zop = zs if tier == 'plain' else zcs              # B operand of the fp32 stash products
+    zarr = _ptr_array(tier.zs)
     for lo, hi, jl, jh, mir in jobs:
         n1 = (jh - jl) * (hi - lo)
         m1, m2 = [b[:n1] for b in buf], [b[n1:] for b in buf]
         has2 = mir < jh
         if sym:
-            _lib.check(L.sga_loss_anchor_multi_bwd_symx(zarr, M, _p(beta), A, _p(sums), alpha, TAU_ICL, TAU_IAL, _p(coef), _ptr_array(m1),
-                                                        _ptr_array(m2) if has2 else (_ct.c_void_p * M)(), _p(gsc), _p(gam2), lo, hi, jl, jh, mir,
-                                                        _p(out), st), 'sga_loss_anchor_multi_bwd_symx')
+            _call('sga_loss_anchor_multi_bwd_symx', zarr, M, _p(beta), A, _p(sums), alpha, TAU_ICL, TAU_IAL, _p(coef), _ptr_array(m1),
+                  _ptr_array(m2) if has2 else (_ct.c_void_p * M)(), _p(gsc), _p(gam2), lo, hi, jl, jh, mir, _p(out))
         else:
-            _lib.check(L.sga_loss_anchor_multi_bwd(zarr, M, _p(beta), A, _p(sums), alpha, TAU_ICL, TAU_IAL, _p(coef), _ptr_array(m1), _p(gsc),
-                                                   _p(gam2), lo, hi, _p(out), st), 'sga_loss_anchor_multi_bwd')
+            _call('sga_loss_anchor_multi_bwd', zarr, M, _p(beta), A, _p(sums), alpha, TAU_ICL, TAU_IAL, _p(coef), _ptr_array(m1), _p(gsc), _p(gam2),
+                  lo, hi, _p(out))
         if out is not None:
             terms += out[:n_terms]
         gs += gsc[0]
         gam += gam2[0]
         for k in range(M):
-            # dX1[i] = sum_j G[i,j] X2[j]  (M1 = G^T),  dX2[j] = sum_i G[i,j] X1[i]
-            if tier == 'planes' and _o.BF16X6_STASH:
-                # the four stash products on the sweeps' three exact bf16 planes (csrc/sweep3.hip: stash3_kernel)
-                _lib.check(L.sga_loss_stash_grad_symx_bf16x6(_p(m1[k]), _p(m2[k]) if has2 else None, _p(zbs[k]), A, s.J1, s.J2, _p(dzs[k]),
-                                                             lo, hi, jl, jh, mir, st), 'sga_loss_stash_grad_symx_bf16x6')
-            elif sym:
-                _lib.check(L.sga_loss_stash_grad_symx(_p(m1[k]), _p(m2[k]) if has2 else None, _p(zop[k]), A, 104, _p(dzs[k]), lo, hi, jl, jh, mir,
-                                                      st), 'sga_loss_stash_grad_symx')
-            else:
-                _lib.check(L.sga_loss_stash_grad(_p(m1[k]), _p(zop[k]), A, 104, _p(dzs[k]), lo, hi, st), 'sga_loss_stash_grad')
+            tier.stash(k, m1[k], m2[k] if has2 else None, dzs[k], (lo, hi, jl, jh, mir), sym)
     return terms, gs, gam
 
 
@@ -535,10 +637,6 @@ class FusedContrastiveFn(torch.autograd.Function):
         st = _stream()
         dp = 104
         dmax = max(e.shape[1] for e in tables)          # real width: the K step that only covers zero padding is skipped
-        # The arithmetic of the sweeps and the stash products: three exact bf16 planes ('planes'), or in mode 'f32' fp32 MFMA over centred
-        # tables ('centred') -- both deliver the gradient in two parts and keep their bookkeeping in columns 100 and 101 -- or, for tables
-        # wider than 100 columns, fp32 MFMA over the plain tables ('plain').
-        tier = 'plain' if dmax > 100 else 'centred' if get_mfma_mode() == 'f32' else 'planes'
         zs, nrms = [], []
         poison = torch.zeros((1,), device=dev, dtype=torch.float32)
         for k, e in enumerate(tables):
@@ -551,44 +649,11 @@ class FusedContrastiveFn(torch.autograd.Function):
             _lib.check(L.sga_loss_gather(_p(e), T, d, _p(s.idx), s.R, _p(z), dp, _p(nrm), st), 'sga_loss_gather')
             _lib.check(L.sga_loss_check_norms(_p(nrm), s.R, _p(poison), st), 'sga_loss_check_norms')
             zs.append(z); nrms.append(nrm)
-        zarr = _ptr_array(zs)
         slots = 1 + L.sga_loss_slots()
         sums = torch.empty((slots, nt, 8), device=dev, dtype=torch.float64)
-        zbs, zcs = [], []
-        if tier == 'planes':
-            # three exact bf16 planes per table (csrc/sweep3.hip): blocked h / m / l planes of the centred rows, once per step
-            nb = L.sga_loss_split3_bytes(s.A, s.J1, s.J2)
-            for z in zs:
-                zb = torch.empty((nb,), device=dev, dtype=torch.uint8)
-                # + the anchor rows as fp32 z - zbar with a ones column: the stash products' B operand (gradient in two parts, see
-                # sga_loss_scatter_tangent)
-                zc = torch.empty((2 * s.A + 32, dp), device=dev, dtype=torch.float32)
-                zc[2 * s.A:].zero_()
-                _lib.check(L.sga_loss_split3_tables(_p(z), s.A, s.J1, s.J2, _p(zb), _p(zc), st), 'sga_loss_split3_tables')
-                zbs.append(zb); zcs.append(zc)
-            ev = _ev_start()
-            lite = _sums_lite(a_hi - a_lo, s.J1, s.J2)
-            _lib.check(L.sga_loss_multi_sums_bf16x6(_ptr_array(zbs), M, _p(beta), s.A, s.J1, s.J2, TAU_ICL, TAU_IAL, _p(sums),
-                                                    a_lo, a_hi, 1 if lite else 0, st), 'sga_loss_multi_sums_bf16x6')
-            _ev_stop(ev, 'loss_multi_sums_bf16x6', (a_hi - a_lo, s.A, s.J1, s.J2, M, bool(lite)))
-        elif tier == 'centred':
-            # fp32-MFMA sweeps over the centred fp32 tables (z - zbar | b | 1): the gradient in the same two parts as the three-plane sweeps
-            nst = int(L.sga_loss_centre_bytes())
-            for z in zs:
-                zc = torch.empty((s.R + 32, dp), device=dev, dtype=torch.float32)
-                zc[s.R:].zero_()
-                stw = torch.empty((nst,), device=dev, dtype=torch.uint8)
-                _lib.check(L.sga_loss_centre_tables(_p(z), s.A, s.J1, s.J2, _p(zc), _p(stw), st), 'sga_loss_centre_tables')
-                zbs.append(stw); zcs.append(zc)
-            ev = _ev_start()
-            _lib.check(L.sga_loss_multi_sums_centred(_ptr_array(zcs), M, _p(beta), s.A, s.J1, s.J2, TAU_ICL, TAU_IAL, _p(sums), a_lo, a_hi, st),
-                       'sga_loss_multi_sums_centred')
-            _ev_stop(ev, 'loss_multi_sums', (a_hi - a_lo, s.A, s.J1, s.J2, M))
-        else:
-            ev = _ev_start()
-            _lib.check(L.sga_loss_multi_sums(zarr, M, dmax, _p(beta), s.A, s.J1, s.J2, TAU_ICL, TAU_IAL, _p(sums), a_lo, a_hi, st),
-                       'sga_loss_multi_sums')
-            _ev_stop(ev, 'loss_multi_sums', (a_hi - a_lo, s.A, s.J1, s.J2, M))
+        tier = TIERS['plain' if dmax > 100 else 'centred' if get_mfma_mode() == 'f32' else 'planes'](s, zs, dmax)
+        tier.prepare()
+        tier.sums(beta, sums, a_lo, a_hi)
         sums = _allreduce_sum(sums[0].contiguous(), reduce)
         out = torch.empty((slots * (nt + 2 * M),), device=dev, dtype=torch.float64)
         onepass = coef_hint is not None and _o.FUSED_AA_ONEPASS and s.A >= _o.ONEPASS_MIN_ANCHORS
@@ -608,32 +673,28 @@ class FusedContrastiveFn(torch.autograd.Function):
                 sym = False
             if not sym:
                 walk = _anchor_chunks(a_lo, a_hi, s.A, M)
-            terms, gs_aa, gam_aa = _aa_walk(s, zs, zbs, zcs, tier, beta, sums, float(alpha), coef, dz_all, walk, sym, out=out)
+            terms, gs_aa, gam_aa = _aa_walk(s, tier, beta, sums, float(alpha), coef, dz_all, walk, sym, out=out)
             out = _allreduce_sum(terms.clone(), reduce)
             extra = [dz_all, gs_aa.clone(), gam_aa.clone(), coef]
         else:
             # joint similarities derived in registers, I block resident in LDS
-            _lib.check(L.sga_loss_anchor_multi_fwd(zarr, M, _p(beta), s.A, _p(sums), float(alpha), TAU_ICL, TAU_IAL, _p(out),
-                                                   a_lo, a_hi, st), 'sga_loss_anchor_multi_fwd')
+            _call('sga_loss_anchor_multi_fwd', _ptr_array(zs), M, _p(beta), s.A, _p(sums), float(alpha), TAU_ICL, TAU_IAL, _p(out), a_lo, a_hi)
             out = _allreduce_sum(out[:nt + 2 * M].contiguous(), reduce)
         ctx.s, ctx.alpha, ctx.M, ctx.shard, ctx.reduce = s, float(alpha), M, (a_lo, a_hi), reduce
         ctx.shapes = [tuple(t.shape) for t in tables]
-        ctx.tier = tier
-        ctx.onepass = onepass
-        ctx.save_for_backward(sums, beta, *zs, *nrms, *zbs, *zcs, *extra)
+        ctx.tier, ctx.dmax, ctx.onepass = type(tier), dmax, onepass
+        ctx.save_for_backward(sums, beta, *zs, *nrms, *tier.saved(), *extra)
         return out.float() + poison
 
     @staticmethod
     def backward(ctx, gout):
         L = _lib.lib()
-        s, M, tier = ctx.s, ctx.M, ctx.tier
+        s, M = ctx.s, ctx.M
         a_lo, a_hi = ctx.shard
-        ns = a_hi - a_lo
         sums, beta, *rest = ctx.saved_tensors
-        nb = 0 if tier == 'plain' else M
-        zs, nrms, zbs, zcs = rest[:M], rest[M:2 * M], rest[2 * M:2 * M + nb], rest[2 * M + nb:2 * M + 2 * nb]
+        zs, nrms = rest[:M], rest[M:2 * M]
+        tier = ctx.tier(s, zs, ctx.dmax, saved=rest[2 * M:])
         dev = sums.device
-        st = _stream()
         dp = 104
         A = s.A
         coef = gout.contiguous().float()
@@ -644,7 +705,7 @@ class FusedContrastiveFn(torch.autograd.Function):
             # (loss / k, loss * w) is applied here: u = <gout, hint> / <hint, hint>.  A gout that is NOT a multiple of the hint (a caller
             # who backpropagates one of the returned components alone, or re-weights them) cannot be served from the saved gradients:
             # that is detected on the device and raised at the next batch (deferred, no host sync) -- set ops.FUSED_AA_ONEPASS = False.
-            dz_aa, gs_aa, gam_aa, hint = rest[2 * M + 2 * nb:]
+            dz_aa, gs_aa, gam_aa, hint = rest[-4:]
             hh = torch.dot(hint, hint)
             u = torch.dot(coef, hint) / hh
             # Always (_o.VALIDATE or not), on the device and without a host sync: a mismatching gradient POISONS what this node returns --
@@ -664,33 +725,16 @@ class FusedContrastiveFn(torch.autograd.Function):
         else:
             dz_all = torch.zeros((M, s.R, dp), device=dev, dtype=torch.float32)      # one fill for the M accumulation targets
             dzs = [dz_all[k] for k in range(M)]
-            _, gs, gam_anc = _aa_walk(s, zs, zbs, zcs, tier, beta, sums, ctx.alpha, coef, dzs, _anchor_chunks(a_lo, a_hi, A, M), False)
+            _, gs, gam_anc = _aa_walk(s, tier, beta, sums, ctx.alpha, coef, dzs, _anchor_chunks(a_lo, a_hi, A, M), False)
             gs = _allreduce_sum(gs, ctx.reduce)                          # dL/d(global sums) needs every shard's tiles
-        ev = _ev_start()
-        if tier == 'planes':                  # the forward's blocked bf16 h / m / l planes
-            _lib.check(L.sga_loss_multi_grad_bf16x6(_ptr_array(zbs), M, _p(beta), A, s.J1, s.J2, TAU_ICL, TAU_IAL, _p(gs), _ptr_array(dzs),
-                                                    _p(gam_neg), a_lo, a_hi, st), 'sga_loss_multi_grad_bf16x6')
-        elif tier == 'centred':               # fp32 MFMA over the centred fp32 tables
-            _lib.check(L.sga_loss_multi_grad_centred(_ptr_array(zcs), M, _p(beta), A, s.J1, s.J2, TAU_ICL, TAU_IAL, _p(gs), _ptr_array(dzs),
-                                                     _p(gam_neg), a_lo, a_hi, st), 'sga_loss_multi_grad_centred')
-        else:
-            _lib.check(L.sga_loss_multi_grad(_ptr_array(zs), M, max(d for _, d in ctx.shapes), _p(beta), A, s.J1, s.J2, TAU_ICL, TAU_IAL, _p(gs), _ptr_array(dzs),
-                                             _p(gam_neg), a_lo, a_hi, st), 'sga_loss_multi_grad')
-        _ev_stop(ev, 'loss_multi_grad_bf16x6' if tier == 'planes' else 'loss_multi_grad', (ns, A, s.J1, s.J2, M))
+        tier.grad(beta, gs, dzs, gam_neg, a_lo, a_hi)
         grads = []
         same = all(sh == ctx.shapes[0] for sh in ctx.shapes)
         de_all = torch.zeros((M,) + tuple(ctx.shapes[0]), device=dev, dtype=torch.float32) if same else None   # one fill
         for k in range(M):
             t, d = ctx.shapes[k]
             de = de_all[k] if same else torch.zeros((t, d), device=dev, dtype=torch.float32)
-            if tier == 'planes':              # the gradient is in two parts (sum c (z - zbar) | sum c): projected without forming their sum
-                _lib.check(L.sga_loss_scatter_tangent(_p(dzs[k]), _p(zs[k]), _p(nrms[k]), _p(s.idx), A, s.J1, s.J2, d, _p(zbs[k]), _p(de), st),
-                           'sga_loss_scatter_tangent')
-            elif tier == 'centred':
-                _lib.check(L.sga_loss_scatter_tangent_stat(_p(dzs[k]), _p(zs[k]), _p(nrms[k]), _p(s.idx), s.R, d, _p(zbs[k]), _p(de), st),
-                           'sga_loss_scatter_tangent_stat')
-            else:
-                _lib.check(L.sga_loss_scatter(_p(dzs[k]), _p(zs[k]), _p(nrms[k]), _p(s.idx), s.R, d, dp, _p(de), st), 'sga_loss_scatter')
+            tier.scatter(k, dzs[k], nrms[k], d, de)
             grads.append(de)
         # d/dbeta_m: through the negatives (gamma) + through the anchors x anchors terms
         gbeta = (gam_neg[0] + gam_anc).float()

@@ -43,6 +43,8 @@ import functools
 import json
 import math
 import os
+import types
+from unittest import mock
 
 import torch
 
@@ -728,104 +730,61 @@ def run_gather(E, idx, Dp):
 
 
 class Tier:
-    """The device images of a case's tables in one tier.  plain: the packed tables; centred: the CPU-made centred images (the stage's stated
-    input) and the statistics blocks of sga_loss_centre_tables; planes: the plane images sga_loss_split3_tables makes of the packed tables.
-    made_zc: the centred rows the library itself produced, for the check against centre_image."""
+    """A case's tables in one tier, launched through the product's own tier object (sgaligner_amd.loss_ops.TIERS), with what is the test's:
+    outputs pre-filled with NaN; centred: the CPU-made centred images (the stage's stated input) in place of the library's.  made_zc: the
+    centred rows the library itself produced, for the check against centre_image."""
 
     def __init__(self, tier, Z, img, A, J1, J2, D):
-        lib, L, p, pa, st = _abi()
+        from sgaligner_amd import loss_ops, ops
+        self.ops = ops
         self.tier, self.M, self.A, self.J1, self.J2, self.D = tier, len(Z), A, J1, J2, D
         self.R = 2 * A + J1 + J2
         self.zs = [packed(z, D).cuda() for z in Z]
-        self.made_zc, self.stat, self.zb = [], [], []
-        if tier == 'plain':
-            self.tabs = self.zs
-        elif tier == 'centred':
-            self.tabs = [i.cuda().contiguous() for i in img]
-            for z in self.zs:
-                zc = torch.full((self.R + 32, DP), NAN, device='cuda')
-                sw = torch.zeros(int(L.sga_loss_centre_bytes()), device='cuda', dtype=torch.uint8)
-                lib.check(L.sga_loss_centre_tables(p(z), A, J1, J2, p(zc), p(sw), st), 'sga_loss_centre_tables')
-                self.made_zc.append(zc[:self.R])
-                self.stat.append(sw)
-        else:
-            nb = int(L.sga_loss_split3_bytes(A, J1, J2))
-            for z in self.zs:
-                zb = torch.zeros(nb, device='cuda', dtype=torch.uint8)
-                zc = torch.full((2 * A + 32, DP), NAN, device='cuda')
-                zc[2 * A:].zero_()
-                lib.check(L.sga_loss_split3_tables(p(z), A, J1, J2, p(zb), p(zc), st), 'sga_loss_split3_tables')
-                self.zb.append(zb)
-                self.made_zc.append(zc)
-            self.tabs = self.zb
-        self.zc_op = self.zs if tier == 'plain' else ([i.cuda().contiguous() for i in img] if tier == 'centred' else self.made_zc)
+        self.index = types.SimpleNamespace(A=A, J1=J1, J2=J2, R=self.R, idx=None)          # what the tier reads of ops.IndexSets
+        t = self.t = loss_ops.TIERS[tier](self.index, self.zs, D)
+        for zc in getattr(t, 'zc', []):
+            zc[:-32].fill_(NAN)
+        t.prepare()
+        self.stat = getattr(t, 'stat', None)
+        self.made_zc = [zc[:-32] for zc in getattr(t, 'zc', [])]
+        if tier == 'centred':
+            t.zc = [i.cuda().contiguous() for i in img]
 
     def sums(self, beta, lo, hi, lite=0):
-        lib, L, p, pa, st = _abi()
-        M, nt = self.M, self.M + 1
-        buf = torch.full((_slots(), nt, 8), NAN, device='cuda', dtype=torch.float64)
-        b = beta.cuda()
-        a = (self.A, self.J1, self.J2, TAU[0], TAU[1], p(buf), lo, hi)
-        if self.tier == 'plain':
-            lib.check(L.sga_loss_multi_sums(pa(self.tabs), M, self.D, p(b), *a, st), 'sga_loss_multi_sums')
-        elif self.tier == 'centred':
-            lib.check(L.sga_loss_multi_sums_centred(pa(self.tabs), M, p(b), *a, st), 'sga_loss_multi_sums_centred')
-        else:
-            lib.check(L.sga_loss_multi_sums_bf16x6(pa(self.tabs), M, p(b), *a, int(lite), st), 'sga_loss_multi_sums_bf16x6')
+        buf = torch.full((_slots(), self.M + 1, 8), NAN, device='cuda', dtype=torch.float64)
+        with mock.patch.object(self.ops, 'BF16X6_SUMS_LITE', bool(lite)):
+            self.t.sums(beta.cuda(), buf, lo, hi)
         return buf[0].cpu()
 
     def grad(self, beta, gs, lo, hi, dz=None):
         """dZ [M][R, 104] (accumulated into dz when given) and gamma [M]."""
-        lib, L, p, pa, st = _abi()
-        M = self.M
         if dz is None:
-            dz = [torch.zeros(self.R + 32, DP, device='cuda') for _ in range(M)]
-        gam = torch.full((_slots(), M), NAN, device='cuda', dtype=torch.float64)
-        b, g = beta.cuda(), gs.cuda().contiguous()
-        a = (self.A, self.J1, self.J2, TAU[0], TAU[1], p(g), pa(dz), p(gam), lo, hi)
-        if self.tier == 'plain':
-            lib.check(L.sga_loss_multi_grad(pa(self.tabs), M, self.D, p(b), *a, st), 'sga_loss_multi_grad')
-        elif self.tier == 'centred':
-            lib.check(L.sga_loss_multi_grad_centred(pa(self.tabs), M, p(b), *a, st), 'sga_loss_multi_grad_centred')
-        else:
-            lib.check(L.sga_loss_multi_grad_bf16x6(pa(self.tabs), M, p(b), *a, st), 'sga_loss_multi_grad_bf16x6')
+            dz = [torch.zeros(self.R + 32, DP, device='cuda') for _ in range(self.M)]
+        gam = torch.full((_slots(), self.M), NAN, device='cuda', dtype=torch.float64)
+        self.t.grad(beta.cuda(), gs.cuda().contiguous(), dz, gam, lo, hi)
         return dz, gam[0].cpu()
 
     def stash(self, m, dS, jobs, entry):
         """The stash products of table m over a walk of `jobs` (lo, hi, j_lo, j_hi, mir): the float32 coefficients dS [A, A] cut into the
         launches' stashes M1[(j - j_lo), (i - lo)] = dS[i, j], M2[(j - mir), (i - lo)] = dS[j, i].  entry: 'stash_grad' (ordered blocks, jobs
-        (lo, hi, 0, A, A)), 'symx', 'symx_bf16x6'.  Returns dZ [2A, 104]."""
-        lib, L, p, pa, st = _abi()
-        A = self.A
+        (lo, hi, 0, A, A)), 'symx', 'symx_bf16x6' (the planes tier's own) -- chosen here, through the tier's arguments.  Returns dZ [2A, 104]."""
         dz = torch.zeros(self.R + 32, DP, device='cuda')
         d = dS.cuda()
-        for lo, hi, jl, jh, mir in jobs:
-            m1 = d[lo:hi, jl:jh].t().contiguous()
-            m2 = d[mir:jh, lo:hi].contiguous() if mir < jh else None
-            if entry == 'stash_grad':
-                assert (jl, jh) == (0, A) and mir >= A
-                lib.check(L.sga_loss_stash_grad(p(m1), p(self.zc_op[m]), A, DP, p(dz), lo, hi, st), 'sga_loss_stash_grad')
-            elif entry == 'symx':
-                lib.check(L.sga_loss_stash_grad_symx(p(m1), p(m2), p(self.zc_op[m]), A, DP, p(dz), lo, hi, jl, jh, mir, st), 'sga_loss_stash_grad_symx')
-            else:
-                lib.check(L.sga_loss_stash_grad_symx_bf16x6(p(m1), p(m2), p(self.zb[m]), A, self.J1, self.J2, p(dz), lo, hi, jl, jh, mir, st),
-                          'sga_loss_stash_grad_symx_bf16x6')
-        return dz[:2 * A].cpu()
+        assert entry != 'symx_bf16x6' or self.tier == 'planes'
+        with mock.patch.object(self.ops, 'BF16X6_STASH', entry == 'symx_bf16x6'):
+            for lo, hi, jl, jh, mir in jobs:
+                m1 = d[lo:hi, jl:jh].t().contiguous()
+                m2 = d[mir:jh, lo:hi].contiguous() if mir < jh else None
+                assert entry != 'stash_grad' or ((jl, jh) == (0, self.A) and mir >= self.A)
+                self.t.stash(m, m1, m2, dz, (lo, hi, jl, jh, mir), entry != 'stash_grad')
+        return dz[:2 * self.A].cpu()
 
     def scatter(self, m, dz_in, nrm, idx, T, stat=None):
         """dE [T, D] by the tier's scatter; centred: stat = a statistics block to hand over instead of the library's own."""
-        lib, L, p, pa, st = _abi()
-        D = self.D
-        dz, n, ix = dz_in.cuda().contiguous(), nrm.cuda(), idx.cuda()
-        de = torch.zeros(T, D, device='cuda')
-        if self.tier == 'plain':
-            lib.check(L.sga_loss_scatter(p(dz), p(self.zs[m]), p(n), p(ix), self.R, D, DP, p(de), st), 'sga_loss_scatter')
-        elif self.tier == 'centred':
-            sw = self.stat[m] if stat is None else stat
-            lib.check(L.sga_loss_scatter_tangent_stat(p(dz), p(self.zs[m]), p(n), p(ix), self.R, D, p(sw), p(de), st), 'sga_loss_scatter_tangent_stat')
-        else:
-            lib.check(L.sga_loss_scatter_tangent(p(dz), p(self.zs[m]), p(n), p(ix), self.A, self.J1, self.J2, D, p(self.zb[m]), p(de), st),
-                      'sga_loss_scatter_tangent')
+        de = torch.zeros(T, self.D, device='cuda')
+        self.index.idx = idx.cuda()
+        self.t.stat = self.stat if stat is None else {m: stat}
+        self.t.scatter(m, dz_in.cuda().contiguous(), nrm.cuda(), self.D, de)
         return de.cpu()
 
 
@@ -886,13 +845,9 @@ def ordered_jobs(A, rows):
 def sym_jobs(A, M, stash_bytes, cuts=None):
     """ops._sym_jobs for every rank of `cuts` (one rank: [0, A]) under a stash bound."""
     from sgaligner_amd import ops
-    keep = ops.STASH_BYTES
-    ops.STASH_BYTES = stash_bytes
-    try:
-        cuts = cuts or [0, A]
+    cuts = cuts or [0, A]
+    with mock.patch.object(ops, 'STASH_BYTES', stash_bytes):
         return [j for r in range(len(cuts) - 1) for j in ops._sym_jobs(list(cuts), r, M)]
-    finally:
-        ops.STASH_BYTES = keep
 
 
 def run_head(terms, lv_ial, lv_icl, A, z_ial, alpha, zoom, f64, gout):
@@ -944,7 +899,7 @@ def measure_centring(name, tier):
     c = _case_inputs(name)
     T, sr = tier_images(name, tier), sweep_refs(name, tier)
     for m, made in enumerate(T.made_zc):
-        n = made.shape[0] - (32 if tier == 'planes' else 0)
+        n = made.shape[0]
         img, got = sr['img'][m][:n].clone(), made[:n].cpu()
         if tier == 'planes':                               # (the anchor rows' copy carries no b: the stash products never read column 100)
             img[:, 100] = 0.0

@@ -264,6 +264,8 @@ ROUTES = {
                         'sga_loss_anchor_multi_bwd', 'sga_loss_stash_grad', 'sga_loss_multi_grad_centred', 'sga_loss_scatter_tangent_stat'}),
     'plain-onepass-sym': (104, 'bf16x6', dict(STASH_BYTES=1 << 19), {'sga_loss_multi_sums', 'sga_loss_anchor_multi_bwd_symx', 'sga_loss_stash_grad_symx',
                           'sga_loss_multi_grad', 'sga_loss_scatter'}),
+    'plain-twopass': (104, 'bf16x6', dict(FUSED_AA_ONEPASS=False), {'sga_loss_multi_sums', 'sga_loss_anchor_multi_fwd', 'sga_loss_anchor_multi_bwd',
+                      'sga_loss_stash_grad', 'sga_loss_multi_grad', 'sga_loss_scatter'}),
 }
 
 
