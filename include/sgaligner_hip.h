@@ -340,6 +340,15 @@ int sga_loss_scatter_tangent(const float* dZ, const float* Z, const float* nrm, 
  * product, fp32 accumulation; dZ [2A.., 104] receives the two-part form (columns 0..99 and 101) that sga_loss_scatter_tangent projects. */
 int sga_loss_stash_grad_symx_bf16x6(const float* M1, const float* M2, const void* Zb, int A, int J1, int J2, float* dZ,
                                     int a_lo, int a_hi, int j_lo, int j_hi, int mir, void* stream);
+/* sga_loss_anchor_multi_bwd_symx with the similarities formed from the three-plane images Zb[m] of sga_loss_split3_tables (same A, J1, J2;
+ * their anchor segments X1 | X2) on the bf16 matrix pipe: the sweeps' six partial products in one fp32 accumulator, then the fp32 kernel's
+ * own epilogue.  M = 2 or 3.  Same outputs: stash layouts, gs / gamma / out_terms slots and their fold.  a_lo, j_lo, mir: multiples of 32
+ * (or mir >= j_hi: no mirrored elements, M2 may be NULL); a_hi, j_hi: multiples of 32 or == A.  The ordered walk of a block is
+ * (j_lo, j_hi, mir) = (0, A, A), M2 == NULL; only then may out_terms be NULL (no term values). */
+int sga_loss_anchor_multi_bwd_symx_bf16x6(const void* const* Zb, int M, const float* beta, int A, int J1, int J2, const double* sums,
+                                          float alpha, float tau_icl, float tau_ial, const float* coef, float* const* M1, float* const* M2,
+                                          double* gs, double* gamma, int a_lo, int a_hi, int j_lo, int j_hi, int mir, double* out_terms,
+                                          void* stream);
 
 /* ---- loss_group = b: the same loss on G independent groups of b consecutive pairs ------------------------
  * replaces the reference trainer feeding b pairs per iteration (configs/scan3r/scan3r_ground_truth.yaml:27,

@@ -25,13 +25,14 @@ def _newer(src_list, target):
     return any(os.path.getmtime(s) > t for s in src_list)
 
 
-# Per-source flags.  The loss kernels (contrastive.hip, loss_pertable.hip, loss_anchor.hip): SLP-packed v_pk_mul/v_pk_fma_f32 (+ the v_movs that assemble their operand pairs) in the sweep
+# Per-source flags.  The loss kernels (contrastive.hip, loss_pertable.hip, loss_anchor.hip, anchor3.hip): SLP-packed v_pk_mul/v_pk_fma_f32 (+ the v_movs that assemble their operand pairs) in the sweep
 # epilogues are slower beside fp32 MFMAs than the scalar instructions they replace (MI355X_MICROARCH guide; measured here: backward sweep
 # 0.767 -> 0.770 of peak, configs[2] step 7.243 -> 7.226 s).
 FILE_FLAGS = {'contrastive.hip': ['-fno-slp-vectorize'],
               'loss_pertable.hip': ['-fno-slp-vectorize'],
               'loss_anchor.hip': ['-fno-slp-vectorize'],
               'sweep3.hip': ['-fno-slp-vectorize'],
+              'anchor3.hip': ['-fno-slp-vectorize'],
               'pointnet.hip': ['-fno-slp-vectorize'],
               # nnsearch.hip: every fp64 operation rounded on its own -- the distances are bit-identical to the host KD-tree's (no FMA)
               'nnsearch.hip': ['-ffp-contract=off'],

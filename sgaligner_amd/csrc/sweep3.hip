@@ -40,22 +40,9 @@
 #include <type_traits>
 
 #include "loss_math.h"
+#include "s3_layout.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-constexpr int S3_DP = 104;
-constexpr int S3_PLANE = 3 * 2 * 1024;           // 6144 B
-constexpr int S3_TAIL = 3 * S3_PLANE;            // byte offset of the tail image in a block
-constexpr int S3_BLOCK = S3_TAIL + 2048;         // 20480 B
-constexpr int S3_NCH = S3_BLOCK / 1024;          // 20 DMA chunks
-constexpr int S3_ROWSLOTS = 3 * 12 + 4;          // 16-byte slots that hold one row: 3 planes x (3 K steps x 4 k groups) + the tail image's 4 k groups
 
 // v0, v1 -> three packed bf16 pairs, v = h + m + l EXACTLY (round to nearest at each step; the residuals are exact in fp32, the last one has
 // at most 8 significant bits).  Residual = v - float(bf16): the bf16 pair is unpacked by a shift / a mask (plain VALU: beside MFMAs they cost
@@ -87,9 +74,6 @@ __device__ __forceinline__ void split3_pair(float v0, float v1, unsigned& h, uns
     const bf16x2 Lo = __builtin_convertvector(f32x2{s0, s1}, bf16x2);
     h = hu; m = mu; l = __builtin_bit_cast(unsigned, Lo);
 }
-__device__ __forceinline__ f32x4 mfma_b(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 __device__ __forceinline__ u32x2 tr_read16(const unsigned char* p) {     // ds_read_b64_tr_b16
     return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p)));
 }
@@ -106,11 +90,6 @@ template <int X, int END, int NR, bool VALU_ALL> __device__ __forceinline__ void
         sgb_seq<X + 1, END, NR, VALU_ALL>();
     }
 }
-__host__ __device__ constexpr int s3_slot(int g, int i) { return 16 * g + (i ^ (12 * (g & 1))); }
-
-struct TLayout { int nbA, nb1, nb2; };
-__host__ __device__ inline TLayout make_tlayout(int A, int J1, int J2) { return TLayout{(A + 31) / 32, (J1 + 31) / 32, (J2 + 31) / 32}; }
-
 // Statistics block of a table, behind its blocks and the slack block: float zbar[104] | float nbh (= |zbar|^2 / 2) ... | at +512 B: double colsum[104].
 constexpr int S3_STAT_BYTES = 2048;
 constexpr int S3_DREAL = 100;                    // data columns; 100, 101 are the bookkeeping columns (emb_dim <= 100 in this mode)
@@ -378,12 +357,7 @@ __device__ __forceinline__ void sweep3_body(const TArgs& a, const int g) {
 #pragma unroll
             for (int q = 0; q < 3; ++q) rescale(opl[m][0][q], opl[m][1][q], opl[m][2][q]);
             rescale(th, tm, tl);
-            // against the image's k groups (h, h, m, l):  O0 = (h, m, h, h) -> h h + h m + m h + l h;  O1 = (l, 0, m, 0) -> h l + m m
-            otl[m][0] = g4 == 1 ? tm : th;
-            otl[m][1] = g4 == 0 ? tl : (g4 == 2 ? tm : u32x4{0, 0, 0, 0});
-#pragma unroll
-            for (int t = 0; t < 2; ++t)                               // columns 100, 101: the owner holds (1, b_i) against the other's (b_j, 1)
-                otl[m][t][2] = (otl[m][t][2] >> 16) | (otl[m][t][2] << 16);
+            s3_own_tails(th, tm, tl, g4, otl[m]);   // O0 = (h, m, h, h), O1 = (l, 0, m, 0), columns 100, 101 swapped (s3_layout.h)
         }
     }
 #pragma unroll

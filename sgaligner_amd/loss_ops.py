@@ -5,9 +5,10 @@ working).  The run-time switches live in ops.py and are read through the module 
 caller or a test takes effect here.
 
 FusedContrastiveFn runs in one of three arithmetic tiers, and a tier is defined in ONE place, its class in TIERS: the table images, the entry
-points and operands of the five stages that differ (images, forward sums, stash products, gradient sweep, scatter) and what backward needs
-saved.  forward(), backward() and _aa_walk only call its methods, and tests/loss_gate.py launches through the same object.  A new tier is one
-more class and one more name where forward() chooses; a new anchors x anchors kernel is a change to the stash() of the tier it serves."""
+points and operands of the six stages that differ (images, forward sums, anchors x anchors launch, stash products, gradient sweep, scatter) and
+what backward needs saved.  forward(), backward() and _aa_walk only call its methods, and tests/loss_gate.py launches through the same object.
+A new tier is one more class and one more name where forward() chooses; a new anchors x anchors kernel is a change to the anchor() / stash() of
+the tier it serves."""
 from __future__ import annotations
 
 import ctypes as _ct
@@ -520,6 +521,17 @@ class PlainTier:
         else:
             _call('sga_loss_stash_grad', _p(m1), b, self.s.A, 104, _p(dz), *job[:2])
 
+    def anchor(self, beta, sums, alpha, coef, m1, m2, gsc, gam2, job, sym, out):
+        """One launch job = (lo, hi, j_lo, j_hi, mir) of the A x A walk: the transposed coefficient stashes m1 (and m2, a symmetric launch's
+        mirrored ones, or None), dL/d(sums) into gsc, dL/dbeta into gam2, the rows' term values into out (None: not wanted)."""
+        lo, hi, jl, jh, mir = job
+        head = (_ptr_array(self.zs), self.M, _p(beta), self.s.A, _p(sums), alpha, TAU_ICL, TAU_IAL, _p(coef), _ptr_array(m1))
+        if sym:
+            _call('sga_loss_anchor_multi_bwd_symx', *head, _ptr_array(m2) if m2 is not None else (_ct.c_void_p * self.M)(), _p(gsc), _p(gam2),
+                  lo, hi, jl, jh, mir, _p(out))
+        else:
+            _call('sga_loss_anchor_multi_bwd', *head, _p(gsc), _p(gam2), lo, hi, _p(out))
+
     def scatter(self, k, dz, nrm, d, de):
         """dE [T, d] of table k from the gradient dz of its unit rows."""
         _call('sga_loss_scatter', _p(dz), _p(self.zs[k]), _p(nrm), _p(self.s.idx), self.s.R, d, 104, _p(de))
@@ -564,6 +576,16 @@ class PlanesTier(PlainTier):
         # the four stash products on the sweeps' three exact bf16 planes (csrc/sweep3.hip: stash3_kernel), on ordered walks too
         _call('sga_loss_stash_grad_symx_bf16x6', _p(m1), _p(m2), _p(self.planes[k]), *self.geom, _p(dz), *job)
 
+    def anchor(self, beta, sums, alpha, coef, m1, m2, gsc, gam2, job, sym, out):
+        lo, hi, jl, jh, mir = job
+        A = self.s.A
+        aligned = lo % 32 == 0 and jl % 32 == 0 and (mir % 32 == 0 or mir >= jh) and (hi % 32 == 0 or hi == A) and (jh % 32 == 0 or jh == A)
+        if not (_o.AA_PLANES and A >= _o.AA_PLANES_MIN_ANCHORS and self.M <= 3 and aligned):
+            return super().anchor(beta, sums, alpha, coef, m1, m2, gsc, gam2, job, sym, out)
+        # the similarities from the sweeps' image on the bf16 matrix pipe (csrc/anchor3.hip); an ordered block is (0, A, A) without m2
+        _call('sga_loss_anchor_multi_bwd_symx_bf16x6', _ptr_array(self.planes), self.M, _p(beta), *self.geom, _p(sums), alpha, TAU_ICL, TAU_IAL, _p(coef),
+              _ptr_array(m1), _ptr_array(m2) if m2 is not None else None, _p(gsc), _p(gam2), lo, hi, jl, jh, mir, _p(out))
+
     def scatter(self, k, dz, nrm, d, de):            # the two parts are projected without forming their sum
         _call('sga_loss_scatter_tangent', _p(dz), _p(self.zs[k]), _p(nrm), _p(self.s.idx), *self.geom, d, _p(self.planes[k]), _p(de))
 
@@ -592,17 +614,11 @@ def _aa_walk(s, tier, beta, sums, alpha, coef, dzs, walk, sym, out=None):
     gam2 = torch.empty((slots, M), device=dev, dtype=torch.float64)
     fl = max(((jh - jl) + max(0, jh - mir)) * (hi - lo) for lo, hi, jl, jh, mir in jobs)
     buf = [torch.empty((fl,), device=dev, dtype=torch.float32) for _ in range(M)]
-    zarr = _ptr_array(tier.zs)
     for lo, hi, jl, jh, mir in jobs:
         n1 = (jh - jl) * (hi - lo)
         m1, m2 = [b[:n1] for b in buf], [b[n1:] for b in buf]
         has2 = mir < jh
-        if sym:
-            _call('sga_loss_anchor_multi_bwd_symx', zarr, M, _p(beta), A, _p(sums), alpha, TAU_ICL, TAU_IAL, _p(coef), _ptr_array(m1),
-                  _ptr_array(m2) if has2 else (_ct.c_void_p * M)(), _p(gsc), _p(gam2), lo, hi, jl, jh, mir, _p(out))
-        else:
-            _call('sga_loss_anchor_multi_bwd', zarr, M, _p(beta), A, _p(sums), alpha, TAU_ICL, TAU_IAL, _p(coef), _ptr_array(m1), _p(gsc), _p(gam2),
-                  lo, hi, _p(out))
+        tier.anchor(beta, sums, alpha, coef, m1, m2 if has2 else None, gsc, gam2, (lo, hi, jl, jh, mir), sym, out)
         if out is not None:
             terms += out[:n_terms]
         gs += gsc[0]

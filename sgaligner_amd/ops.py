@@ -454,6 +454,13 @@ FUSED_AA_ONEPASS = True      # training: A x A terms + gradients from one pass i
 # unordered pair once (sga_loss_anchor_multi_bwd_sym: -34 % per ordered pair, tools/bench_aa.py); across ranks by _sym_jobs.
 AA_SYMMETRIC = True
 ONEPASS_MIN_ANCHORS = 256    # below this the A x A work is negligible and the saved gradients' bookkeeping is not worth its launches
+# 'bf16x6': the A x A backward's similarities from the sweeps' three-plane image on the bf16 matrix pipe (csrc/anchor3.hip,
+# sga_loss_anchor_multi_bwd_symx_bf16x6; M <= 3, launches on 32-row boundaries) instead of the fp32 MFMA over the packed tables; env SGA_AA_PLANES=0
+# switches it off.  AA_PLANES_MIN_ANCHORS: the three-plane kernel is
+# faster on every symmetric 1024-row block measured, 1024 anchors up (ratio 0.82 .. 0.88, profiles/aa_planes_bench_aa.txt: tools/bench_aa.py
+# crossover); below 1024 anchors the A x A part of a step is microseconds, no difference can be measured and the fp32 kernel stays the route.
+AA_PLANES = _os.environ.get('SGA_AA_PLANES', '1') != '0'
+AA_PLANES_MIN_ANCHORS = 1024
 WIDE_STASH = True         # tables wider than 128 columns: coefficient stash + GEMMs instead of the multi-pass gradient sweep (tests flip it)
 KERNEL_EVENTS = None   # bench.py sets this to {} to time the dominant kernel with HIP events on the launch stream
 

@@ -1,5 +1,7 @@
 """Time the anchors x anchors kernel (sga_loss_anchor_multi_bwd, TERMS build) and its stash GEMMs alone on random unit rows.
-  python tools/bench_aa.py [anchors=19456] [rows_per_block=2048] [M=3] [reps=5]"""
+  python tools/bench_aa.py [anchors=19456] [rows_per_block=2048] [M=3] [reps=5]
+  python tools/bench_aa.py 155648 2048 3 5 planes     # + the same symmetric block through sga_loss_anchor_multi_bwd_symx_bf16x6 (three-plane image)
+  python tools/bench_aa.py 0 0 3 5 crossover          # symmetric 1024-row block, fp32 entry against the three-plane one, over a ladder of anchor counts"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ctypes as ct
@@ -10,7 +12,63 @@ A = int(sys.argv[1]) if len(sys.argv) > 1 else 19456
 NS = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
 M = int(sys.argv[3]) if len(sys.argv) > 3 else 3
 reps = int(sys.argv[4]) if len(sys.argv) > 4 else 5
+mode = sys.argv[5] if len(sys.argv) > 5 else ''
 L = _lib.lib(); st = _stream(); dev = 'cuda'
+
+
+def sym_block(A, NS, M, reps, planes):
+    """Median ms of one symmetric block rows [0, NS) x columns [0, A) (mirrored from NS on): (fp32 entry, three-plane entry or None)."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    zs = []
+    for m in range(M):
+        z = torch.zeros(2 * A + 32, 104, device=dev)
+        z[:2 * A, :100] = torch.nn.functional.normalize(torch.randn(2 * A, 100, device=dev, generator=g), dim=1)
+        zs.append(z)
+    nt, slots = M + 1, 1 + L.sga_loss_slots()
+    sums = torch.rand(nt, 8, device=dev, dtype=torch.float64, generator=g) * 1e5 + 1e5
+    beta = torch.full((M,), 1.0 / M, device=dev)
+    coef = (torch.rand(3 * M + 1, device=dev, generator=g) + 0.5) * 1e-4
+    m1 = [torch.empty(A * NS, device=dev) for _ in range(M)]
+    m2 = [torch.empty(max(1, (A - NS) * NS), device=dev) for _ in range(M)]
+    gsc = torch.empty(slots + 1, nt, 8, device=dev, dtype=torch.float64)
+    gam2 = torch.empty(slots, M, device=dev, dtype=torch.float64)
+    out = torch.empty(slots * (nt + 2 * M), device=dev, dtype=torch.float64)
+    e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    res, sums_out = [], []
+    imgs = None
+    if planes:
+        imgs = [torch.empty((L.sga_loss_split3_bytes(A, 0, 0),), device=dev, dtype=torch.uint8) for _ in zs]
+        for z, im in zip(zs, imgs):
+            _lib.check(L.sga_loss_split3_tables(_p(z), A, 0, 0, _p(im), None, st), 'split3')
+    for which in (0, 1) if planes else (0,):
+        t = []
+        for r in range(reps + 1):
+            e[0].record()
+            if which:
+                _lib.check(L.sga_loss_anchor_multi_bwd_symx_bf16x6(_ptr_array(imgs), M, _p(beta), A, 0, 0, _p(sums), 0.5, 0.1, 1.0, _p(coef), _ptr_array(m1),
+                                                                   _ptr_array(m2), _p(gsc), _p(gam2), 0, NS, 0, A, NS, _p(out), st), 'planes')
+            else:
+                _lib.check(L.sga_loss_anchor_multi_bwd_symx(_ptr_array(zs), M, _p(beta), A, _p(sums), 0.5, 0.1, 1.0, _p(coef), _ptr_array(m1), _ptr_array(m2),
+                                                            _p(gsc), _p(gam2), 0, NS, 0, A, NS, _p(out), st), 'sym')
+            e[1].record()
+            torch.cuda.synchronize()
+            if r:
+                t.append(e[0].elapsed_time(e[1]))
+        res.append(float(np.median(t)))
+        sums_out.append((float(out[:nt + 2 * M].sum()), float(m1[0].abs().sum())))
+    return res, sums_out
+
+
+if mode == 'crossover':
+    for a in (1024, 2048, 4096, 8192, 19456, 38912):
+        (f32, pl), cs = sym_block(a, 1024, M, reps, True)
+        print(f'crossover M={M} symmetric 1024 x {a}: fp32 {f32:.3f} ms | three-plane {pl:.3f} ms | ratio {pl / f32:.3f} | checksums {cs[0][0]:.6e} {cs[1][0]:.6e}')
+    sys.exit(0)
+if mode == 'planes':
+    (f32, pl), cs = sym_block(A, NS, M, reps, True)
+    print(f'symmetric block M={M} {NS} x {A}: fp32 entry {f32:.3f} ms | three-plane entry {pl:.3f} ms | ratio {pl / f32:.3f} | term checksums {cs[0][0]:.9e} {cs[1][0]:.9e} '
+          f'| stash checksums {cs[0][1]:.6e} {cs[1][1]:.6e}')
+    sys.exit(0)
 g = torch.Generator(device=dev).manual_seed(0)
 zs = []
 for m in range(M):
