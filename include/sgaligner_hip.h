@@ -281,23 +281,18 @@ int sga_loss_anchor_multi_fwd(const float* const* Z, int M, const float* beta, i
 int sga_loss_anchor_multi_bwd(const float* const* Z, int M, const float* beta, int A, const double* sums, float alpha,
                               float tau_icl, float tau_ial, const float* coef, float* const* M1, double* gs, double* gamma,
                               int a_lo, int a_hi, double* out_terms, void* stream);
-/* Symmetric walk of the anchors x anchors terms for an UNSHARDED anchor set (M in {2,3,4}; reference arithmetic losses.py:43-97, where
- * term (i,j) and term (j,i) are made of the same two similarities S[i,j], S[j,i]): block [a_lo, a_hi) meets the columns j >= a_lo only
- * and also evaluates the mirrored elements (j, i), j >= a_hi -- every unordered anchor pair once over the whole walk instead of twice.
- * a_lo % 32 == 0; a_hi % 32 == 0 or a_hi == A.  M1[m]: [A - a_lo, a_hi - a_lo] floats, M1[m][(j-a_lo)*ns + (i-a_lo)] = dL/dS_m[i,j];
- * M2[m]: [A - a_hi, ns], M2[m][(j-a_hi)*ns + (i-a_lo)] = dL/dS_m[j,i] (may be NULL when a_hi == A).  out_terms / gs / gamma: the block's
- * share, both elements of every pair it visits; summed over the blocks of a walk they equal sga_loss_anchor_multi_bwd's over the same
- * rows.  sga_loss_stash_grad_sym applies one table's two stashes: dX1[R] += M1^T X2[a_lo:A], dX2[a_lo:A] += M1 X1[R],
- * dX1[a_hi:A] += M2 X2[R], dX2[R] += M2^T X1[a_hi:A]. */
-int sga_loss_anchor_multi_bwd_sym(const float* const* Z, int M, const float* beta, int A, const double* sums, float alpha,
-                                  float tau_icl, float tau_ial, const float* coef, float* const* M1, float* const* M2, double* gs,
-                                  double* gamma, int a_lo, int a_hi, double* out_terms, void* stream);
-int sga_loss_stash_grad_sym(const float* M1, const float* M2, const float* Z, int A, int Dp, float* dZ, int a_lo, int a_hi,
-                            void* stream);
-/* The same two entry points for ONE RANK of an anchor-sharded job (new design; the reference has no multi-GPU path:
- * src/engine/base_trainer.py:70,146-158 is dead): rows [a_lo, a_hi) meet the columns [j_lo, j_hi) only; tiles at j >= mir also produce the
- * mirrored element (j, i) (stash M2, rows j - mir), tiles left of mir are visited in the ordered way and must lie in the block's own
- * square.  sga_loss_anchor_multi_bwd_sym == (j_lo, j_hi, mir) = (a_lo, A, a_hi).  M1[m]: [j_hi - j_lo, a_hi - a_lo], M2[m]: [j_hi - mir, a_hi - a_lo]. */
+/* Symmetric form of the anchors x anchors backward (M in {2,3,4}; reference arithmetic losses.py:43-97, where term (i,j) and term (j,i)
+ * are made of the same two similarities S[i,j], S[j,i]): rows [a_lo, a_hi) meet the columns [j_lo, j_hi) only; tiles at j >= mir also
+ * produce the mirrored element (j, i) (stash M2, rows j - mir), tiles left of mir are visited in the ordered way and must lie in the
+ * block's own square.  An UNSHARDED anchor set walked in blocks is (j_lo, j_hi, mir) = (a_lo, A, a_hi): block [a_lo, a_hi) meets the
+ * columns j >= a_lo only and also evaluates the mirrored elements (j, i), j >= a_hi -- every unordered anchor pair once over the whole
+ * walk instead of twice.  Other jobs serve ONE RANK of an anchor-sharded job (new design; the reference has no multi-GPU path:
+ * src/engine/base_trainer.py:70,146-158 is dead).  a_lo % 32 == 0; a_hi % 32 == 0 or a_hi == A; j_lo, j_hi (or == A), mir (or >= j_hi)
+ * multiples of 16.  M1[m]: [j_hi - j_lo, ns = a_hi - a_lo] floats, M1[m][(j-j_lo)*ns + (i-a_lo)] = dL/dS_m[i,j]; M2[m]: [j_hi - mir, ns],
+ * M2[m][(j-mir)*ns + (i-a_lo)] = dL/dS_m[j,i] (M2 or M2[m] may be NULL when mir >= j_hi).  out_terms / gs / gamma: the block's share,
+ * both elements of every pair it visits; summed over the blocks of a walk they equal sga_loss_anchor_multi_bwd's over the same rows.
+ * sga_loss_stash_grad_symx applies one table's two stashes: dX1[R] += M1^T X2[j_lo:j_hi], dX2[j_lo:j_hi] += M1 X1[R],
+ * dX1[mir:j_hi] += M2 X2[R], dX2[R] += M2^T X1[mir:j_hi]  (R = [a_lo, a_hi)). */
 int sga_loss_anchor_multi_bwd_symx(const float* const* Z, int M, const float* beta, int A, const double* sums, float alpha,
                                    float tau_icl, float tau_ial, const float* coef, float* const* M1, float* const* M2,
                                    double* gs, double* gamma, int a_lo, int a_hi, int j_lo, int j_hi, int mir, double* out_terms, void* stream);

@@ -112,8 +112,6 @@ SIGNATURES = {
     'sga_loss_anchor_multi_fwd': (I, [P, I, P, I, P, F, F, F, P, I, I, P]),
     'sga_loss_anchor_multi_bwd': (I, [P, I, P, I, P, F, F, F, P, P, P, P, I, I, P, P]),
     'sga_loss_stash_grad': (I, [P, P, I, I, P, I, I, P]),
-    'sga_loss_anchor_multi_bwd_sym': (I, [P, I, P, I, P, F, F, F, P, P, P, P, P, I, I, P, P]),
-    'sga_loss_stash_grad_sym': (I, [P, P, P, I, I, P, I, I, P]),
     'sga_loss_anchor_multi_bwd_symx': (I, [P, I, P, I, P, F, F, F, P, P, P, P, P, I, I, I, I, I, P, P]),
     'sga_loss_stash_grad_symx': (I, [P, P, P, I, I, P, I, I, I, I, I, P]),
     'sga_loss_split3_bytes': (c_size_t, [I, I, I]),

@@ -1,6 +1,6 @@
 // What the anchors x anchors backward kernels share once a lane holds its similarities (loss_anchor.hip: fp32 MFMA over the packed tables;
 // anchor3.hip: bf16 MFMA over the three-plane image): the launch arguments, the per-element epilogue in its ordered and symmetric forms and
-// the hand-over of the fp32 partial sums to the fp64 slots.  A lane holds P[m][r] = S_m[i, j], Q[m][r] = S_m[j, i] for its anchor row
+// the hand-over of the fp32 partial sums to the fp64 slots.  Their host side is aa_launch.h.  A lane holds P[m][r] = S_m[i, j], Q[m][r] = S_m[j, i] for its anchor row
 // i = my_i and the four columns j = jg + r; which (lane, r) maps to which column is the calling kernel's business (jg).
 #pragma once
 #include "loss_math.h"

@@ -22,13 +22,15 @@
 #include <type_traits>
 
 #include "s3_layout.h"
-#include "aa_epilogue.h"
+#include "aa_launch.h"
 
 namespace {
 
 constexpr int A3_THREADS = 512;
 constexpr int A3_TW = 4;                          // J shares per workgroup (waves = 2 anchor halves x A3_TW)
 constexpr int A3_NOP = 11;                        // own operands per (table, side, half): O1, O0, then [plane h, m, l][K step]
+constexpr size_t a3_lds_bytes(int M) { return (size_t)M * 2 * 2 * A3_NOP * 1024; }      // the workgroup's own rows: what the launch asks for
+static_assert(a3_lds_bytes(3) <= 160 * 1024, "the own rows of three tables fit a CU's LDS");
 
 struct Anchor3Args {
     AnchorMultiArgs a;                            // (Z unused)
@@ -151,6 +153,11 @@ __global__ __launch_bounds__(A3_THREADS) void anchor3_bwd_kernel(Anchor3Args A3)
     aa_flush<M, TERMS>(a, inv_s, lane, slot, acc_gs, acc_gam, acc_out);
 }
 
+template <int M>
+AAKernels<Anchor3Args> anchor3_kernels() {
+    return {anchor3_bwd_kernel<M, true, true>, anchor3_bwd_kernel<M, true, false>, anchor3_bwd_kernel<M, false, false>, 32, A3_TW, a3_lds_bytes(M)};
+}
+
 }  // namespace
 
 /* sga_loss_anchor_multi_bwd_symx on the three-plane images Zb[m] (sga_loss_split3_tables with the same A, J1, J2), M = 2, 3: same outputs, same
@@ -161,56 +168,14 @@ extern "C" int sga_loss_anchor_multi_bwd_symx_bf16x6(const void* const* Zb, int 
                                                      float alpha, float tau_icl, float tau_ial, const float* coef, float* const* M1, float* const* M2,
                                                      double* gs, double* gamma, int a_lo, int a_hi, int j_lo, int j_hi, int mir, double* out_terms,
                                                      void* stream) {
-    SGA_CHECK_ARG(Zb && beta && sums && coef && M1 && gs && gamma && A >= 0 && J1 >= 0 && J2 >= 0, "sga_loss_anchor_multi_bwd_symx_bf16x6: bad argument");
-    SGA_CHECK_ARG(M == 2 || M == 3, "sga_loss_anchor_multi_bwd_symx_bf16x6: M=%d (2 or 3; four tables take sga_loss_anchor_multi_bwd_symx)", M);
-    SGA_CHECK_ARG(a_lo >= 0 && a_lo <= a_hi && a_hi <= A && a_lo % 32 == 0 && (a_hi % 32 == 0 || a_hi == A),
-                  "sga_loss_anchor_multi_bwd_symx_bf16x6: block [%d,%d) not on 32-row boundaries of [0,%d]", a_lo, a_hi, A);
-    SGA_CHECK_ARG(j_lo >= 0 && j_lo % 32 == 0 && j_hi <= A && j_lo <= j_hi && (j_hi % 32 == 0 || j_hi == A) && mir >= j_lo && (mir % 32 == 0 || mir >= j_hi),
-                  "sga_loss_anchor_multi_bwd_symx_bf16x6: columns [%d,%d) / mirror start %d not on 32-column boundaries", j_lo, j_hi, mir);
-    // columns left of the mirror start are visited in the ordered way: the whole ordered walk (0, A, A), or columns of the block's own square
-    const bool ordered = j_lo == 0 && j_hi == A && mir >= j_hi;
-    SGA_CHECK_ARG(ordered || mir <= j_lo || (j_lo >= a_lo && (mir < j_hi ? mir : j_hi) <= a_hi),
-                  "sga_loss_anchor_multi_bwd_symx_bf16x6: ordered columns [%d,%d) outside the block's square [%d,%d)", j_lo, mir, a_lo, a_hi);
-    SGA_CHECK_ARG(ordered || out_terms, "sga_loss_anchor_multi_bwd_symx_bf16x6: a symmetric launch returns its terms (out_terms == NULL)");
-    for (int m = 0; m < M; ++m)
-        SGA_CHECK_ARG(Zb[m] && M1[m] && (mir >= j_hi || (M2 && M2[m])), "sga_loss_anchor_multi_bwd_symx_bf16x6: null table or stash");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc0 = zero_slots(gs, (M + 1) * 8, s, "sga_loss_anchor_multi_bwd_symx_bf16x6")) return rc0;
-    if (int rc1 = zero_slots(gamma, M, s, "sga_loss_anchor_multi_bwd_symx_bf16x6")) return rc1;
-    if (out_terms) { if (int rc2 = zero_slots(out_terms, (M + 1) + 2 * M, s, "sga_loss_anchor_multi_bwd_symx_bf16x6")) return rc2; }
-    if (A == 0 || a_hi <= a_lo || j_hi <= j_lo) return SGA_OK;
+    // (four tables take sga_loss_anchor_multi_bwd_symx)
+    static const AAContract C = {"sga_loss_anchor_multi_bwd_symx_bf16x6", 2, 3, 32, 32, AA_EITHER};
+    const AAOperands o = {Zb, M, beta, A, sums, alpha, tau_icl, tau_ial, coef, M1, M2, gs, gamma, a_lo, a_hi, j_lo, j_hi, mir, out_terms};
+    SGA_CHECK_ARG(J1 >= 0 && J2 >= 0, "sga_loss_anchor_multi_bwd_symx_bf16x6: bad argument");
+    if (int rc = aa_validate(C, o)) return rc;
     Anchor3Args k{};
-    AnchorMultiArgs& a = k.a;
-    a.M = M; a.A = A; a.i_lo = a_lo; a.i_hi = a_hi; a.beta = beta; a.sums = sums; a.alpha = alpha;
-    a.kc = LOG2E / tau_icl; a.ki = LOG2E / tau_ial; a.itc = 1.f / tau_icl; a.iti = 1.f / tau_ial;
-    a.coef = coef; a.gs = gs; a.gamma = gamma; a.out = out_terms;
-    a.j_lo = j_lo; a.j_hi = j_hi; a.mir = mir;
     k.nbA = make_tlayout(A, J1, J2).nbA;
-    for (int m = 0; m < M; ++m) {
-        k.Zb[m] = static_cast<const unsigned char*>(Zb[m]);
-        a.M1[m] = M1[m]; a.M2[m] = M2 ? M2[m] : nullptr;
-    }
-    // float copy of 1/(sums+eps): lives in the block after the gs slots (gs buffers hold (2 + slots) * (M+1)*8 doubles)
-    float* inv = reinterpret_cast<float*>(gs + (size_t)(1 + SGA_SLOTS) * (M + 1) * 8);
-    hipLaunchKernelGGL(inv_sums_kernel, dim3(1), dim3(64), 0, s, sums, inv, (M + 1) * 8);
-    a.inv = inv;
-    // one workgroup per CU (LDS): ~3 rounds of workgroups, each with at least one tile per wave
-    const size_t lds = (size_t)M * 2 * 2 * A3_NOP * 1024;
-    const int nib = (a_hi - a_lo + 31) / 32, ntile16 = 2 * ((j_hi + 31) / 32) - (j_lo >> 4);
-    int nsp = (3 * sga_num_cus() + nib - 1) / nib;
-    if (nsp > (ntile16 + A3_TW - 1) / A3_TW) nsp = (ntile16 + A3_TW - 1) / A3_TW;
-    if (nsp < 1) nsp = 1;
-    a.nsplit = nsp;
-    auto go = [&](auto kern) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, dim3(nib * nsp), dim3(A3_THREADS), lds, s, k);
-    };
-    if (!ordered) { if (M == 2) go(anchor3_bwd_kernel<2, true, true>); else go(anchor3_bwd_kernel<3, true, true>); }
-    else if (out_terms) { if (M == 2) go(anchor3_bwd_kernel<2, true, false>); else go(anchor3_bwd_kernel<3, true, false>); }
-    else { if (M == 2) go(anchor3_bwd_kernel<2, false, false>); else go(anchor3_bwd_kernel<3, false, false>); }
-    if (out_terms) fold_slots(out_terms, (M + 1) + 2 * M, s);
-    fold_slots(gs, (M + 1) * 8, s);
-    fold_slots(gamma, M, s);
-    SGA_CHECK_LAUNCH("sga_loss_anchor_multi_bwd_symx_bf16x6");
-    return SGA_OK;
+    for (int m = 0; m < M; ++m) k.Zb[m] = static_cast<const unsigned char*>(Zb[m]);
+    // 32 anchor rows per workgroup, one workgroup per CU (LDS): ~3 rounds of workgroups, each with at least one tile per wave
+    return aa_run(C, o, k, k.a, M == 2 ? anchor3_kernels<2>() : anchor3_kernels<3>(), A3_THREADS, 3, stream);
 }

@@ -5,7 +5,7 @@
 #include <type_traits>
 
 #include "loss_math.h"
-#include "aa_epilogue.h"      // AnchorMultiArgs, inv_sums_kernel, the backward epilogue (shared with anchor3.hip)
+#include "aa_launch.h"        // AnchorMultiArgs, inv_sums_kernel, the backward epilogue and its host path (shared with anchor3.hip)
 
 // gemm.hip (include/sgaligner_hip.h): the stash gradient of the anchors x anchors backward runs on the GEMM kernels
 extern "C" int sga_gemm(int transA, int transB, int M, int N, int K, const void* A, long lda, int a_is_f64, const float* B,
@@ -286,135 +286,67 @@ __global__ __launch_bounds__(CT_THREADS, 2) void anchor_multi_bwd16_kernel(Ancho
 }  // namespace
 
 // ---- fused anchors x anchors entry points -------------------------------------------------------------------------
-static int fill_anchor_multi(AnchorMultiArgs& a, const float* const* Z, int M, const float* beta, int A, const double* sums,
-                             float alpha, float tau_icl, float tau_ial, int a_lo, int a_hi) {
-    if (M < 2 || M > 4) { sga_set_error("sga_loss_anchor_multi: M=%d not in {2,3,4} (use the per-table kernels)", M); return SGA_ERR_ARG; }
-    if (a_lo < 0 || a_hi > A || a_lo > a_hi) { sga_set_error("sga_loss_anchor_multi: anchor shard [%d,%d) outside [0,%d]", a_lo, a_hi, A); return SGA_ERR_ARG; }
-    a.M = M; a.A = A; a.i_lo = a_lo; a.i_hi = a_hi; a.beta = beta; a.sums = sums; a.alpha = alpha;
-    a.kc = LOG2E / tau_icl; a.ki = LOG2E / tau_ial; a.itc = 1.f / tau_icl; a.iti = 1.f / tau_ial;
-    for (int m = 0; m < M; ++m) { if (!Z[m]) { sga_set_error("sga_loss_anchor_multi: null table"); return SGA_ERR_ARG; } a.Z[m] = Z[m]; }
-    const int nib = (a_hi - a_lo + 31) / 32, ntile = (A + 31) / 32;
-    int ns = (4 * sga_num_cus() + nib - 1) / (nib > 0 ? nib : 1);
-    if (ns > (ntile + 3) / 4) ns = (ntile + 3) / 4;
-    if (ns < 1) ns = 1;
-    a.nsplit = ns;
-    return SGA_OK;
-}
-
-template <int M>
-static void launch_anchor_multi(const AnchorMultiArgs& a, hipStream_t s) {
-    const size_t lds = (size_t)(M * 2 * 32 * 104 + (M + 1) * 8) * sizeof(float);
-    auto k = anchor_multi_kernel<M>;
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const int nib = (a.i_hi - a.i_lo + 31) / 32;
-    hipLaunchKernelGGL(k, dim3(nib * a.nsplit), dim3(CT_THREADS), lds, s, a);
-}
-
 extern "C" int sga_loss_anchor_multi_fwd(const float* const* Z, int M, const float* beta, int A, const double* sums,
                                          float alpha, float tau_icl, float tau_ial, double* out, int a_lo, int a_hi,
                                          void* stream) {
     SGA_CHECK_ARG(Z && beta && sums && out && A >= 0, "sga_loss_anchor_multi_fwd: bad argument");
+    SGA_CHECK_ARG(M >= 2 && M <= 4, "sga_loss_anchor_multi_fwd: M=%d not in {2,3,4} (use the per-table kernels)", M);
+    SGA_CHECK_ARG(a_lo >= 0 && a_hi <= A && a_lo <= a_hi, "sga_loss_anchor_multi_fwd: anchor shard [%d,%d) outside [0,%d]", a_lo, a_hi, A);
+    for (int m = 0; m < M; ++m) SGA_CHECK_ARG(Z[m], "sga_loss_anchor_multi_fwd: null table");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int n = (M + 1) + 2 * M;
     if (int rc0 = zero_slots(out, n, s, "sga_loss_anchor_multi_fwd")) return rc0;
     if (A == 0 || a_hi <= a_lo) return SGA_OK;
     AnchorMultiArgs a{};
-    int rc = fill_anchor_multi(a, Z, M, beta, A, sums, alpha, tau_icl, tau_ial, a_lo, a_hi);
-    if (rc) return rc;
+    aa_fill(a, M, beta, A, sums, alpha, tau_icl, tau_ial, a_lo, a_hi);
+    for (int m = 0; m < M; ++m) a.Z[m] = Z[m];
     a.out = out;
-    if (M == 2) launch_anchor_multi<2>(a, s); else if (M == 3) launch_anchor_multi<3>(a, s); else launch_anchor_multi<4>(a, s);
+    // 32 anchor rows per workgroup, whose four waves walk 32-row J tiles side by side: ~4 rounds of workgroups
+    const int nib = (a_hi - a_lo + 31) / 32;
+    a.nsplit = aa_plan(nib, (A + 31) / 32, 4, 4);
+    const size_t lds = (size_t)(M * 2 * 32 * 104 + (M + 1) * 8) * sizeof(float);
+    auto k = M == 2 ? anchor_multi_kernel<2> : M == 3 ? anchor_multi_kernel<3> : anchor_multi_kernel<4>;
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k, dim3(nib * a.nsplit), dim3(CT_THREADS), lds, s, a);
     fold_slots(out, n, s);
     SGA_CHECK_LAUNCH("sga_loss_anchor_multi_fwd");
     return SGA_OK;
 }
 
-// The backward launch over the columns [j_lo, j_hi) for a block whose shard, tables, coefficients, outputs and stashes are set (tiles at
-// j >= mir also produce the mirrored element when sym): 1/(sums + eps), the split plan, the kernel, the folds.  TERMS follows a.out.
-static void launch_anchor_multi_bwd(AnchorMultiArgs& a, int j_lo, int j_hi, int mir, bool sym, hipStream_t s) {
-    const int M = a.M;
-    a.j_lo = j_lo; a.j_hi = j_hi; a.mir = mir;
-    // float copy of 1/(sums+eps): lives in the block after the gs slots (gs buffers hold (2 + slots) * (M+1)*8 doubles)
-    float* inv = reinterpret_cast<float*>(a.gs + (size_t)(1 + SGA_SLOTS) * (M + 1) * 8);
-    hipLaunchKernelGGL(inv_sums_kernel, dim3(1), dim3(64), 0, s, a.sums, inv, (M + 1) * 8);
-    a.inv = inv;
-    const int RB = M <= 3 ? 32 : 16, TW = M <= 3 ? 2 : 4;
-    const size_t lds = (size_t)(M * 2 * RB * 104 + (M + 1) * 8) * sizeof(float);
-    const int nib = (a.i_hi - a.i_lo + RB - 1) / RB, ntile16 = (j_hi - j_lo + 15) / 16;
-    int nsp = (6 * sga_num_cus() + nib - 1) / nib;
-    if (nsp > (ntile16 + TW - 1) / TW) nsp = (ntile16 + TW - 1) / TW;
-    if (nsp < 1) nsp = 1;
-    a.nsplit = nsp;
-    auto go = [&](auto k) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k, dim3(nib * nsp), dim3(CT_THREADS), lds, s, a);
-    };
-    if (sym) { if (M == 2) go(anchor_multi_bwd16_kernel<2, true, 32, true>); else if (M == 3) go(anchor_multi_bwd16_kernel<3, true, 32, true>); else go(anchor_multi_bwd16_kernel<4, true, 16, true>); }
-    else if (a.out) { if (M == 2) go(anchor_multi_bwd16_kernel<2, true>); else if (M == 3) go(anchor_multi_bwd16_kernel<3, true>); else go(anchor_multi_bwd16_kernel<4, true>); }
-    else { if (M == 2) go(anchor_multi_bwd16_kernel<2, false>); else if (M == 3) go(anchor_multi_bwd16_kernel<3, false>); else go(anchor_multi_bwd16_kernel<4, false>); }
-    if (a.out) fold_slots(a.out, (M + 1) + 2 * M, s);
-    fold_slots(a.gs, (M + 1) * 8, s);
-    fold_slots(a.gamma, M, s);
+// The backward entry points (aa_launch.h): RB anchor rows per workgroup and 4 * 16 / RB shares of the 16-column J tiles; ~6 rounds of workgroups.
+template <int M>
+static AAKernels<AnchorMultiArgs> anchor_multi_bwd_kernels() {
+    constexpr int RB = M <= 3 ? 32 : 16;                             // (the kernel's own default)
+    return {anchor_multi_bwd16_kernel<M, true, RB, true>, anchor_multi_bwd16_kernel<M, true>, anchor_multi_bwd16_kernel<M, false>, RB, 64 / RB,
+            (size_t)(M * 2 * RB * 104 + (M + 1) * 8) * sizeof(float)};
+}
+
+static int anchor_multi_bwd(const AAContract& c, const AAOperands& o, const float* const* Z, void* stream) {
+    if (int rc = aa_validate(c, o)) return rc;
+    AnchorMultiArgs a{};
+    for (int m = 0; m < o.M; ++m) a.Z[m] = Z[m];
+    const auto kern = o.M == 2 ? anchor_multi_bwd_kernels<2>() : o.M == 3 ? anchor_multi_bwd_kernels<3>() : anchor_multi_bwd_kernels<4>();
+    return aa_run(c, o, a, a, kern, CT_THREADS, 6, stream);
 }
 
 extern "C" int sga_loss_anchor_multi_bwd(const float* const* Z, int M, const float* beta, int A, const double* sums,
                                          float alpha, float tau_icl, float tau_ial, const float* coef, float* const* M1,
                                          double* gs, double* gamma, int a_lo, int a_hi, double* out_terms, void* stream) {
-    SGA_CHECK_ARG(Z && beta && sums && coef && M1 && gs && gamma && A >= 0, "sga_loss_anchor_multi_bwd: bad argument");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc0 = zero_slots(gs, (M + 1) * 8, s, "sga_loss_anchor_multi_bwd")) return rc0;
-    if (int rc1 = zero_slots(gamma, M, s, "sga_loss_anchor_multi_bwd")) return rc1;
-    if (out_terms) { if (int rc2 = zero_slots(out_terms, (M + 1) + 2 * M, s, "sga_loss_anchor_multi_bwd")) return rc2; }
-    if (A == 0 || a_hi <= a_lo) return SGA_OK;
-    AnchorMultiArgs a{};
-    int rc = fill_anchor_multi(a, Z, M, beta, A, sums, alpha, tau_icl, tau_ial, a_lo, a_hi);
-    if (rc) return rc;
-    a.coef = coef; a.gs = gs; a.gamma = gamma; a.out = out_terms;
-    for (int m = 0; m < M; ++m) { SGA_CHECK_ARG(M1[m], "sga_loss_anchor_multi_bwd: null stash"); a.M1[m] = M1[m]; }
-    launch_anchor_multi_bwd(a, 0, A, A, false, s);
-    SGA_CHECK_LAUNCH("sga_loss_anchor_multi_bwd");
-    return SGA_OK;
+    static const AAContract C = {"sga_loss_anchor_multi_bwd", 2, 4, 1, 16, AA_ORDERED};
+    return anchor_multi_bwd(C, {reinterpret_cast<const void* const*>(Z), M, beta, A, sums, alpha, tau_icl, tau_ial, coef, M1, nullptr, gs, gamma,
+                                a_lo, a_hi, 0, A, A, out_terms}, Z, stream);
 }
 
-/* Symmetric form of sga_loss_anchor_multi_bwd for an UNSHARDED anchor set walked in blocks (M = 2, 3; terms always returned): block
- * [a_lo, a_hi) meets the columns j >= a_lo only and also produces the mirrored elements (j, i), j >= a_hi, i in the block, so every
- * unordered pair is evaluated once over the whole walk.  a_lo must be a multiple of 32, a_hi a multiple of 32 or == A.
- *   M1[m][(j - a_lo) * ns + (i - a_lo)] = dL/dS_m[i, j],  j in [a_lo, A)          ([A - a_lo, ns] floats)
- *   M2[m][(j - a_hi) * ns + (i - a_lo)] = dL/dS_m[j, i],  j in [a_hi, A)          ([A - a_hi, ns] floats)
- * out_terms / gs / gamma as in sga_loss_anchor_multi_bwd: this block's share (both elements of every pair it visits). */
+/* Symmetric form of sga_loss_anchor_multi_bwd (terms always returned; jobs and stash layouts: include/sgaligner_hip.h): rows [a_lo, a_hi) meet
+ * the columns [j_lo, j_hi) only, tiles at j >= mir also produce the mirrored elements (j, i) into M2, tiles left of mir are visited in the
+ * ordered way.  An unsharded anchor set walked in blocks is (j_lo, j_hi, mir) = (a_lo, A, a_hi): every unordered pair once over the walk. */
 extern "C" int sga_loss_anchor_multi_bwd_symx(const float* const* Z, int M, const float* beta, int A, const double* sums, float alpha,
                                               float tau_icl, float tau_ial, const float* coef, float* const* M1, float* const* M2,
                                               double* gs, double* gamma, int a_lo, int a_hi, int j_lo, int j_hi, int mir, double* out_terms,
                                               void* stream) {
-    SGA_CHECK_ARG(Z && beta && sums && coef && M1 && M2 && gs && gamma && out_terms && A >= 0, "sga_loss_anchor_multi_bwd_symx: bad argument");
-    SGA_CHECK_ARG(M >= 2 && M <= 4, "sga_loss_anchor_multi_bwd_symx: M=%d (2, 3 or 4)", M);
-    SGA_CHECK_ARG(a_lo % 32 == 0 && (a_hi % 32 == 0 || a_hi == A), "sga_loss_anchor_multi_bwd_symx: block [%d,%d) not on 32-row boundaries", a_lo, a_hi);
-    SGA_CHECK_ARG(j_lo >= 0 && j_lo % 16 == 0 && j_hi <= A && j_lo <= j_hi && (j_hi % 16 == 0 || j_hi == A) && mir >= j_lo && (mir % 16 == 0 || mir >= j_hi),
-                  "sga_loss_anchor_multi_bwd_symx: columns [%d,%d) / mirror start %d not on 16-column boundaries", j_lo, j_hi, mir);
-    // columns left of the mirror start are visited in the ordered way: they must lie in the block's own square
-    SGA_CHECK_ARG(mir <= j_lo || (j_lo >= a_lo && (mir < j_hi ? mir : j_hi) <= a_hi), "sga_loss_anchor_multi_bwd_symx: ordered columns [%d,%d) outside the block's square [%d,%d)",
-                  j_lo, mir, a_lo, a_hi);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc0 = zero_slots(gs, (M + 1) * 8, s, "sga_loss_anchor_multi_bwd_symx")) return rc0;
-    if (int rc1 = zero_slots(gamma, M, s, "sga_loss_anchor_multi_bwd_symx")) return rc1;
-    if (int rc2 = zero_slots(out_terms, (M + 1) + 2 * M, s, "sga_loss_anchor_multi_bwd_symx")) return rc2;
-    if (A == 0 || a_hi <= a_lo || j_hi <= j_lo) return SGA_OK;
-    AnchorMultiArgs a{};
-    int rc = fill_anchor_multi(a, Z, M, beta, A, sums, alpha, tau_icl, tau_ial, a_lo, a_hi);
-    if (rc) return rc;
-    a.coef = coef; a.gs = gs; a.gamma = gamma; a.out = out_terms;
-    for (int m = 0; m < M; ++m) {
-        SGA_CHECK_ARG(M1[m] && (M2[m] || mir >= j_hi), "sga_loss_anchor_multi_bwd_symx: null stash");
-        a.M1[m] = M1[m]; a.M2[m] = M2[m];
-    }
-    launch_anchor_multi_bwd(a, j_lo, j_hi, mir, true, s);
-    SGA_CHECK_LAUNCH("sga_loss_anchor_multi_bwd_symx");
-    return SGA_OK;
-}
-
-extern "C" int sga_loss_anchor_multi_bwd_sym(const float* const* Z, int M, const float* beta, int A, const double* sums, float alpha,
-                                             float tau_icl, float tau_ial, const float* coef, float* const* M1, float* const* M2,
-                                             double* gs, double* gamma, int a_lo, int a_hi, double* out_terms, void* stream) {
-    return sga_loss_anchor_multi_bwd_symx(Z, M, beta, A, sums, alpha, tau_icl, tau_ial, coef, M1, M2, gs, gamma, a_lo, a_hi, a_lo, A, a_hi, out_terms, stream);
+    static const AAContract C = {"sga_loss_anchor_multi_bwd_symx", 2, 4, 32, 16, AA_SYMMETRIC};
+    return anchor_multi_bwd(C, {reinterpret_cast<const void* const*>(Z), M, beta, A, sums, alpha, tau_icl, tau_ial, coef, M1, M2, gs, gamma,
+                                a_lo, a_hi, j_lo, j_hi, mir, out_terms}, Z, stream);
 }
 
 /* The four products of a symmetric block's two stashes for one table (Z = [X1 | X2 | ...] rows of width Dp; R = [a_lo, a_hi), C = [j_lo, j_hi),
@@ -435,9 +367,4 @@ extern "C" int sga_loss_stash_grad_symx(const float* M1, const float* M2, const 
     if (!rc && c2 > 0) rc = sga_gemm(0, 0, c2, Dp, ns, M2, ns, 0, X2 + (size_t)a_lo * Dp, Dp, d1 + (size_t)mir * Dp, Dp, nullptr, 1, stream);
     if (!rc && c2 > 0) rc = sga_gemm(1, 0, ns, Dp, c2, M2, ns, 0, X1 + (size_t)mir * Dp, Dp, d2 + (size_t)a_lo * Dp, Dp, nullptr, 1, stream);
     return rc;
-}
-
-extern "C" int sga_loss_stash_grad_sym(const float* M1, const float* M2, const float* Z, int A, int Dp, float* dZ, int a_lo, int a_hi,
-                                       void* stream) {
-    return sga_loss_stash_grad_symx(M1, M2, Z, A, Dp, dZ, a_lo, a_hi, a_lo, A, a_hi, stream);
 }

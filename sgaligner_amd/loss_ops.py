@@ -8,7 +8,7 @@ FusedContrastiveFn runs in one of three arithmetic tiers, and a tier is defined 
 points and operands of the six stages that differ (images, forward sums, anchors x anchors launch, stash products, gradient sweep, scatter) and
 what backward needs saved.  forward(), backward() and _aa_walk only call its methods, and tests/loss_gate.py launches through the same object.
 A new tier is one more class and one more name where forward() chooses; a new anchors x anchors kernel is a change to the anchor() / stash() of
-the tier it serves."""
+the tier it serves (its C side: a contract and a kernel row for csrc/aa_launch.h)."""
 from __future__ import annotations
 
 import ctypes as _ct
@@ -527,8 +527,7 @@ class PlainTier:
         lo, hi, jl, jh, mir = job
         head = (_ptr_array(self.zs), self.M, _p(beta), self.s.A, _p(sums), alpha, TAU_ICL, TAU_IAL, _p(coef), _ptr_array(m1))
         if sym:
-            _call('sga_loss_anchor_multi_bwd_symx', *head, _ptr_array(m2) if m2 is not None else (_ct.c_void_p * self.M)(), _p(gsc), _p(gam2),
-                  lo, hi, jl, jh, mir, _p(out))
+            _call('sga_loss_anchor_multi_bwd_symx', *head, _ptr_array(m2) if m2 is not None else None, _p(gsc), _p(gam2), lo, hi, jl, jh, mir, _p(out))
         else:
             _call('sga_loss_anchor_multi_bwd', *head, _p(gsc), _p(gam2), lo, hi, _p(out))
 
@@ -610,7 +609,7 @@ def _aa_walk(s, tier, beta, sums, alpha, coef, dzs, walk, sym, out=None):
     if not walk:
         return terms, gs, gam
     jobs = walk if sym else [(lo, hi, 0, A, A) for lo, hi in walk]
-    gsc = torch.empty((slots + 1, nt, 8), device=dev, dtype=torch.float64)     # + one block: float copy of 1/(sums+eps)
+    gsc = torch.empty((slots + 1, nt, 8), device=dev, dtype=torch.float64)     # + one block (csrc/aa_launch.h: aa_inv_block)
     gam2 = torch.empty((slots, M), device=dev, dtype=torch.float64)
     fl = max(((jh - jl) + max(0, jh - mir)) * (hi - lo) for lo, hi, jl, jh, mir in jobs)
     buf = [torch.empty((fl,), device=dev, dtype=torch.float32) for _ in range(M)]

@@ -451,7 +451,7 @@ class IndexSets:
 
 FUSED_AA_ONEPASS = True      # training: A x A terms + gradients from one pass in forward() when the loss head announces dL/d(terms)
 # One-pass mode: walk the anchors x anchors pairs SYMMETRICALLY -- a block evaluates (i, j) and (j, i) from the same two similarities, every
-# unordered pair once (sga_loss_anchor_multi_bwd_sym: -34 % per ordered pair, tools/bench_aa.py); across ranks by _sym_jobs.
+# unordered pair once (sga_loss_anchor_multi_bwd_symx: -34 % per ordered pair, tools/bench_aa.py); across ranks by _sym_jobs.
 AA_SYMMETRIC = True
 ONEPASS_MIN_ANCHORS = 256    # below this the A x A work is negligible and the saved gradients' bookkeeping is not worth its launches
 # 'bf16x6': the A x A backward's similarities from the sweeps' three-plane image on the bf16 matrix pipe (csrc/anchor3.hip,

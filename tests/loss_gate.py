@@ -798,12 +798,18 @@ def run_anchor_fwd(zs, beta, A, sums, lo, hi):
     return out[:n].cpu()
 
 
-def run_anchor_bwd(zs, beta, A, sums, coef, jobs, sym, terms=True):
-    """A whole walk of the A x A backward: jobs (lo, hi, j_lo, j_hi, mir); sym: sga_loss_anchor_multi_bwd_symx, else sga_loss_anchor_multi_bwd over
-    (lo, hi) (terms: with out_terms).  Stashes are pre-filled with NaN and written into NaN-filled [A, A] matrices dS[m][i, j] -- an element no
-    launch produced stays NaN, an element produced twice must agree.  Returns (dS [M][A, A], terms, gs [NT, 8], gamma [M]), summed over the walk."""
+AA_ORDERED, AA_SYMX, AA_PLANES = 'sga_loss_anchor_multi_bwd', 'sga_loss_anchor_multi_bwd_symx', 'sga_loss_anchor_multi_bwd_symx_bf16x6'
+
+
+def run_anchor_bwd(entry, tables, geom, beta, sums, coef, jobs, terms=True):
+    """A whole walk of the A x A backward through `entry`: jobs (lo, hi, j_lo, j_hi, mir).  AA_ORDERED takes the packed tables, geom = (A,) and
+    ordered jobs (lo, hi, 0, A, A); AA_SYMX the packed tables and geom = (A,); AA_PLANES the three-plane images and geom = (A, J1, J2).  terms:
+    with out_terms (a symmetric launch always).  A job without mirrored elements (mir >= j_hi) passes M2 == NULL.  Stashes are pre-filled with
+    NaN and written into NaN-filled [A, A] matrices dS[m][i, j] -- an element no launch produced stays NaN, an element produced twice must
+    agree.  Returns (dS [M][A, A], terms, gs [NT, 8], gamma [M]), summed over the walk."""
     lib, L, p, pa, st = _abi()
-    M, nt = len(zs), len(zs) + 1
+    A = geom[0]
+    M, nt = len(tables), len(tables) + 1
     n = 3 * M + 1
     s, b, cf = sums.cuda().contiguous(), beta.cuda(), coef.cuda()
     dS = [torch.full((A, A), NAN, device='cuda') for _ in range(M)]
@@ -814,24 +820,24 @@ def run_anchor_bwd(zs, beta, A, sums, coef, jobs, sym, terms=True):
         gsc = torch.full((_slots() + 1, nt, 8), NAN, device='cuda', dtype=torch.float64)
         gam = torch.full((_slots(), M), NAN, device='cuda', dtype=torch.float64)
         m1 = [torch.full(((jh - jl) * ns,), NAN, device='cuda') for _ in range(M)]
-        m2 = [torch.full((max(1, (jh - mir) * ns),), NAN, device='cuda') for _ in range(M)]
-        if sym:
-            lib.check(L.sga_loss_anchor_multi_bwd_symx(pa(zs), M, p(b), A, p(s), ALPHA, TAU[0], TAU[1], p(cf), pa(m1), pa(m2), p(gsc), p(gam),
-                                                       lo, hi, jl, jh, mir, p(out), st), 'sga_loss_anchor_multi_bwd_symx')
+        m2 = [torch.full(((jh - mir) * ns,), NAN, device='cuda') for _ in range(M)] if mir < jh else None
+        if entry == AA_ORDERED:
+            assert (jl, jh) == (0, A) and m2 is None
+            stash2, where = (), (lo, hi)
         else:
-            assert (jl, jh) == (0, A)
-            lib.check(L.sga_loss_anchor_multi_bwd(pa(zs), M, p(b), A, p(s), ALPHA, TAU[0], TAU[1], p(cf), pa(m1), p(gsc), p(gam), lo, hi,
-                                                  p(out) if terms else None, st), 'sga_loss_anchor_multi_bwd')
+            stash2, where = (pa(m2) if m2 else None,), (lo, hi, jl, jh, mir)
+        lib.check(getattr(L, entry)(pa(tables), M, p(b), *geom, p(s), ALPHA, TAU[0], TAU[1], p(cf), pa(m1), *stash2, p(gsc), p(gam), *where,
+                                    p(out) if terms else None, st), entry)
         for m in range(M):
             new = [(slice(lo, hi), slice(jl, jh), m1[m].view(jh - jl, ns).t())]
-            if sym and mir < jh:
-                new.append((slice(mir, jh), slice(lo, hi), m2[m][:(jh - mir) * ns].view(jh - mir, ns)))
+            if m2:
+                new.append((slice(mir, jh), slice(lo, hi), m2[m].view(jh - mir, ns)))
             for ri, ci, v in new:
                 old = dS[m][ri, ci]
                 seen = ~torch.isnan(old)
                 assert torch.equal(old[seen], v[seen]), 'an element written by two launches of a walk differs'
                 dS[m][ri, ci] = v
-        if terms or sym:
+        if terms:
             acc[0] += out[:n].cpu()
         acc[1] += gsc[0].cpu()
         acc[2] += gam[0].cpu()
@@ -964,7 +970,7 @@ def measure_anchor(name):
     if len(sh) > 1:
         yield _row('anchor_terms.terms', 'f32', sum(run_anchor_fwd(T.zs, c['beta'], A, an['sums'], lo, hi) for lo, hi in sh), *t3)
     for label, jobs, sym in aa_walks(A, M):
-        dS, terms, gs, gam = run_anchor_bwd(T.zs, c['beta'], A, an['sums'], c['coef'], jobs, sym)
+        dS, terms, gs, gam = run_anchor_bwd(AA_SYMX if sym else AA_ORDERED, T.zs, (A,), c['beta'], an['sums'], c['coef'], jobs)
         yield _row('anchor_terms.terms', 'f32', terms, *t3)
         for m in range(M):
             yield _row('anchor_coef.dS', 'f32', dS[m], ref['dS'][m], ref['env_dS'][m], yard['dS'][m])

@@ -12,45 +12,9 @@ import loss_gate as LG
 
 pytestmark = pytest.mark.gpu
 
-ENTRY = 'sga_loss_anchor_multi_bwd_symx_bf16x6'
+ENTRY = LG.AA_PLANES
 GATE = [c['name'] for c in LG.gate_cases() if c['D'] <= 100 and c['M'] in (2, 3)]
 NAN = LG.NAN
-
-
-def run_anchor3(planes, geom, beta, sums, coef, jobs, terms=True):
-    """LG.run_anchor_bwd for the new entry: a whole walk of jobs (lo, hi, j_lo, j_hi, mir) on the images `planes`; a job without mirrored
-    elements (mir >= j_hi) passes M2 == NULL.  Stashes pre-filled with NaN and written into NaN-filled [A, A] matrices: an element no launch
-    produced stays NaN, an element produced twice must agree.  Returns (dS [M][A, A], terms, gs [NT, 8], gamma [M]) summed over the walk."""
-    lib, L, p, pa, st = LG._abi()
-    A = geom[0]
-    M, nt = len(planes), len(planes) + 1
-    n = 3 * M + 1
-    s, b, cf = sums.cuda().contiguous(), beta.cuda(), coef.cuda()
-    dS = [torch.full((A, A), NAN, device='cuda') for _ in range(M)]
-    acc = [torch.zeros(n, dtype=torch.float64), torch.zeros(nt, 8, dtype=torch.float64), torch.zeros(M, dtype=torch.float64)]
-    for lo, hi, jl, jh, mir in jobs:
-        ns = hi - lo
-        out = torch.full((LG._slots() * n,), NAN, device='cuda', dtype=torch.float64)
-        gsc = torch.full((LG._slots() + 1, nt, 8), NAN, device='cuda', dtype=torch.float64)
-        gam = torch.full((LG._slots(), M), NAN, device='cuda', dtype=torch.float64)
-        m1 = [torch.full(((jh - jl) * ns,), NAN, device='cuda') for _ in range(M)]
-        m2 = [torch.full(((jh - mir) * ns,), NAN, device='cuda') for _ in range(M)] if mir < jh else None
-        lib.check(getattr(L, ENTRY)(pa(planes), M, p(b), *geom, p(s), LG.ALPHA, LG.TAU[0], LG.TAU[1], p(cf), pa(m1), pa(m2) if m2 else None, p(gsc), p(gam),
-                                    lo, hi, jl, jh, mir, p(out) if terms else None, st), ENTRY)
-        for m in range(M):
-            new = [(slice(lo, hi), slice(jl, jh), m1[m].view(jh - jl, ns).t())]
-            if m2:
-                new.append((slice(mir, jh), slice(lo, hi), m2[m].view(jh - mir, ns)))
-            for ri, ci, v in new:
-                old = dS[m][ri, ci]
-                seen = ~torch.isnan(old)
-                assert torch.equal(old[seen], v[seen]), 'an element written by two launches of a walk differs'
-                dS[m][ri, ci] = v
-        if terms:
-            acc[0] += out[:n].cpu()
-        acc[1] += gsc[0].cpu()
-        acc[2] += gam[0].cpu()
-    return [d.cpu() for d in dS], acc[0], acc[1], acc[2]
 
 
 @pytest.mark.parametrize('name', GATE)
@@ -68,7 +32,7 @@ def test_gate_at_the_fp32_kernel_s_r(name):
 
     def rows():
         for label, jobs, sym in LG.aa_walks(A, M):
-            dS, terms, gs, gam = run_anchor3(T.t.planes, (A, c['J1'], c['J2']), c['beta'], an['sums'], c['coef'], jobs)
+            dS, terms, gs, gam = LG.run_anchor_bwd(ENTRY, T.t.planes, (A, c['J1'], c['J2']), c['beta'], an['sums'], c['coef'], jobs)
             yield LG._row('anchor_terms.terms', 'f32', terms, *t3)
             for m in range(M):
                 yield LG._row('anchor_coef.dS', 'f32', dS[m], ref['dS'][m], ref['env_dS'][m], yard['dS'][m])
@@ -95,8 +59,8 @@ def _edge(A, M):
 def _against_fp32(A, M, jobs, sym):
     """The new entry against the fp32 entry on the same inputs and jobs: terms 1e-6, stashes 2e-5 of the maximum, the same elements produced."""
     T, sums, beta, coef = _edge(A, M)
-    want = LG.run_anchor_bwd(T.zs, beta, A, sums, coef, jobs, sym)
-    got = run_anchor3(T.t.planes, (A, T.J1, T.J2), beta, sums, coef, jobs)
+    want = LG.run_anchor_bwd(LG.AA_SYMX if sym else LG.AA_ORDERED, T.zs, (A,), beta, sums, coef, jobs)
+    got = LG.run_anchor_bwd(ENTRY, T.t.planes, (A, T.J1, T.J2), beta, sums, coef, jobs)
     for m in range(M):
         assert torch.equal(torch.isnan(got[0][m]), torch.isnan(want[0][m])), 'the two entries produce different elements'
         ok = ~torch.isnan(want[0][m])
@@ -138,8 +102,8 @@ def test_exact_similarities_give_the_fp32_entry_s_stashes():
     T = LG.tier_images(name, 'planes')
     P = LG.tier_images(name, 'plain')
     for label, jobs, sym in LG.aa_walks(A, M):
-        want = LG.run_anchor_bwd(P.zs, c['beta'], A, an['sums'], c['coef'], jobs, sym)[0]
-        got = run_anchor3(T.t.planes, (A, c['J1'], c['J2']), c['beta'], an['sums'], c['coef'], jobs)[0]
+        want = LG.run_anchor_bwd(LG.AA_SYMX if sym else LG.AA_ORDERED, P.zs, (A,), c['beta'], an['sums'], c['coef'], jobs)[0]
+        got = LG.run_anchor_bwd(ENTRY, T.t.planes, (A, c['J1'], c['J2']), c['beta'], an['sums'], c['coef'], jobs)[0]
         for m in range(M):
             assert torch.equal(torch.isnan(got[m]), torch.isnan(want[m]))
             ok = ~torch.isnan(want[m])

@@ -22,7 +22,8 @@ def test_anchor3_kernels_fit_two_waves_per_simd():
     assert {w for w in want if any(w in k for k in ks)} == want, sorted(ks)
     text = open(src).read()
     nop = int(re.search(r'constexpr int A3_NOP = (\d+);', text).group(1))
-    assert re.search(r'const size_t lds = \(size_t\)M \* 2 \* 2 \* A3_NOP \* 1024;', text), 'the launch computes its LDS some other way: update this test'
+    lds = re.search(r'constexpr size_t a3_lds_bytes\(int M\) \{ return \(size_t\)M \* 2 \* 2 \* A3_NOP \* 1024; \}', text)
+    assert lds and 'a3_lds_bytes(M)}' in text[lds.end():], 'the launch computes its LDS some other way: update this test'
     for k, v in ks.items():
         m = int(re.search(r'anchor3_bwd_kernelILi(\d)E', k).group(1))
         print(k, v)

@@ -39,6 +39,30 @@ def test_argument_errors_reported_without_gpu():
     assert rc != 0 and b'multiple of 8' in l.sga_last_error()
 
 
+def test_anchor_backward_entries_share_one_contract():
+    """The three A x A backward entry points (csrc/aa_launch.h) refuse a bad job before they touch a buffer -- host memory here, never
+    dereferenced -- each under its own name: the table count, the row grid, the column tile (16 for fp32, 32 for planes), a symmetric job
+    without out_terms, a mirrored job without M2."""
+    from sgaligner_amd import _lib
+    l = _lib.lib()
+    p = np.zeros(64, dtype=np.float64).ctypes.data
+    arr = (ctypes.c_void_p * 4)(p, p, p, p)
+
+    def call(name, M=3, job=(32, 96, 32, 160, 96), m2=arr, out=p):
+        head = (arr, M, p, 160) + ((5, 5) if name.endswith('bf16x6') else ()) + (p, 0.5, 0.1, 1.0, p, arr)
+        tail = (p, p, *job[:2], out, None) if name.endswith('multi_bwd') else (m2, p, p, *job, out, None)
+        assert getattr(l, name)(*head, *tail) != 0
+        assert l.sga_last_error().startswith(name.encode() + b':'), l.sga_last_error()
+        return l.sga_last_error()
+
+    symx, planes = 'sga_loss_anchor_multi_bwd_symx', 'sga_loss_anchor_multi_bwd_symx_bf16x6'
+    assert b'M=5' in call('sga_loss_anchor_multi_bwd', M=5) and b'M=4' in call(planes, M=4) and b'M=1' in call(symx, M=1)
+    assert b'[170,96)' in call('sga_loss_anchor_multi_bwd', job=(170, 96)) and b'32-column' in call(planes, job=(32, 96, 48, 160, 96))
+    for name in (symx, planes):
+        assert b'32-row' in call(name, job=(8, 96, 32, 160, 96)) and b'out_terms' in call(name, out=None) and b'null table or stash' in call(name, m2=None)
+        assert b'%d-column' % (16 if name == symx else 32) in call(name, job=(32, 96, 32, 160, 104))
+
+
 def test_product_path_has_no_cpu_fallback():
     from sgaligner_amd import ops
     from sgaligner_amd.aligner.sg_aligner import MultiModalEncoder

@@ -146,7 +146,7 @@ def test_symmetric_walk_equals_ordered_walk(mods, stash_rows):
 
 @pytest.mark.parametrize('A,rows,M', [(2100, 512, 3), (1000, 96, 2), (333, 160, 3), (1500, 480, 4), (333, 96, 4)])
 def test_symmetric_kernel_walk_at_the_c_abi(A, rows, M):
-    """sga_loss_anchor_multi_bwd_sym + sga_loss_stash_grad_sym over a whole walk == sga_loss_anchor_multi_bwd + sga_loss_stash_grad:
+    """sga_loss_anchor_multi_bwd_symx + sga_loss_stash_grad_symx (jobs (lo, A, hi)) over a whole walk == sga_loss_anchor_multi_bwd + sga_loss_stash_grad:
     terms, dL/d(sums), dL/dbeta and dZ; ragged last block, A not a multiple of 16, stashes poisoned with NaN beforehand."""
     from sgaligner_amd import _lib
     from sgaligner_amd.ops import _p, _ptr_array, _stream
@@ -175,10 +175,10 @@ def test_symmetric_kernel_walk_at_the_c_abi(A, rows, M):
             m1 = [torch.full(((A - lo if sym else A) * ns,), float('nan'), device=dev) for _ in range(M)]
             if sym:
                 m2 = [torch.full((max(1, (A - hi) * ns),), float('nan'), device=dev) for _ in range(M)]
-                _lib.check(L.sga_loss_anchor_multi_bwd_sym(zarr, M, _p(beta), A, _p(sums), 0.5, 0.1, 1.0, _p(coef), _ptr_array(m1), _ptr_array(m2),
-                                                           _p(gsc), _p(gam2), lo, hi, _p(out), st), 'sym')
+                _lib.check(L.sga_loss_anchor_multi_bwd_symx(zarr, M, _p(beta), A, _p(sums), 0.5, 0.1, 1.0, _p(coef), _ptr_array(m1), _ptr_array(m2),
+                                                            _p(gsc), _p(gam2), lo, hi, lo, A, hi, _p(out), st), 'sym')
                 for k in range(M):
-                    _lib.check(L.sga_loss_stash_grad_sym(_p(m1[k]), _p(m2[k]), _p(zs[k]), A, 104, _p(dz[k]), lo, hi, st), 'stash sym')
+                    _lib.check(L.sga_loss_stash_grad_symx(_p(m1[k]), _p(m2[k]), _p(zs[k]), A, 104, _p(dz[k]), lo, hi, lo, A, hi, st), 'stash sym')
             else:
                 _lib.check(L.sga_loss_anchor_multi_bwd(zarr, M, _p(beta), A, _p(sums), 0.5, 0.1, 1.0, _p(coef), _ptr_array(m1), _p(gsc), _p(gam2),
                                                        lo, hi, _p(out), st), 'ordered')
@@ -201,8 +201,8 @@ def test_symmetric_entry_refuses_blocks_off_the_32_row_grid():
     z = [torch.zeros(2 * 64 + 32, 104, device='cuda') for _ in range(2)]
     d = torch.zeros(4096, device='cuda', dtype=torch.float64)
     f = torch.zeros(64 * 64, device='cuda')
-    rc = L.sga_loss_anchor_multi_bwd_sym(_ptr_array(z), 2, _p(f), 64, _p(d), 0.5, 0.1, 1.0, _p(f), _ptr_array([f, f]), _ptr_array([f, f]),
-                                         _p(d), _p(d), 8, 40, _p(d), _stream())
+    rc = L.sga_loss_anchor_multi_bwd_symx(_ptr_array(z), 2, _p(f), 64, _p(d), 0.5, 0.1, 1.0, _p(f), _ptr_array([f, f]), _ptr_array([f, f]),
+                                          _p(d), _p(d), 8, 40, 8, 64, 40, _p(d), _stream())
     assert rc != 0 and b'32-row' in L.sga_last_error()
 
 

@@ -108,11 +108,11 @@ if M <= 4 and NS % 32 == 0:
     ts, tgs = [], []
     for r in range(reps + 1):
         e[0].record()
-        _lib.check(L.sga_loss_anchor_multi_bwd_sym(zarr, M, _p(beta), A, _p(sums), 0.5, 0.1, 1.0, _p(coef), _ptr_array(m1s), _ptr_array(m2s), _p(gsc), _p(gam2),
-                                                   0, NS, _p(out), st), 'sym')
+        _lib.check(L.sga_loss_anchor_multi_bwd_symx(zarr, M, _p(beta), A, _p(sums), 0.5, 0.1, 1.0, _p(coef), _ptr_array(m1s), _ptr_array(m2s), _p(gsc), _p(gam2),
+                                                    0, NS, 0, A, NS, _p(out), st), 'sym')
         e[1].record()
         for k in range(M):
-            _lib.check(L.sga_loss_stash_grad_sym(_p(m1s[k]), _p(m2s[k]), _p(zs[k]), A, 104, _p(dz[k]), 0, NS, st), 'sgs')
+            _lib.check(L.sga_loss_stash_grad_symx(_p(m1s[k]), _p(m2s[k]), _p(zs[k]), A, 104, _p(dz[k]), 0, NS, 0, A, NS, st), 'sgs')
         e[2].record()
         torch.cuda.synchronize()
         if r:

@@ -1,4 +1,4 @@
-"""Symmetric anchors x anchors walk (sga_loss_anchor_multi_bwd_sym + sga_loss_stash_grad_sym) against the ordinary one
+"""Symmetric anchors x anchors walk (sga_loss_anchor_multi_bwd_symx + sga_loss_stash_grad_symx, jobs (lo, A, hi)) against the ordinary one
 (sga_loss_anchor_multi_bwd + sga_loss_stash_grad) at the C ABI: terms, dL/d(sums), dL/dbeta, dZ of a whole walk; then timing of one block.
   python tools/dbg/aa_sym_check.py [anchors=2100] [rows_per_block=512] [M=3]"""
 import os, sys
@@ -36,10 +36,10 @@ def walk(sym):
         if sym:
             m1 = [torch.full(((A - lo) * ns,), float('nan'), device=dev) for _ in range(M)]
             m2 = [torch.full((max(1, (A - hi) * ns),), float('nan'), device=dev) for _ in range(M)]
-            _lib.check(L.sga_loss_anchor_multi_bwd_sym(zarr, M, _p(beta), A, _p(sums), 0.5, 0.1, 1.0, _p(coef), _ptr_array(m1), _ptr_array(m2),
-                                                       _p(gsc), _p(gam2), lo, hi, _p(out), st), 'sym')
+            _lib.check(L.sga_loss_anchor_multi_bwd_symx(zarr, M, _p(beta), A, _p(sums), 0.5, 0.1, 1.0, _p(coef), _ptr_array(m1), _ptr_array(m2),
+                                                        _p(gsc), _p(gam2), lo, hi, lo, A, hi, _p(out), st), 'sym')
             for k in range(M):
-                _lib.check(L.sga_loss_stash_grad_sym(_p(m1[k]), _p(m2[k]), _p(zs[k]), A, 104, _p(dz[k]), lo, hi, st), 'sgs')
+                _lib.check(L.sga_loss_stash_grad_symx(_p(m1[k]), _p(m2[k]), _p(zs[k]), A, 104, _p(dz[k]), lo, hi, lo, A, hi, st), 'sgs')
         else:
             m1 = [torch.full((A * ns,), float('nan'), device=dev) for _ in range(M)]
             _lib.check(L.sga_loss_anchor_multi_bwd(zarr, M, _p(beta), A, _p(sums), 0.5, 0.1, 1.0, _p(coef), _ptr_array(m1), _p(gsc), _p(gam2),
