@@ -344,6 +344,13 @@ int sga_loss_anchor_multi_bwd_symx_bf16x6(const void* const* Zb, int M, const fl
                                           float alpha, float tau_icl, float tau_ial, const float* coef, float* const* M1, float* const* M2,
                                           double* gs, double* gamma, int a_lo, int a_hi, int j_lo, int j_hi, int mir, double* out_terms,
                                           void* stream);
+/* How an A x A backward job (rows [a_lo, a_hi) x columns [j_lo, j_hi)) is cut into workgroups on `slots` workgroup slots (on a device: CUs x
+ * resident workgroups of the kernel); launches nothing and needs no device.  planes != 0: the three-plane entry point above, else
+ * sga_loss_anchor_multi_bwd / _symx.  plan[8] = {R rows of a row block, H 16-column halves a workgroup walks side by side per step, nib row
+ * blocks, nib1, n1, n2, workgroups, steps of a row block}: workgroup w < nib1 * n1 is (row block w / n1, split w % n1 of n = n1), the
+ * others follow from row block nib1 on with n = n2; split s of n walks the steps s, s + n, ... of its row block, step t being the halves
+ * j_lo / 16 + H t .. + H - 1.  The first run fills whole rounds of workgroups, the second, cut finer, the last one. */
+int sga_loss_anchor_plan(int planes, int M, int A, int a_lo, int a_hi, int j_lo, int j_hi, int slots, int32_t* plan);
 
 /* ---- loss_group = b: the same loss on G independent groups of b consecutive pairs ------------------------
  * replaces the reference trainer feeding b pairs per iteration (configs/scan3r/scan3r_ground_truth.yaml:27,

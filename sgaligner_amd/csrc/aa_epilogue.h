@@ -22,7 +22,16 @@ struct AnchorMultiArgs {
     int j_lo;                      // bwd: first column (a multiple of 16); stash rows are j - j_lo.  0 except in the symmetric mode
     float* M2[4];                  // symmetric mode: M2[m][(j - mir)*ns + (i - i_lo)] = the MIRRORED coefficient dL/dS_m[j,i], j >= mir
     int j_hi, mir;                 // symmetric mode: columns [j_lo, j_hi); tiles at j >= mir also produce the mirrored element (one GPU: A, i_hi)
+    int nib1, nsplit2;             // bwd: row blocks [0, nib1) are cut into nsplit workgroups each, the row blocks behind them into nsplit2 (aa_plan)
 };
+
+// Workgroup -> (row block ib, share `split` of `ns` of its J tiles): the launch plan of aa_launch.h, two runs of row blocks with a split
+// count each.  Workgroup-uniform: scalar registers only.
+__device__ __forceinline__ void aa_unit(const AnchorMultiArgs& a, int& ib, int& split, int& ns) {
+    const int b = blockIdx.x, n1 = a.nib1 * a.nsplit;
+    if (b < n1) { ns = a.nsplit; ib = b / ns; split = b - ib * ns; }
+    else { ns = a.nsplit2; ib = (b - n1) / ns; split = (b - n1) - ib * ns; ib += a.nib1; }
+}
 
 __global__ void inv_sums_kernel(const double* __restrict__ sums, float* __restrict__ inv, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

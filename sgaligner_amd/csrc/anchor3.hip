@@ -50,7 +50,8 @@ __global__ __launch_bounds__(A3_THREADS) void anchor3_bwd_kernel(Anchor3Args A3)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, l15 = lane & 15;
     const int A = a.A, ns = a.i_hi - a.i_lo;
     const int JH = SYM ? a.j_hi : A;
-    const int ib = blockIdx.x / a.nsplit, split = blockIdx.x % a.nsplit;
+    int ib, split, nsp;
+    aa_unit(a, ib, split, nsp);
     const int i0 = a.i_lo + ib * 32;                                  // a multiple of 32: image block i0 >> 5 of both anchor segments
     const int ih = wave & 1, tw = wave >> 1;
     const int my_i = i0 + ih * 16 + l15;
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(A3_THREADS) void anchor3_bwd_kernel(Anchor3Args A3)
     const int aoff = s3_slot(g, l15) * 16;                           // the lane's slot in a [64 slots][16 B] operand image
     const int jt_end = 2 * ((JH + 31) >> 5);                         // 16-row halves: jt = 2 jb + jh
 #pragma unroll 1
-    for (int jt = (a.j_lo >> 4) + split * A3_TW + tw; jt < jt_end; jt += a.nsplit * A3_TW) {
+    for (int jt = (a.j_lo >> 4) + split * A3_TW + tw; jt < jt_end; jt += nsp * A3_TW) {
         const int jb = jt >> 1, jh = jt & 1, j0 = 32 * jb;
         // The own operands are loop invariant; an opaque zero offset keeps their ds_reads inside the loop (as in anchor_multi_bwd16_kernel:
         // hoisted they would take 2 M x 44 registers).
@@ -155,7 +156,8 @@ __global__ __launch_bounds__(A3_THREADS) void anchor3_bwd_kernel(Anchor3Args A3)
 
 template <int M>
 AAKernels<Anchor3Args> anchor3_kernels() {
-    return {anchor3_bwd_kernel<M, true, true>, anchor3_bwd_kernel<M, true, false>, anchor3_bwd_kernel<M, false, false>, 32, A3_TW, a3_lds_bytes(M)};
+    static_assert(aa_geom(true, M).rows == 32 && aa_geom(true, M).shares == A3_TW, "the plan's numbers are this kernel's");
+    return {anchor3_bwd_kernel<M, true, true>, anchor3_bwd_kernel<M, true, false>, anchor3_bwd_kernel<M, false, false>, aa_geom(true, M), a3_lds_bytes(M)};
 }
 
 }  // namespace
@@ -176,6 +178,6 @@ extern "C" int sga_loss_anchor_multi_bwd_symx_bf16x6(const void* const* Zb, int 
     Anchor3Args k{};
     k.nbA = make_tlayout(A, J1, J2).nbA;
     for (int m = 0; m < M; ++m) k.Zb[m] = static_cast<const unsigned char*>(Zb[m]);
-    // 32 anchor rows per workgroup, one workgroup per CU (LDS): ~3 rounds of workgroups, each with at least one tile per wave
-    return aa_run(C, o, k, k.a, M == 2 ? anchor3_kernels<2>() : anchor3_kernels<3>(), A3_THREADS, 3, stream);
+    // 32 anchor rows per workgroup, one workgroup per CU (LDS); how the row blocks are cut into workgroups: aa_plan
+    return aa_run(C, o, k, k.a, M == 2 ? anchor3_kernels<2>() : anchor3_kernels<3>(), A3_THREADS, stream);
 }

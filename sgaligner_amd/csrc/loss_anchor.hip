@@ -181,7 +181,8 @@ __global__ __launch_bounds__(CT_THREADS, 2) void anchor_multi_bwd16_kernel(Ancho
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, l15 = lane & 15;
     const int A = a.A, ns = a.i_hi - a.i_lo;
     const int JH = SYM ? a.j_hi : A;                                 // column end (the symmetric walk of a rank stops where another rank's starts)
-    const int ib = blockIdx.x / a.nsplit, split = blockIdx.x % a.nsplit;
+    int ib, split, nsp;
+    aa_unit(a, ib, split, nsp);
     const int i0 = a.i_lo + ib * RB;
     const int ih = wave % NSUB, tw = wave / NSUB;                    // which 16 anchor rows of the block / which share of the J tiles
     const int my_i = i0 + ih * 16 + l15;
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(CT_THREADS, 2) void anchor_multi_bwd16_kernel(Ancho
 
     const int ntile = (JH + 15) / 16;
 #pragma unroll 1
-    for (int jt = (a.j_lo >> 4) + split * TW + tw; jt < ntile; jt += a.nsplit * TW) {
+    for (int jt = (a.j_lo >> 4) + split * TW + tw; jt < ntile; jt += nsp * TW) {
         const int j0 = jt * 16;
         const int jrow = min(j0 + l15, A - 1);
         // The anchor-row operands are loop invariant; left alone, LICM parks all M*2*26 of them in registers
@@ -301,12 +302,15 @@ extern "C" int sga_loss_anchor_multi_fwd(const float* const* Z, int M, const flo
     aa_fill(a, M, beta, A, sums, alpha, tau_icl, tau_ial, a_lo, a_hi);
     for (int m = 0; m < M; ++m) a.Z[m] = Z[m];
     a.out = out;
-    // 32 anchor rows per workgroup, whose four waves walk 32-row J tiles side by side: ~4 rounds of workgroups
+    // 32 anchor rows per workgroup, whose four waves walk 32-row J tiles side by side: one split count for all row blocks, searched from
+    // ~4 rounds of workgroups up (aa_plan without its second run).  Timed against the split count it had, ceil(4 CUs / row blocks), for
+    // M = 2, 3, 4 and A = 992 .. 38 912 (profiles/aa_fill_forward.txt): equal or faster (M = 3, A = 38 912: 25.2 -> 22.9 ms) except
+    // M = 2, A = 4096, 0.230 -> 0.262 ms.
     const int nib = (a_hi - a_lo + 31) / 32;
-    a.nsplit = aa_plan(nib, (A + 31) / 32, 4, 4);
     const size_t lds = (size_t)(M * 2 * 32 * 104 + (M + 1) * 8) * sizeof(float);
     auto k = M == 2 ? anchor_multi_kernel<2> : M == 3 ? anchor_multi_kernel<3> : anchor_multi_kernel<4>;
     hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    a.nsplit = aa_plan(nib, (A + 31) / 32, 4, aa_slots(reinterpret_cast<const void*>(k), CT_THREADS, lds), 4, false).n1;
     hipLaunchKernelGGL(k, dim3(nib * a.nsplit), dim3(CT_THREADS), lds, s, a);
     fold_slots(out, n, s);
     SGA_CHECK_LAUNCH("sga_loss_anchor_multi_fwd");
@@ -317,7 +321,8 @@ extern "C" int sga_loss_anchor_multi_fwd(const float* const* Z, int M, const flo
 template <int M>
 static AAKernels<AnchorMultiArgs> anchor_multi_bwd_kernels() {
     constexpr int RB = M <= 3 ? 32 : 16;                             // (the kernel's own default)
-    return {anchor_multi_bwd16_kernel<M, true, RB, true>, anchor_multi_bwd16_kernel<M, true>, anchor_multi_bwd16_kernel<M, false>, RB, 64 / RB,
+    static_assert(aa_geom(false, M).rows == RB && aa_geom(false, M).shares == 64 / RB, "the plan's numbers are this kernel's");
+    return {anchor_multi_bwd16_kernel<M, true, RB, true>, anchor_multi_bwd16_kernel<M, true>, anchor_multi_bwd16_kernel<M, false>, aa_geom(false, M),
             (size_t)(M * 2 * RB * 104 + (M + 1) * 8) * sizeof(float)};
 }
 
@@ -326,7 +331,23 @@ static int anchor_multi_bwd(const AAContract& c, const AAOperands& o, const floa
     AnchorMultiArgs a{};
     for (int m = 0; m < o.M; ++m) a.Z[m] = Z[m];
     const auto kern = o.M == 2 ? anchor_multi_bwd_kernels<2>() : o.M == 3 ? anchor_multi_bwd_kernels<3>() : anchor_multi_bwd_kernels<4>();
-    return aa_run(c, o, a, a, kern, CT_THREADS, 6, stream);
+    return aa_run(c, o, a, a, kern, CT_THREADS, stream);
+}
+
+/* The launch plan of an A x A backward job (aa_launch.h: aa_plan) on `slots` workgroup slots, nothing launched and no device asked.
+ * planes != 0: sga_loss_anchor_multi_bwd_symx_bf16x6, else the fp32 entry points.  plan[8] = {rows of a row block, 16-column halves a
+ * workgroup walks side by side per step, row blocks, row blocks of the first run, splits of a row block in the first run, splits in the
+ * second, workgroups, steps of a row block}.  Workgroup w < nib1 * n1 is (row block w / n1, split w % n1 of n1), the others likewise
+ * behind them with n2; split s of n walks the steps s, s + n, ... */
+extern "C" int sga_loss_anchor_plan(int planes, int M, int A, int a_lo, int a_hi, int j_lo, int j_hi, int slots, int32_t* plan) {
+    SGA_CHECK_ARG(plan && slots >= 1 && M >= 2 && M <= (planes ? 3 : 4) && A >= 0 && a_lo >= 0 && a_lo <= a_hi && a_hi <= A && j_lo >= 0 && j_lo <= j_hi &&
+                      j_hi <= A && j_lo % 16 == 0, "sga_loss_anchor_plan: bad argument");
+    const AAGeom g = aa_geom(planes != 0, M);
+    const AAPlan p = aa_job_plan(g, a_lo, a_hi, j_lo, j_hi, slots);
+    const int nib = (a_hi - a_lo + g.rows - 1) / g.rows, ntile16 = ((j_hi + g.col_tile - 1) / g.col_tile * g.col_tile - j_lo) / 16;
+    const int32_t out[8] = {g.rows, g.shares, nib, p.nib1, p.n1, p.n2, j_hi > j_lo ? p.wgs : 0, (ntile16 + g.shares - 1) / g.shares};
+    for (int i = 0; i < 8; ++i) plan[i] = out[i];
+    return SGA_OK;
 }
 
 extern "C" int sga_loss_anchor_multi_bwd(const float* const* Z, int M, const float* beta, int A, const double* sums,
