@@ -496,6 +496,31 @@ int sga_nn_search(const double* pts, const int32_t* offsets, int n_clouds, int t
                   const int32_t* offsets_host, const int32_t* pairs_host, int squared, double* out_dist, int32_t* out_idx,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- batched exact-fp32 nearest-neighbour search in feature space, fp32 matrix cores -------------------------------------------
+ * the matching step of utils/open3d.py:137-170 registration_with_ransac_from_feats (every source descriptor to its nearest reference
+ * descriptor) and of src/engine/registration_evaluator.py:92-127: a GEMM with an arg-min epilogue on v_mfma_f32_32x32x2_f32.
+ * feats [total_rows, C] f32 row-major, feature sets packed back to back, C >= 1 and C % 4 == 0, base 16-byte aligned (pad other widths
+ * with zero columns: they change nothing); offsets [n_sets + 1]; pairs [n_pairs, 2] = (query set, support set); out_offsets [n_pairs]:
+ * where job p's nq results start in out_idx / out_d2 [total_queries] (jobs must not overlap); tiles [n_tiles, 3] = (job, query tile of
+ * 128 rows, chunk): the grid, one workgroup per entry -- every (query tile, chunk) a job has, nothing for those it has not; the first
+ * n_query_tiles entries are the chunk-0 entries (one per query tile of every job), which also drive the closing kernel.  These are
+ * DEVICE int32 arrays; offsets_host / pairs_host / tiles_host (nullable) are host copies that, when given, are validated before anything
+ * is launched.  max_queries / max_support: the largest query / support set of any job (they size the partial workspace; the kernels
+ * re-check every id and offset they read -- a bad one makes a workgroup do nothing, never read or write out of bounds).
+ * Arithmetic: score s_j = n_j - 2 * dot_j in fp32, n_j = |b_j|^2 as an ascending fmaf chain, dot_j the MFMA's k-ordered fmaf chain (the
+ * fixed k order is documented at the top of csrc/featnn.hip): a pure function of the two rows.  out_idx: the support-set-local arg-min
+ * of s_j, the LOWEST index among exactly equal scores; a NaN score never wins; an empty support (or no score below +inf) gives -1.
+ * out_d2 (f64) is recomputed for the chosen row alone: sum_k (double(a_k) - double(b_k))^2, k ascending, each operation rounded on its
+ * own; +inf with -1.  chunk: support rows per workgroup pass.  Jobs with ns <= chunk are finished in one pass; larger ones write
+ * per-chunk (score, idx) partials that are folded in ascending chunk order.  workspace (sga_featnn_workspace_bytes()): 4 bytes x
+ * total_rows for the norms, rounded up to 8, plus 8 bytes x ceil(max_support / chunk) x total_queries when anything is split.  No
+ * atomics: the output is a pure function of the input. */
+size_t sga_featnn_workspace_bytes(int total_rows, int total_queries, int max_support, int chunk);
+int sga_featnn_search(const float* feats, int C, const int32_t* offsets, int n_sets, int total_rows, const int32_t* pairs, int n_pairs,
+                      const int32_t* out_offsets, const int32_t* tiles, int n_tiles, int n_query_tiles, int total_queries, int max_queries,
+                      int max_support, int chunk, const int32_t* offsets_host, const int32_t* pairs_host, const int32_t* tiles_host,
+                      int32_t* out_idx, double* out_d2, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- batched RANSAC rigid registration from point correspondences, fp64 -------------------------------------------------------
  * the estimator of src/engine/registration_evaluator.py:129-208 (pygcransac.findRigidTransform with min_iters == max_iters and
  * spatial_coherence_weight == 0: a fixed number of three-point hypotheses, scored against every correspondence, then least-squares refits

@@ -36,6 +36,8 @@ FILE_FLAGS = {'contrastive.hip': ['-fno-slp-vectorize'],
               'pointnet.hip': ['-fno-slp-vectorize'],
               # nnsearch.hip: every fp64 operation rounded on its own -- the distances are bit-identical to the host KD-tree's (no FMA)
               'nnsearch.hip': ['-ffp-contract=off'],
+              # featnn.hip: the fp64 distance to the chosen row is a sequential sum of separately rounded squares (no FMA)
+              'featnn.hip': ['-ffp-contract=off'],
               # visibility.hip: same -- the frustum tests are bit-identical to the NumPy restatement of the reference's projection
               'visibility.hip': ['-ffp-contract=off']}
 

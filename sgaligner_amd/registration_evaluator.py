@@ -9,7 +9,13 @@ matcher (GeoTransformer in the reference) is not part of this package: it is inj
         {'src_corr_points': [k, 3], 'ref_corr_points': [k, 3], 'corr_scores': [k]}
 
 `run_aligner_registration_batch` runs the matcher for every pair first and then solves all pairs in one launch set -- what a loop over the
-subscan pairs of a scan wants."""
+subscan pairs of a scan wants.
+
+`FeatureMatcher` is a point matcher that ships with the package: nearest neighbours in the space of an injected per-point descriptor
+(`descriptor(points [n, 3]) -> [n, C]`: FPFH, a learned backbone, ... -- computing descriptors is not part of this package), searched on
+the device (csrc/featnn.hip through utils/registration.match_features_pairs).  Besides the call above it has `match_many`, which matches
+a list of pairs in one launch set; `collect_correspondences` uses it when the matcher has it, and `run_normal_registration` /
+`run_registration` (src/engine/registration_evaluator.py:92-127, 211-220), which match the two whole clouds, need it."""
 from __future__ import annotations
 
 import numpy as np
@@ -17,7 +23,39 @@ import numpy as np
 from .utils import registration
 
 
+class FeatureMatcher:
+    """point_matcher by nearest neighbours in descriptor space.  descriptor(points [n, 3] numpy) -> [n, C] array, one row per point.
+    mutual=True keeps the mutual nearest neighbours only.  corr_scores = exp(-d2), d2 the squared descriptor distance: monotone in the
+    distance and in (0, 1]; the evaluator only uses the order of the scores and their mean."""
+
+    def __init__(self, descriptor, mutual=True):
+        if not callable(descriptor):
+            raise TypeError('descriptor must be callable: points [n, 3] -> features [n, C]')
+        self.descriptor = descriptor
+        self.mutual = bool(mutual)
+
+    def match_many(self, list_of_pairs):
+        """[(src_pts, ref_pts), ...] -> [None or {'src_corr_points', 'ref_corr_points', 'corr_scores'}, ...]: every pair matched in one
+        launch set, one download."""
+        pairs = [(np.asarray(s), np.asarray(r)) for s, r in list_of_pairs]
+        if not pairs:
+            return []
+        feats = [tuple(np.ascontiguousarray(self.descriptor(p), dtype=np.float32) for p in pair) for pair in pairs]
+        for (s, r), (fs, fr) in zip(pairs, feats):
+            if fs.ndim != 2 or fr.ndim != 2 or len(fs) != len(s) or len(fr) != len(r):
+                raise ValueError(f'descriptor must return one feature row per point: {fs.shape} for {s.shape}, {fr.shape} for {r.shape}')
+        out = []
+        for (s, r), (cij, d2) in zip(pairs, registration.match_features_pairs(feats, mutual=self.mutual)):
+            cij, d2 = cij.cpu().numpy(), d2.cpu().numpy()
+            out.append(None if len(cij) == 0 else {'src_corr_points': s[cij[:, 0]], 'ref_corr_points': r[cij[:, 1]], 'corr_scores': np.exp(-d2)})
+        return out
+
+    def __call__(self, src_pts, ref_pts, gt_transform=None):
+        return self.match_many([(src_pts, ref_pts)])[0]
+
+
 class RegistrationEvaluator:
+    NORMAL_MAX_POINTS = 10000          # perform_registration's npoint: larger clouds are subsampled before they are matched
     RESULT_KEYS = ('CD', 'IR', 'RRE', 'RTE', 'recall', 'FMR')
 
     def __init__(self, point_matcher, num_p2p_corrs=20000, ransac_threshold=0.03, ransac_iters=5000, inlier_ratio_thresh=0.05,
@@ -50,12 +88,17 @@ class RegistrationEvaluator:
         src_points, ref_points = reg_data_dict['src_points'], reg_data_dict['ref_points']
         src_ids, ref_ids = reg_data_dict['src_plydata']['objectId'], reg_data_dict['ref_plydata']['objectId']
         gt_transform = reg_data_dict['gt_transform']
-        src_rows, ref_rows = [], []
+        src_rows, ref_rows, eligible = [], [], []
         for src_id, ref_id in node_corrs:
             obj_src, obj_ref = src_points[src_ids == src_id], ref_points[ref_ids == ref_id]
             if min(obj_src.shape[0], obj_ref.shape[0]) < self.min_object_points:
                 continue
-            matched = self.point_matcher(obj_src, obj_ref, gt_transform)
+            eligible.append((obj_src, obj_ref))
+        if hasattr(self.point_matcher, 'match_many'):
+            results = self.point_matcher.match_many(eligible)                       # all node pairs of the call in one launch set
+        else:
+            results = (self.point_matcher(obj_src, obj_ref, gt_transform) for obj_src, obj_ref in eligible)
+        for matched in results:
             if matched is None:
                 continue
             src_c, ref_c, scores = (np.asarray(matched[k]) for k in ('src_corr_points', 'ref_corr_points', 'corr_scores'))
@@ -81,6 +124,42 @@ class RegistrationEvaluator:
 
     def _solve(self, corrs):
         return registration.find_rigid_transform_pairs(corrs, threshold=self.ransac_threshold, iters=self.ransac_iters, seed=self.seed)
+
+    def _subsample(self, points, rng):
+        points = np.asarray(points)
+        if points.shape[0] <= self.NORMAL_MAX_POINTS:
+            return points
+        return points[rng.choice(points.shape[0], self.NORMAL_MAX_POINTS, replace=False)]
+
+    def run_normal_registration(self, reg_data_dict, evaluate_registration=True):
+        """src/engine/registration_evaluator.py:92-127: registration of the two WHOLE clouds, without the aligner's node matches.  Each
+        cloud is subsampled to 10 000 rows when larger (numpy.random.default_rng(self.seed)), the matcher's match_many matches them, and
+        the transform is estimated by RANSAC on those correspondences with the evaluator's threshold and iteration count.  (The reference
+        takes GeoTransformer's own estimate, output_dict['estimated_transform'], at this point; a matcher here yields correspondences
+        only.)  -> None (no correspondences or no model), (transform, mean correspondence score) with evaluate_registration=False, or the
+        dict of CD / IR / RRE / RTE / recall / FMR."""
+        if not hasattr(self.point_matcher, 'match_many'):
+            raise TypeError('run_normal_registration matches whole clouds: the point matcher needs match_many (FeatureMatcher has it)')
+        rng = np.random.default_rng(self.seed)
+        src, ref = self._subsample(reg_data_dict['src_points'], rng), self._subsample(reg_data_dict['ref_points'], rng)
+        matched, = self.point_matcher.match_many([(src, ref)])
+        if matched is None:
+            return None
+        corr = np.concatenate([np.asarray(matched['src_corr_points']), np.asarray(matched['ref_corr_points'])], axis=1)
+        (est_transform, _), = self._solve([corr])
+        if est_transform is None:
+            return None
+        if not evaluate_registration:
+            return est_transform, np.mean(matched['corr_scores'])
+        return self._finish(reg_data_dict, corr, est_transform, True)
+
+    def run_registration(self, reg_data_dict):
+        """src/engine/registration_evaluator.py:211-220 -> (normal result dict, aligner result dict), (None, None) when the normal
+        registration yields nothing."""
+        normal = self.run_normal_registration(reg_data_dict)
+        if normal is None:
+            return None, None
+        return normal, self.run_aligner_registration(reg_data_dict)
 
     def run_aligner_registration(self, reg_data_dict, evaluate_registration=True):
         """One scan pair -> None (no correspondences or no model), the 4x4 transform (evaluate_registration=False), or the dict of

@@ -6,7 +6,9 @@ the reference tree further down sys.path (see sgaligner_amd/_dropin.py).
 `sgaligner_amd.utils.point_cloud` also carries the exact nearest-neighbour helpers (get_nearest_neighbor, compute_pcl_overlap[_pairs],
 apply_transform) and `sgaligner_amd.utils.registration` the chamfer / mosaicking / registration metrics built on them (csrc/nnsearch.hip)
 and the estimator those metrics judge: batched RANSAC rigid registration from point correspondences (csrc/ransac.hip) as
-find_rigid_transform[_pairs / _batch], draw_samples, score_hypotheses_batch and registration_with_ransac_from_correspondences.
+find_rigid_transform[_pairs / _batch], draw_samples, score_hypotheses_batch and registration_with_ransac_from_correspondences, and the
+registration from per-point descriptors (csrc/featnn.hip): feature_nn_batch, match_features_pairs, edge_length_filter and
+registration_with_ransac_from_feats[_pairs].
 Neither is aliased: callers import them from `sgaligner_amd.utils...` explicitly."""
 if __name__ == 'utils':
     import os as _os

@@ -2,8 +2,10 @@
 GPU (csrc/nnsearch.hip through utils/point_cloud.py).  The searches return exact fp64 distances -- bit-identical to the KD-tree's -- and
 every mean is taken by numpy on the host from those arrays, so the figures equal the reference's bit for bit.  The transform those
 metrics judge comes from the second half of the file: RANSAC rigid registration from point correspondences, batched over pairs
-(csrc/ransac.hip), with the shift and composition of src/engine/registration_evaluator.py:176-192 around it.  Nothing here falls back to
-the host: without a HIP device the functions that need one raise."""
+(csrc/ransac.hip), with the shift and composition of src/engine/registration_evaluator.py:176-192 around it.  The last part is registration from per-point
+descriptors (utils/open3d.py:137-170): an exact nearest-neighbour search in feature space on the fp32 matrix cores (csrc/featnn.hip),
+the mutual filter and Open3D's edge-length checker as gathers and compares on the device, then the same RANSAC.  Nothing here falls back
+to the host: without a HIP device the functions that need one raise."""
 from __future__ import annotations
 
 import numpy as np
@@ -260,3 +262,209 @@ def registration_with_ransac_from_correspondences(src_points, ref_points, corres
         corr = np.concatenate([src[idx[:, 0]], ref[idx[:, 1]]], axis=1)
     T, _ = find_rigid_transform(corr, threshold=distance_threshold, iters=num_iterations)
     return np.eye(4) if T is None else T
+
+
+# ---- registration from per-point descriptors (utils/open3d.py:137-170; src/engine/registration_evaluator.py:92-127) ----------------------
+FEATNN_CHUNK = None           # support rows per workgroup pass of csrc/featnn.hip; None = chosen per call (_featnn_chunk).  Tests lower it to
+                              # force the split (chunked + folded) form on small inputs.
+FEATNN_QUERY_TILE = 128       # queries per workgroup of featnn_kernel (4 waves x 32)
+FEATNN_SUPPORT_TILE = 128     # support rows per staged LDS tile
+FEATNN_MIN_CHUNK = 1024       # never split a support finer than this: 8 staged tiles, below it the partial workspace and the fold cost
+                              # more than idle CUs
+
+
+def _featnn_chunk(sizes_q, sizes_s) -> int:
+    """Chunk size for a job list, by _nn_chunk's rule: split the supports just far enough that the grid fills the device a few times over
+    (about 4 workgroups per CU -- the kernel keeps two resident), no further: the partial workspace is 8 B x n_chunks x total queries.  A
+    whole number of staged tiles, so that only a support's last tile is ragged."""
+    tiles = int(sum(-(-int(q) // FEATNN_QUERY_TILE) for q in sizes_q)) or 1
+    ns_max = int(max(sizes_s, default=0))
+    want = 4 * int(_lib.lib().sga_device_cus())
+    n_chunks = max(1, min(-(-want // tiles), -(-ns_max // FEATNN_MIN_CHUNK)))
+    chunk = max(FEATNN_MIN_CHUNK, -(-ns_max // n_chunks))
+    return -(-chunk // FEATNN_SUPPORT_TILE) * FEATNN_SUPPORT_TILE
+
+
+def _featnn_tiles(nq, ns, chunk):
+    """The grid of featnn_kernel as a list: (job, query tile, chunk) for every tile a job has; the chunk-0 entries first (they also drive
+    the closing kernel).  -> (tiles [n, 3] int32, number of chunk-0 entries)."""
+    q_tiles = -(-np.asarray(nq, dtype=np.int64) // FEATNN_QUERY_TILE)
+    chunks = np.where(np.asarray(ns) <= chunk, 1, -(-np.asarray(ns, dtype=np.int64) // chunk))
+    job = np.repeat(np.arange(len(q_tiles), dtype=np.int64), q_tiles)
+    qt = np.arange(len(job), dtype=np.int64) - np.repeat(np.cumsum(q_tiles) - q_tiles, q_tiles)
+    reps = chunks[job]
+    c = np.arange(int(reps.sum()), dtype=np.int64) - np.repeat(np.cumsum(reps) - reps, reps)
+    full = np.stack([np.repeat(job, reps), np.repeat(qt, reps), c], axis=1)
+    order = np.argsort(c != 0, kind='stable')
+    return np.ascontiguousarray(full[order], dtype=np.int32), int(len(job))
+
+
+def feature_nn_batch(feats, offsets, pairs, chunk=None):
+    """feats [sum N, C] float32 HIP tensor (feature sets packed back to back), offsets [n_sets+1] host ints, pairs [n_pairs, 2] host ints
+    (query set, support set).  One small upload and one launch set for all jobs.  Returns (idx [sum nq] int32, d2 [sum nq] float64,
+    out_offsets [n_pairs+1] int64 numpy): job p's results are idx[out_offsets[p]:out_offsets[p+1]].  idx is support-set-local: the arg-min
+    of the fp32 score |b|^2 - 2 a.b (csrc/featnn.hip), the LOWEST index among exactly equal scores, -1 for an empty support; d2 is the
+    fp64 squared distance to that row, summed in ascending column order (+inf with -1).  A width that is no multiple of 4 is padded with
+    zero columns, which change neither."""
+    ft = device_tensor(feats, 'feats', torch.float32)
+    if ft.dim() != 2 or ft.shape[1] < 1:
+        raise ValueError(f'feats must be [N, C] with C >= 1, got {tuple(ft.shape)}')
+    off = prefix_offsets(offsets, 'offsets', ft.shape[0])
+    n_sets = len(off) - 1
+    pr = np.ascontiguousarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
+    if pr.size and (pr.min() < 0 or pr.max() >= n_sets):
+        raise ValueError(f'pairs must name sets in [0, {n_sets})')
+    sizes = np.diff(off)
+    nq, ns = sizes[pr[:, 0]], sizes[pr[:, 1]]
+    out_off = np.concatenate([[0], np.cumsum(nq)]).astype(np.int64)
+    total_q = int(out_off[-1])
+    if total_q >= 2 ** 31:
+        raise ValueError('feature_nn_batch indexes with int32: fewer than 2^31 queries per call')
+    from .. import ops
+    if ops.VALIDATE and ft.numel() and not bool(torch.isfinite(ft).all()):
+        raise RuntimeError('sgaligner_amd: `feats` holds NaN or infinite values')
+    dev = ft.device
+    idx = torch.empty((total_q,), device=dev, dtype=torch.int32)
+    d2 = torch.empty((total_q,), device=dev, dtype=torch.float64)
+    if total_q == 0:
+        return idx, d2, out_off
+    if ft.shape[1] % 4:
+        ft = torch.nn.functional.pad(ft, (0, 4 - ft.shape[1] % 4))
+    if ft.data_ptr() % 16:
+        ft = ft.clone()
+    chunk = int(chunk if chunk is not None else FEATNN_CHUNK if FEATNN_CHUNK is not None else _featnn_chunk(nq, ns))
+    if chunk < 1:
+        raise ValueError(f'chunk must be >= 1, got {chunk}')
+    L = _lib.lib()
+    h_tiles, n_qt = _featnn_tiles(nq, ns, chunk)
+    h_off, h_pr, h_oo = off.astype(np.int32), np.ascontiguousarray(pr, dtype=np.int32), out_off[:-1].astype(np.int32)
+    d_off, d_pr, d_oo, d_tiles = upload([h_off, h_pr, h_oo, h_tiles], dev)                   # one small upload
+    total, C = int(ft.shape[0]), int(ft.shape[1])
+    ws_bytes = int(L.sga_featnn_workspace_bytes(total, total_q, int(ns.max()), chunk))
+    ws = torch.empty((max((ws_bytes + 7) // 8, 1),), device=dev, dtype=torch.float64)
+    rc = L.sga_featnn_search(_p(ft), C, _p(d_off), n_sets, total, _p(d_pr), len(pr), _p(d_oo), _p(d_tiles), len(h_tiles), n_qt, total_q,
+                             int(nq.max()), int(ns.max()), chunk, h_off.ctypes.data, h_pr.ctypes.data, h_tiles.ctypes.data, _p(idx), _p(d2),
+                             _p(ws), ws_bytes, _stream())
+    _lib.check(rc, 'sga_featnn_search')
+    return idx, d2, out_off
+
+
+def _feat32(a, name):
+    """One feature set as a float32 [n, C] HIP tensor: a device tensor as it is, a numpy array uploaded; a CPU tensor is refused."""
+    if isinstance(a, torch.Tensor):
+        t = device_tensor(a, name, torch.float32)
+    else:
+        a = np.asarray(a)
+        if a.ndim != 2:
+            raise ValueError(f'{name} must be [n, C], got {a.shape}')
+        _need_device(name)
+        t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    if t.dim() != 2:
+        raise ValueError(f'{name} must be [n, C], got {tuple(t.shape)}')
+    return t
+
+
+def match_features_pairs(list_of_feats, mutual=True):
+    """list_of_feats: [(src_feats [n, C], ref_feats [m, C]), ...] (float32 HIP tensors, or numpy arrays that are uploaded; every set of the
+    call has the same C).  Both directions of every pair go to the device in ONE feature_nn_batch call.  mutual=True keeps (i, j) iff
+    nn(i) = j and nn(j) = i -- a gather and a compare on the device; mutual=False keeps every source row with its nearest reference row
+    (what Open3D's registration_ransac_based_on_feature_matching does when the reference calls it: no mutual filter).  -> per pair
+    (correspondences [k, 2] int64 sorted by source index, d2 [k] float64), HIP tensors."""
+    sets = [_feat32(f, f'list_of_feats[{i}][{j}]') for i, p in enumerate(list_of_feats) for j, f in enumerate(p)]
+    if not sets:
+        return []
+    if len({int(t.shape[1]) for t in sets}) != 1:
+        raise ValueError('every feature set of one call must have the same width')
+    n_pairs = len(sets) // 2
+    off = np.concatenate([[0], np.cumsum([t.shape[0] for t in sets])]).astype(np.int64)
+    pairs = [(2 * p, 2 * p + 1) for p in range(n_pairs)] + ([(2 * p + 1, 2 * p) for p in range(n_pairs)] if mutual else [])
+    idx, d2, oo = feature_nn_batch(torch.cat(sets) if len(sets) > 1 else sets[0], off, pairs)
+    idx = idx.long()
+    out = []
+    for p in range(n_pairs):
+        fwd, dist = idx[oo[p]:oo[p + 1]], d2[oo[p]:oo[p + 1]]
+        keep = fwd >= 0
+        if mutual:
+            back = idx[oo[n_pairs + p]:oo[n_pairs + p + 1]]
+            if back.numel():
+                keep &= back[fwd.clamp(min=0)] == torch.arange(fwd.numel(), device=fwd.device)
+        src = torch.nonzero(keep).reshape(-1)                                        # ascending: sorted by source index
+        out.append((torch.stack([src, fwd[src]], dim=1), dist[src]))
+    return out
+
+
+def edge_length_filter(corr, offsets, samples, hyp_offsets, similarity=0.9):
+    """Open3D's CorrespondenceCheckerBasedOnEdgeLength on a packed hypothesis list, on the device (arguments as find_rigid_transform_batch
+    takes them).  A triple passes iff for each of its three point pairs d_src >= similarity * d_ref and d_ref >= similarity * d_src, d the
+    fp64 distance sqrt((dx*dx + dy*dy) + dz*dz) between the two rows on that side.  A failing triple is overwritten with an invalid one
+    (its first index three times), which sga_ransac_rigid scores 0 and never selects: hypothesis indices keep their meaning.  -> samples
+    [sum H, 3] int32 HIP tensor (a new one)."""
+    cr = device_tensor(corr, 'corr', torch.float64)
+    sm = device_tensor(samples, 'samples', torch.int32).reshape(-1, 3)
+    off = prefix_offsets(offsets, 'offsets', int(cr.shape[0]))
+    hoff = prefix_offsets(hyp_offsets, 'hyp_offsets', int(sm.shape[0]))
+    if len(off) != len(hoff):
+        raise ValueError(f'offsets names {len(off) - 1} jobs, hyp_offsets {len(hoff) - 1}')
+    if sm.shape[0] == 0:
+        return sm.clone()
+    sizes = torch.from_numpy(np.repeat(np.diff(off), np.diff(hoff))).to(cr.device)
+    base = torch.from_numpy(np.repeat(off[:-1], np.diff(hoff))).to(cr.device)
+    local = sm.long()
+    ok = ((local >= 0) & (local < sizes[:, None])).all(dim=1)
+    rows = cr[(local.clamp(min=0) + base[:, None]).clamp(max=max(int(cr.shape[0]) - 1, 0))]      # [H, 3, 6]
+    for a, b in ((0, 1), (1, 2), (2, 0)):
+        d = rows[:, a] - rows[:, b]
+        sq = d * d
+        d_src = torch.sqrt((sq[:, 0] + sq[:, 1]) + sq[:, 2])
+        d_ref = torch.sqrt((sq[:, 3] + sq[:, 4]) + sq[:, 5])
+        ok &= (d_src >= similarity * d_ref) & (d_ref >= similarity * d_src)
+    return torch.where(ok[:, None], sm, sm[:, :1].expand(-1, 3)).contiguous()
+
+
+def registration_with_ransac_from_feats_pairs(list_of_clouds, distance_threshold=0.05, ransac_n=3, num_iterations=50000, val_iterations=1000,
+                                              mutual=False, seed=0):
+    """registration_with_ransac_from_feats for many pairs: list_of_clouds = [(src_points, ref_points, src_feats, ref_feats), ...].  One
+    matching launch set and one RANSAC launch set for all of them.  -> [4x4 transform, ...] in the order given."""
+    if ransac_n != 3:
+        raise ValueError(f'registration_with_ransac_from_feats: only ransac_n == 3 is implemented (got {ransac_n})')
+    _need_device('registration_with_ransac_from_feats')
+    clouds = [(_cloud64(s, f'list_of_clouds[{i}][0]'), _cloud64(r, f'list_of_clouds[{i}][1]'), sf, rf)
+              for i, (s, r, sf, rf) in enumerate(list_of_clouds)]
+    if not clouds:
+        return []
+    for i, (s, r, sf, rf) in enumerate(clouds):
+        if len(s) != len(sf) or len(r) != len(rf):
+            raise ValueError(f'list_of_clouds[{i}]: one feature row per point ({len(s)} / {len(sf)} source, {len(r)} / {len(rf)} reference)')
+    matches = match_features_pairs([(sf, rf) for _, _, sf, rf in clouds], mutual=mutual)
+    dev = matches[0][0].device
+    pts = torch.from_numpy(np.concatenate([np.concatenate([s, r]) for s, r, _, _ in clouds])).to(dev)
+    rows, base = [], 0
+    for (s, r, _, _), (cij, _) in zip(clouds, matches):
+        rows.append(torch.cat([pts[base + cij[:, 0]], pts[base + len(s) + cij[:, 1]]], dim=1))
+        base += len(s) + len(r)
+    sizes = [int(c.shape[0]) for c in rows]
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    samples, hoff = draw_samples(sizes, num_iterations, seed)
+    corr = torch.cat(rows)
+    checked = edge_length_filter(corr, off, torch.from_numpy(samples).to(dev), hoff)
+    res = find_rigid_transform_batch(corr, off, checked, hoff, distance_threshold)
+    status, transform = res['status'].cpu().numpy(), res['transform'].cpu().numpy()
+    return [np.eye(4) if status[j] != 0 else transform[j] for j in range(len(clouds))]
+
+
+def registration_with_ransac_from_feats(src_points, ref_points, src_feats, ref_feats, distance_threshold=0.05, ransac_n=3,
+                                        num_iterations=50000, val_iterations=1000, mutual=False, seed=0):
+    """utils/open3d.py:137-170 (Open3D's registration_ransac_based_on_feature_matching) on the device: the reference signature plus
+    `mutual` and `seed`.  src_points / ref_points [N, 3], src_feats / ref_feats [N, C] (numpy, or float32 HIP tensors for the features).
+    -> 4x4 transform with apply_transform(src, T) ~ ref, identity when no model is found.
+      1. correspondences from match_features_pairs: every source row with its nearest reference row in feature space (mutual=False, as
+         the reference's call), or the mutual nearest neighbours only;
+      2. `num_iterations` sample triples of correspondences from draw_samples (numpy.random.default_rng(seed));
+      3. Open3D's edge-length checker (0.9) on the triples (edge_length_filter), before scoring;
+      4. find_rigid_transform_batch with threshold = distance_threshold.
+    ransac_n != 3 raises.  val_iterations is accepted and unused: the iteration count is fixed, as in
+    registration_with_ransac_from_correspondences.  Open3D's distance checker is an early reject before its costly evaluation; it is not
+    reproduced because every hypothesis is scored in full here.  A model is scored on the feature correspondences (the rows its transform
+    brings within distance_threshold), not on a geometric nearest-neighbour search of all source points as Open3D's evaluation does."""
+    return registration_with_ransac_from_feats_pairs([(src_points, ref_points, src_feats, ref_feats)], distance_threshold, ransac_n,
+                                                     num_iterations, val_iterations, mutual, seed)[0]
