@@ -521,6 +521,51 @@ int sga_featnn_search(const float* feats, int C, const int32_t* offsets, int n_s
                       int max_support, int chunk, const int32_t* offsets_host, const int32_t* pairs_host, const int32_t* tiles_host,
                       int32_t* out_idx, double* out_d2, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- FPFH descriptors: exact neighbour lists, normals, SPFH census, FPFH weighting (fp64; csrc/fpfh.hip) ----------------------------
+ * the descriptor side of utils/open3d.py:61-66 (estimate_normals), :78-86 and :137-170: points -> neighbour lists -> normals -> SPFH -> FPFH,
+ * whose fp32 output feeds sga_featnn_search.  Open3D is not a dependency and equality with its output is not tested: the text below is
+ * the definition (tests/fpfh_ref.py restates it in numpy).  All four entries take clouds packed back to back: pts [total_points, 3] f64,
+ * offsets [n_clouds + 1] DEVICE int32; offsets_host (nullable) is a host copy that, when given, is validated before anything is launched.
+ * The kernels re-check every offset, count and index they read: a bad one makes them do nothing (or skip that neighbour), never read or
+ * write out of bounds.  Neighbours are always taken from the point's own cloud; indices are cloud-local.  1 <= max_nn <= 128 (the lists'
+ * row width in every entry).  No floating-point atomics: every output is a pure function of the input.  Stream-ordered, no workspace.
+ *
+ * sga_knn_lists: for point i the first max_nn entries of { j : d2(i, j) <= r2 } sorted ascending by (d2, j), j over the whole cloud (the
+ * point itself included, d2 = 0).  d2 = (dx*dx + dy*dy) + dz*dz, each operation rounded on its own: sga_nn_search's arithmetic, bit for
+ * bit.  r2 = +inf: pure k-NN.  A NaN distance never enters a list.  count [total] int32; idx [total, max_nn] int32, -1 past count; d2
+ * [total, max_nn] f64, +inf past count.  Brute force, hence exact; meant for clouds of up to about 20 000 points, larger ones are merely slow.
+ *
+ * sga_normals: viewpoints [n_clouds, 3] f64, nullable.  m = count[i].  m < 3, a non-finite coordinate of the point or of a neighbour, or an
+ * index outside the cloud: normal (0, 0, 1), status 1, no orientation (Open3D's rule for too few neighbours).  Otherwise: mean = the sum
+ * in list order / m; the six covariance entries = the sums of (q - mean)_a (q - mean)_b in list order / m; eigenvectors by 8 cyclic Jacobi
+ * sweeps (pairs (0,1), (0,2), (1,2); a pair whose off-diagonal entry is exactly 0 is left alone); normal = the unit eigenvector of the
+ * smallest eigenvalue, the lowest column among exactly equal ones.  Orientation: with a viewpoint v negate when n . (v - p) < 0; without
+ * one negate so that the component of largest magnitude (lowest axis on ties) is positive.  normals [total, 3] f64, status [total] int32.
+ *
+ * sga_spfh_counts: counts [total, 33] int32, all zeros when m <= 1.  For list entries k = 1 .. m-1 (entry 0 is taken to be the point
+ * itself, as Open3D does), p1 the point, p2 the neighbour, n1 / n2 their normals, dp = p2 - p1, d = sqrt(d2_k):  d == 0 -> (f0, f1, f2) =
+ * (0, 0, 0); else a1 = n1.dp / d, a2 = n2.dp / d; if |a1| < |a2|: swap n1 and n2, dp = -dp, f2 = -a2 (Open3D's acos|a1| > acos|a2| up to
+ * the rounding of acos), else f2 = a1; v = dp x n1; |v| == 0 -> (0, 0, 0); else v /= |v|, w = n1 x v, f1 = v.n2, f0 = atan2(w.n2, n1.n2).
+ * Bins b0 = floor(11 (f0 + pi) / 2 pi), b1 = floor(11 (f1 + 1) / 2), b2 = floor(11 (f2 + 1) / 2), each clamped to [0, 10], a NaN to 0;
+ * counts[i, b0], counts[i, 11 + b1], counts[i, 22 + b2] each gain 1.  A neighbour index outside the cloud is skipped, never read.
+ *
+ * sga_fpfh: with s_x[j] = counts[x, j] * (100.0 / (m_x - 1)) (0 when m_x <= 1), for point i and bin group g (columns 11 g .. 11 g + 10):
+ * acc_j = 0, sum_g = 0; for k = 1 .. m-1 ascending, skipping d2_k == 0 and indices outside the cloud, for j ascending within the group:
+ * val = s_{idx_k}[j] / d2_k (the SQUARED distance, as in Open3D), sum_g += val, acc_j += val.  Then if sum_g != 0: acc_j *= 100.0 / sum_g.
+ * out[i, j] = acc_j + s_i[j].  Each operation rounded on its own, in exactly this order.  out64 [total, 33] f64, nullable; out32
+ * [total, ld] f32, ld >= 33 and ld % 4 == 0, the padding columns zero (ld = 36 feeds sga_featnn_search as it is); the f32 values are the
+ * round-to-nearest casts of the f64 values. */
+int sga_knn_lists(const double* pts, const int32_t* offsets, int n_clouds, int total_points, const int32_t* offsets_host, double r2,
+                  int max_nn, int32_t* count, int32_t* idx, double* d2, void* stream);
+int sga_normals(const double* pts, const int32_t* offsets, int n_clouds, int total_points, const int32_t* offsets_host,
+                const int32_t* count, const int32_t* idx, int max_nn, const double* viewpoints, double* normals, int32_t* status,
+                void* stream);
+int sga_spfh_counts(const double* pts, const double* normals, const int32_t* offsets, int n_clouds, int total_points,
+                    const int32_t* offsets_host, const int32_t* count, const int32_t* idx, const double* d2, int max_nn, int32_t* counts,
+                    void* stream);
+int sga_fpfh(const int32_t* counts, const int32_t* offsets, int n_clouds, int total_points, const int32_t* offsets_host,
+             const int32_t* count, const int32_t* idx, const double* d2, int max_nn, double* out64, float* out32, int ld, void* stream);
+
 /* ---- batched RANSAC rigid registration from point correspondences, fp64 -------------------------------------------------------
  * the estimator of src/engine/registration_evaluator.py:129-208 (pygcransac.findRigidTransform with min_iters == max_iters and
  * spatial_coherence_weight == 0: a fixed number of three-point hypotheses, scored against every correspondence, then least-squares refits

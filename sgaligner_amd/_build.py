@@ -38,6 +38,8 @@ FILE_FLAGS = {'contrastive.hip': ['-fno-slp-vectorize'],
               'nnsearch.hip': ['-ffp-contract=off'],
               # featnn.hip: the fp64 distance to the chosen row is a sequential sum of separately rounded squares (no FMA)
               'featnn.hip': ['-ffp-contract=off'],
+              # fpfh.hip: neighbour-list distances bit-identical to nnsearch.hip's, and the FPFH weighting's pinned fp64 operation order (no FMA)
+              'fpfh.hip': ['-ffp-contract=off'],
               # visibility.hip: same -- the frustum tests are bit-identical to the NumPy restatement of the reference's projection
               'visibility.hip': ['-ffp-contract=off']}
 

@@ -72,6 +72,10 @@ SIGNATURES = {
     'sga_nn_search': (I, [P, P, I, I, P, I, P, I, I, I, I, P, P, I, P, P, P, c_size_t, P]),
     'sga_featnn_workspace_bytes': (c_size_t, [I, I, I, I]),
     'sga_featnn_search': (I, [P, I, P, I, I, P, I, P, P, I, I, I, I, I, I, P, P, P, P, P, P, c_size_t, P]),
+    'sga_knn_lists': (I, [P, P, I, I, P, c_double, I, P, P, P, P]),
+    'sga_normals': (I, [P, P, I, I, P, P, P, I, P, P, P, P]),
+    'sga_spfh_counts': (I, [P, P, P, I, I, P, P, P, P, I, P, P]),
+    'sga_fpfh': (I, [P, P, I, I, P, P, P, P, I, P, P, I, P]),
     'sga_ransac_workspace_bytes': (c_size_t, [I, I, I, I]),
     'sga_ransac_rigid': (I, [P, P, I, I, P, P, I, I, I, I, P, P, c_double, I, P, P, P, P, P, P, P, c_size_t, P]),
     'sga_subscan_lds_slots': (I, []),

@@ -13,5 +13,5 @@ void sga_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* sga_last_error(void) { return g_err; }
-extern "C" int sga_version(void) { return 102; }  // 0.1.2: + GAT attention for any head count and width (sga_gat_attn_*_hc)
+extern "C" int sga_version(void) { return 103; }  // 0.1.3: + FPFH descriptors (sga_knn_lists, sga_normals, sga_spfh_counts, sga_fpfh)
 extern "C" int sga_device_cus(void) { return sga_num_cus(); }

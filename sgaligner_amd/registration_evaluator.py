@@ -12,8 +12,9 @@ matcher (GeoTransformer in the reference) is not part of this package: it is inj
 subscan pairs of a scan wants.
 
 `FeatureMatcher` is a point matcher that ships with the package: nearest neighbours in the space of an injected per-point descriptor
-(`descriptor(points [n, 3]) -> [n, C]`: FPFH, a learned backbone, ... -- computing descriptors is not part of this package), searched on
-the device (csrc/featnn.hip through utils/registration.match_features_pairs).  Besides the call above it has `match_many`, which matches
+(`descriptor(points [n, 3]) -> [n, C]`: `utils.features.FPFHDescriptor`, which ships with the package and computes FPFH on the device
+(csrc/fpfh.hip), a learned backbone, ...), searched on the device (csrc/featnn.hip through utils/registration.match_features_pairs).  A
+descriptor that has `many(list of clouds)` is asked for all clouds of a call at once.  Besides the call above it has `match_many`, which matches
 a list of pairs in one launch set; `collect_correspondences` uses it when the matcher has it, and `run_normal_registration` /
 `run_registration` (src/engine/registration_evaluator.py:92-127, 211-220), which match the two whole clouds, need it."""
 from __future__ import annotations
@@ -40,7 +41,11 @@ class FeatureMatcher:
         pairs = [(np.asarray(s), np.asarray(r)) for s, r in list_of_pairs]
         if not pairs:
             return []
-        feats = [tuple(np.ascontiguousarray(self.descriptor(p), dtype=np.float32) for p in pair) for pair in pairs]
+        if hasattr(self.descriptor, 'many'):                                        # all 2 * len(pairs) clouds in one launch set
+            flat = [np.ascontiguousarray(f, dtype=np.float32) for f in self.descriptor.many([p for pair in pairs for p in pair])]
+            feats = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(pairs))]
+        else:
+            feats = [tuple(np.ascontiguousarray(self.descriptor(p), dtype=np.float32) for p in pair) for pair in pairs]
         for (s, r), (fs, fr) in zip(pairs, feats):
             if fs.ndim != 2 or fr.ndim != 2 or len(fs) != len(s) or len(fr) != len(r):
                 raise ValueError(f'descriptor must return one feature row per point: {fs.shape} for {s.shape}, {fr.shape} for {r.shape}')
