@@ -27,7 +27,7 @@
 #include <math.h>
 
 #include "mfma_tiles.h"
-#include "packed.h"
+#include "pair_jobs.h"
 
 namespace {
 
@@ -35,24 +35,6 @@ constexpr int FN_THREADS = 256;
 constexpr int FN_QTILE = 128;                     // queries per workgroup: 32 per wave
 constexpr int FN_NT = 4;                          // 32-row support sub-tiles per staged tile
 constexpr int FN_STILE = 32 * FN_NT;              // support rows per staged tile
-
-struct FNJob { int q0, nq, s0, ns, oo; bool ok; };
-
-// Everything a workgroup needs to know about job `job`, read from the device arrays and range-checked: a bad id or offset makes the
-// workgroup do nothing instead of reading or writing out of bounds.
-__device__ __forceinline__ FNJob fn_job(const int* __restrict__ off, int n_sets, int total_rows, const int* __restrict__ pairs, int n_pairs,
-                                        const int* __restrict__ out_off, int total_queries, int job) {
-    FNJob j{0, 0, 0, 0, 0, false};
-    if (job < 0 || job >= n_pairs) return j;
-    const int qc = pairs[2 * job], sc = pairs[2 * job + 1];
-    if (qc < 0 || qc >= n_sets || sc < 0 || sc >= n_sets) return j;
-    const int q0 = off[qc], q1 = off[qc + 1], s0 = off[sc], s1 = off[sc + 1], oo = out_off[job];
-    if (q0 < 0 || q1 < q0 || q1 > total_rows || s0 < 0 || s1 < s0 || s1 > total_rows) return j;
-    if (oo < 0 || oo > total_queries || q1 - q0 > total_queries - oo) return j;
-    return FNJob{q0, q1 - q0, s0, s1 - s0, oo, true};
-}
-
-__device__ __forceinline__ int fn_chunks(int ns, int chunk) { return ns <= chunk ? 1 : (int)(((long long)ns + chunk - 1) / chunk); }
 
 // |b|^2 of every packed row: n = fmaf(b_k, b_k, n), k ascending.
 __global__ __launch_bounds__(FN_THREADS) void featnn_norm_kernel(const float* __restrict__ feats, int C, int total_rows, float* __restrict__ norms) {
@@ -105,11 +87,11 @@ __global__ __launch_bounds__(FN_THREADS) void featnn_kernel(const float* __restr
     __shared__ __attribute__((aligned(16))) float sn[2][FN_STILE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int job = tiles[3 * (size_t)blockIdx.x], qt = tiles[3 * (size_t)blockIdx.x + 1], c = tiles[3 * (size_t)blockIdx.x + 2];
-    const FNJob J = fn_job(off, n_sets, total_rows, pairs, n_pairs, out_off, total_queries, job);
+    const SgaPairJob J = sga_pair_job(off, n_sets, total_rows, pairs, n_pairs, out_off, total_queries, job);
     if (!J.ok || qt < 0 || c < 0) return;
     if ((long long)qt * FN_QTILE >= J.nq) return;
     const int qb = qt * FN_QTILE;
-    const int my_chunks = fn_chunks(J.ns, chunk);                           // empty support: one pass that writes -1
+    const int my_chunks = sga_chunks(J.ns, chunk);                           // empty support: one pass that writes -1
     if (c >= my_chunks || c >= n_chunks) return;
     const bool direct = my_chunks == 1;
     if (!direct && (!ws_s || !ws_i)) return;
@@ -176,12 +158,12 @@ __global__ __launch_bounds__(FN_QTILE) void featnn_finish_kernel(const float* __
                                                                  int n_chunks, int chunk, int* __restrict__ out_i, double* __restrict__ out_d,
                                                                  const float* __restrict__ ws_s, const int* __restrict__ ws_i) {
     const int job = tiles[3 * (size_t)blockIdx.x], qt = tiles[3 * (size_t)blockIdx.x + 1], c = tiles[3 * (size_t)blockIdx.x + 2];
-    const FNJob J = fn_job(off, n_sets, total_rows, pairs, n_pairs, out_off, total_queries, job);
+    const SgaPairJob J = sga_pair_job(off, n_sets, total_rows, pairs, n_pairs, out_off, total_queries, job);
     if (!J.ok || qt < 0 || c != 0) return;
     const long long il = (long long)qt * FN_QTILE + threadIdx.x;
     if (il >= J.nq) return;
     const int i = (int)il;
-    const int my_chunks = fn_chunks(J.ns, chunk);
+    const int my_chunks = sga_chunks(J.ns, chunk);
     int bi = -1;
     if (my_chunks > 1) {
         if (!ws_s || !ws_i) return;
@@ -212,14 +194,13 @@ __global__ __launch_bounds__(FN_QTILE) void featnn_finish_kernel(const float* __
     out_d[(size_t)J.oo + i] = d2;
 }
 
-inline long fn_host_chunks(int max_support, int chunk) { return max_support <= chunk ? 1 : ((long)max_support + chunk - 1) / chunk; }
 inline size_t fn_norm_bytes(int total_rows) { return ((size_t)total_rows * sizeof(float) + 7) / 8 * 8; }
 
 }  // namespace
 
 extern "C" size_t sga_featnn_workspace_bytes(int total_rows, int total_queries, int max_support, int chunk) {
     if (total_rows <= 0 || total_queries <= 0 || chunk <= 0) return 0;
-    const long nc = fn_host_chunks(max_support, chunk);                     // the norms are needed even when every support is empty
+    const long nc = sga_chunks(max_support, chunk);                     // the norms are needed even when every support is empty
     return fn_norm_bytes(total_rows) + (nc <= 1 ? 0 : (size_t)nc * (size_t)total_queries * (sizeof(float) + sizeof(int32_t)));
 }
 
@@ -235,8 +216,7 @@ extern "C" int sga_featnn_search(const float* feats, int C, const int32_t* offse
                   "n_tiles %d, n_query_tiles %d)",
                   n_sets, total_rows, n_pairs, total_queries, max_queries, max_support, n_tiles, n_query_tiles);
     SGA_CHECK_ARG(C >= 1 && C % 4 == 0, "sga_featnn_search: C must be a positive multiple of 4 (got %d); pad the rows with zero columns", C);
-    SGA_CHECK_ARG(chunk >= 1, "sga_featnn_search: chunk must be >= 1 (got %d)", chunk);
-    SGA_CHECK_ARG(max_queries <= total_queries, "sga_featnn_search: max_queries %d exceeds total_queries %d", max_queries, total_queries);
+    if (int rc = sga_check_chunked(who, chunk, max_queries, total_queries)) return rc;
     SGA_CHECK_ARG(n_query_tiles <= n_tiles, "sga_featnn_search: n_query_tiles %d exceeds n_tiles %d", n_query_tiles, n_tiles);
     if (n_pairs == 0 || total_queries == 0 || max_queries == 0 || n_tiles == 0) return SGA_OK;               // nothing to write
     SGA_CHECK_ARG(offsets && pairs && out_offsets && tiles && out_idx && out_d2, "sga_featnn_search: null pointer");
@@ -245,17 +225,8 @@ extern "C" int sga_featnn_search(const float* feats, int C, const int32_t* offse
                   "sga_featnn_search: misaligned pointer (feats needs 16 bytes, fp64 arrays and the workspace 8, int32 arrays 4)");
     const SgaPrefix OFFSETS{"offsets", "decrease", "set", "total_rows", nullptr, nullptr};
     if (int rc = sga_check_prefix(who, OFFSETS, offsets_host, n_sets, total_rows, SGA_ANY)) return rc;
-    if (pairs_host) {
-        for (int p = 0; p < n_pairs; ++p) {
-            const int qc = pairs_host[2 * p], sc = pairs_host[2 * p + 1];
-            SGA_CHECK_ARG(qc >= 0 && qc < n_sets && sc >= 0 && sc < n_sets, "sga_featnn_search: pair %d names set (%d, %d) of %d", p, qc, sc, n_sets);
-            if (offsets_host) {
-                SGA_CHECK_ARG(offsets_host[qc + 1] - offsets_host[qc] <= max_queries && offsets_host[sc + 1] - offsets_host[sc] <= max_support,
-                              "sga_featnn_search: pair %d is larger than max_queries %d / max_support %d", p, max_queries, max_support);
-            }
-        }
-    }
-    const long n_chunks = fn_host_chunks(max_support, chunk);
+    if (int rc = sga_check_pairs(who, "set", pairs_host, n_pairs, offsets_host, n_sets, max_queries, max_support)) return rc;
+    const long n_chunks = sga_chunks(max_support, chunk);
     if (tiles_host) {
         for (int t = 0; t < n_tiles; ++t) {
             const int job = tiles_host[3 * (size_t)t], qt = tiles_host[3 * (size_t)t + 1], c = tiles_host[3 * (size_t)t + 2];
@@ -267,10 +238,7 @@ extern "C" int sga_featnn_search(const float* feats, int C, const int32_t* offse
     if (int rc = sga_check_grid(who, n_tiles, 1, 1, "split the job list")) return rc;
     if (int rc = sga_check_grid(who, ((long)total_rows + FN_THREADS - 1) / FN_THREADS, 1, 1, "split the job list")) return rc;
     const size_t need = sga_featnn_workspace_bytes(total_rows, total_queries, max_support, chunk);
-    if (need > 0 && (!workspace || workspace_bytes < need)) {
-        sga_set_error("sga_featnn_search: workspace of %zu bytes needed, %zu given", need, workspace ? workspace_bytes : (size_t)0);
-        return SGA_ERR_WORKSPACE;
-    }
+    if (int rc = sga_check_workspace(who, need, workspace, workspace_bytes)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     float* norms = static_cast<float*>(workspace);
     float* ws_s = n_chunks > 1 ? reinterpret_cast<float*>(static_cast<char*>(workspace) + fn_norm_bytes(total_rows)) : nullptr;

@@ -28,7 +28,7 @@
 #include <limits.h>
 #include <math.h>
 
-#include "packed.h"
+#include "pair_jobs.h"
 
 namespace {
 
@@ -46,9 +46,8 @@ struct FCloud { int o0, n, c; bool ok; };
 
 // Cloud c of the packed array, range-checked.
 __device__ __forceinline__ FCloud fp_cloud(const int* __restrict__ off, int total_points, int c) {
-    const int o0 = off[c], o1 = off[c + 1];
-    if (o0 < 0 || o1 < o0 || o1 > total_points) return FCloud{0, 0, c, false};
-    return FCloud{o0, o1 - o0, c, true};
+    const SgaSegment s = sga_segment(off, total_points, c);
+    return FCloud{s.o0, s.n, c, s.ok};
 }
 
 // The cloud that holds packed point i: the LAST c with offsets[c] <= i (empty clouds repeat an offset), re-checked.

@@ -18,7 +18,7 @@
 // a pure function of the input.
 #include <math.h>
 
-#include "packed.h"
+#include "pair_jobs.h"
 
 namespace {
 
@@ -27,23 +27,8 @@ constexpr int NN_QPL = 4;                         // queries per lane (6 VGPRs o
 constexpr int NN_QTILE = NN_THREADS * NN_QPL;     // queries per workgroup
 constexpr int NN_STILE = 512;                     // support points per LDS tile (12 KiB)
 
-struct NNJob { int q0, nq, s0, ns, oo; bool ok; };
-
-// Everything a workgroup needs to know about job `job`, read from the device arrays and range-checked: a bad id or offset
-// makes the workgroup do nothing instead of reading or writing out of bounds.
-__device__ __forceinline__ NNJob nn_job(const int* __restrict__ off, int n_clouds, int total_points, const int* __restrict__ pairs,
-                                        const int* __restrict__ out_off, int total_queries, int job) {
-    NNJob j{0, 0, 0, 0, 0, false};
-    const int qc = pairs[2 * job], sc = pairs[2 * job + 1];
-    if (qc < 0 || qc >= n_clouds || sc < 0 || sc >= n_clouds) return j;
-    const int q0 = off[qc], q1 = off[qc + 1], s0 = off[sc], s1 = off[sc + 1], oo = out_off[job];
-    if (q0 < 0 || q1 < q0 || q1 > total_points || s0 < 0 || s1 < s0 || s1 > total_points) return j;
-    if (oo < 0 || oo > total_queries || q1 - q0 > total_queries - oo) return j;
-    return NNJob{q0, q1 - q0, s0, s1 - s0, oo, true};
-}
-
 __global__ __launch_bounds__(NN_THREADS) void nn_kernel(const double* __restrict__ pts, const int* __restrict__ off, int n_clouds,
-                                                        int total_points, const int* __restrict__ pairs,
+                                                        int total_points, const int* __restrict__ pairs, int n_pairs,
                                                         const int* __restrict__ out_off, int total_queries, int q_tiles,
                                                         int n_chunks, int chunk, int squared, double* __restrict__ out_d,
                                                         int* __restrict__ out_i, double* __restrict__ ws_d, int* __restrict__ ws_i) {
@@ -53,11 +38,11 @@ __global__ __launch_bounds__(NN_THREADS) void nn_kernel(const double* __restrict
     const int qt = b % q_tiles;
     b /= q_tiles;
     const int c = b % n_chunks, job = b / n_chunks;
-    const NNJob J = nn_job(off, n_clouds, total_points, pairs, out_off, total_queries, job);
+    const SgaPairJob J = sga_pair_job(off, n_clouds, total_points, pairs, n_pairs, out_off, total_queries, job);
     if (!J.ok) return;
     const int qb = qt * NN_QTILE;
     if (qb >= J.nq) return;
-    const int my_chunks = J.ns <= chunk ? 1 : (int)(((long long)J.ns + chunk - 1) / chunk);     // empty support: one pass that writes (+inf, -1)
+    const int my_chunks = sga_chunks(J.ns, chunk);     // empty support: one pass that writes (+inf, -1)
     if (c >= my_chunks) return;
     const int c0 = c * chunk, c1 = (int)min((long long)J.ns, (long long)c0 + chunk);     // c < my_chunks: c * chunk < ns
 
@@ -114,15 +99,15 @@ __global__ __launch_bounds__(NN_THREADS) void nn_kernel(const double* __restrict
 
 // Jobs that were split: fold the chunks' partial minima in ascending chunk order (strict <, so equal minima keep the lower index).
 __global__ __launch_bounds__(NN_THREADS) void nn_merge_kernel(const int* __restrict__ off, int n_clouds, int total_points,
-                                                              const int* __restrict__ pairs, const int* __restrict__ out_off,
+                                                              const int* __restrict__ pairs, int n_pairs, const int* __restrict__ out_off,
                                                               int total_queries, int m_tiles, int n_chunks, int chunk, int squared,
                                                               double* __restrict__ out_d, int* __restrict__ out_i,
                                                               const double* __restrict__ ws_d, const int* __restrict__ ws_i) {
     const int job = blockIdx.x / m_tiles;
     const int i = (blockIdx.x % m_tiles) * NN_THREADS + threadIdx.x;
-    const NNJob J = nn_job(off, n_clouds, total_points, pairs, out_off, total_queries, job);
+    const SgaPairJob J = sga_pair_job(off, n_clouds, total_points, pairs, n_pairs, out_off, total_queries, job);
     if (!J.ok || J.ns <= chunk || i >= J.nq) return;
-    const int my_chunks = (int)min((long long)n_chunks, ((long long)J.ns + chunk - 1) / chunk);   // never past what nn_kernel wrote
+    const int my_chunks = min(n_chunks, sga_chunks(J.ns, chunk));   // never past what nn_kernel wrote
     double bd = INFINITY;
     int bi = -1;
     for (int c = 0; c < my_chunks; ++c) {
@@ -134,13 +119,11 @@ __global__ __launch_bounds__(NN_THREADS) void nn_merge_kernel(const int* __restr
     out_i[(size_t)J.oo + i] = bi;
 }
 
-inline long nn_chunks(int max_support, int chunk) { return max_support <= chunk ? 1 : ((long)max_support + chunk - 1) / chunk; }
-
 }  // namespace
 
 extern "C" size_t sga_nn_workspace_bytes(int total_queries, int max_support, int chunk) {
     if (total_queries <= 0 || max_support <= 0 || chunk <= 0) return 0;
-    const long nc = nn_chunks(max_support, chunk);
+    const long nc = sga_chunks(max_support, chunk);
     return nc <= 1 ? 0 : (size_t)nc * (size_t)total_queries * (sizeof(double) + sizeof(int32_t));
 }
 
@@ -148,45 +131,33 @@ extern "C" int sga_nn_search(const double* pts, const int32_t* offsets, int n_cl
                              const int32_t* out_offsets, int total_queries, int max_queries, int max_support, int chunk,
                              const int32_t* offsets_host, const int32_t* pairs_host, int squared, double* out_dist,
                              int32_t* out_idx, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "sga_nn_search";
     SGA_CHECK_ARG(n_clouds >= 0 && total_points >= 0 && n_pairs >= 0 && total_queries >= 0 && max_queries >= 0 && max_support >= 0,
                   "sga_nn_search: negative count (n_clouds %d, total_points %d, n_pairs %d, total_queries %d, max_queries %d, max_support %d)",
                   n_clouds, total_points, n_pairs, total_queries, max_queries, max_support);
-    SGA_CHECK_ARG(chunk >= 1, "sga_nn_search: chunk must be >= 1 (got %d)", chunk);
-    SGA_CHECK_ARG(max_queries <= total_queries, "sga_nn_search: max_queries %d exceeds total_queries %d", max_queries, total_queries);
+    if (int rc = sga_check_chunked(who, chunk, max_queries, total_queries)) return rc;
     if (n_pairs == 0 || total_queries == 0 || max_queries == 0) return SGA_OK;               // nothing to write
     SGA_CHECK_ARG(offsets && pairs && out_offsets && out_dist && out_idx, "sga_nn_search: null pointer");
     SGA_CHECK_ARG(pts || total_points == 0, "sga_nn_search: null point array");
     SGA_CHECK_ARG(sga_aligned(8, pts, out_dist, workspace) && sga_aligned(4, offsets, pairs, out_offsets, out_idx),
                   "sga_nn_search: misaligned pointer (fp64 arrays need 8 bytes, int32 arrays 4)");
     const SgaPrefix OFFSETS{"offsets", "decrease", "cloud", "total_points", nullptr, nullptr};
-    if (int rc = sga_check_prefix("sga_nn_search", OFFSETS, offsets_host, n_clouds, total_points, SGA_ANY)) return rc;
-    if (pairs_host) {
-        for (int p = 0; p < n_pairs; ++p) {
-            const int qc = pairs_host[2 * p], sc = pairs_host[2 * p + 1];
-            SGA_CHECK_ARG(qc >= 0 && qc < n_clouds && sc >= 0 && sc < n_clouds, "sga_nn_search: pair %d names cloud (%d, %d) of %d", p, qc, sc, n_clouds);
-            if (offsets_host) {
-                SGA_CHECK_ARG(offsets_host[qc + 1] - offsets_host[qc] <= max_queries && offsets_host[sc + 1] - offsets_host[sc] <= max_support,
-                              "sga_nn_search: pair %d is larger than max_queries %d / max_support %d", p, max_queries, max_support);
-            }
-        }
-    }
-    const long n_chunks = nn_chunks(max_support, chunk);
+    if (int rc = sga_check_prefix(who, OFFSETS, offsets_host, n_clouds, total_points, SGA_ANY)) return rc;
+    if (int rc = sga_check_pairs(who, "cloud", pairs_host, n_pairs, offsets_host, n_clouds, max_queries, max_support)) return rc;
+    const long n_chunks = sga_chunks(max_support, chunk);
     const long q_tiles = ((long)max_queries + NN_QTILE - 1) / NN_QTILE, m_tiles = ((long)max_queries + NN_THREADS - 1) / NN_THREADS;
-    if (int rc = sga_check_grid("sga_nn_search", q_tiles, n_chunks, n_pairs, "raise chunk or split the job list")) return rc;
-    if (int rc = sga_check_grid("sga_nn_search", m_tiles, 1, n_pairs, "raise chunk or split the job list")) return rc;
+    if (int rc = sga_check_grid(who, q_tiles, n_chunks, n_pairs, "raise chunk or split the job list")) return rc;
+    if (int rc = sga_check_grid(who, m_tiles, 1, n_pairs, "raise chunk or split the job list")) return rc;
     const size_t need = sga_nn_workspace_bytes(total_queries, max_support, chunk);
-    if (need > 0 && (!workspace || workspace_bytes < need)) {
-        sga_set_error("sga_nn_search: workspace of %zu bytes needed, %zu given", need, workspace ? workspace_bytes : (size_t)0);
-        return SGA_ERR_WORKSPACE;
-    }
+    if (int rc = sga_check_workspace(who, need, workspace, workspace_bytes)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* ws_d = static_cast<double*>(workspace);
     int* ws_i = need ? reinterpret_cast<int*>(ws_d + (size_t)n_chunks * total_queries) : nullptr;
     hipLaunchKernelGGL(nn_kernel, dim3((unsigned)(q_tiles * n_chunks * n_pairs)), dim3(NN_THREADS), 0, s, pts, offsets, n_clouds, total_points,
-                       pairs, out_offsets, total_queries, (int)q_tiles, (int)n_chunks, chunk, squared, out_dist, out_idx, ws_d, ws_i);
+                       pairs, n_pairs, out_offsets, total_queries, (int)q_tiles, (int)n_chunks, chunk, squared, out_dist, out_idx, ws_d, ws_i);
     if (need)
         hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)(m_tiles * n_pairs)), dim3(NN_THREADS), 0, s, offsets, n_clouds, total_points, pairs,
-                           out_offsets, total_queries, (int)m_tiles, (int)n_chunks, chunk, squared, out_dist, out_idx, ws_d, ws_i);
+                           n_pairs, out_offsets, total_queries, (int)m_tiles, (int)n_chunks, chunk, squared, out_dist, out_idx, ws_d, ws_i);
     SGA_CHECK_LAUNCH("sga_nn_search");
     return SGA_OK;
 }

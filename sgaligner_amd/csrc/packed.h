@@ -1,6 +1,6 @@
-// The packed-segment contract of the batched geometry ops (visibility.hip, scenegraph.hip, nnsearch.hip, ransac.hip): segments packed back
-// to back, an [n + 1] int32 prefix array on the device, and a host copy of that array which is checked before anything is launched.
-// The prefix check, pointer alignment, zero-fill and the grid limit, all on the host.
+// The packed-segment contract of the batched geometry ops (visibility.hip, scenegraph.hip, nnsearch.hip, ransac.hip, featnn.hip, fpfh.hip):
+// segments packed back to back, an [n + 1] int32 prefix array on the device, and a host copy of it that is checked before any launch: prefix
+// check, pointer alignment, zero-fill and the grid limit, all on the host.  pair_jobs.h adds the searches' job list and the device lookup.
 #pragma once
 #include "sga_common.h"
 

@@ -24,7 +24,7 @@
 // belongs to it can never disagree.
 #include <math.h>
 
-#include "packed.h"
+#include "pair_jobs.h"
 
 namespace {
 
@@ -46,7 +46,7 @@ struct RSState {            // per job, in the workspace
 
 struct RSJob { int o0, n, h0, nh; bool ok; };
 
-// Rows and hypotheses of job `job`, range-checked: a bad offset makes the caller do nothing instead of touching memory it does not own.
+// Rows and hypotheses of job `job`, range-checked (two sga_segment lookups of pair_jobs.h, written out): a bad offset makes the caller do nothing.
 __device__ __forceinline__ RSJob rs_job(const int* __restrict__ off, int total_rows, const int* __restrict__ hoff, int total_hyp, int job) {
     const int o0 = off[job], o1 = off[job + 1], h0 = hoff[job], h1 = hoff[job + 1];
     if (o0 < 0 || o1 < o0 || o1 > total_rows || h0 < 0 || h1 < h0 || h1 > total_hyp) return RSJob{0, 0, 0, 0, false};
@@ -423,9 +423,6 @@ __global__ __launch_bounds__(RS_THREADS) void ransac_mask_kernel(const double* _
     }
 }
 
-inline long rs_chunks(int max_rows, int chunk) { return max_rows <= chunk ? 1 : ((long)max_rows + chunk - 1) / chunk; }
-inline long rs_rchunks(int max_rows) { return max_rows <= RS_RCHUNK ? 1 : ((long)max_rows + RS_RCHUNK - 1) / RS_RCHUNK; }
-
 struct RSLayout { size_t model, state, partials, counts, total; };
 
 inline RSLayout rs_layout(int n_jobs, int total_hyp, int max_rows, int chunk) {
@@ -433,8 +430,8 @@ inline RSLayout rs_layout(int n_jobs, int total_hyp, int max_rows, int chunk) {
     L.model = 0;
     L.state = L.model + (size_t)12 * total_hyp * sizeof(double);
     L.partials = L.state + (size_t)n_jobs * sizeof(RSState);
-    L.counts = L.partials + (size_t)n_jobs * rs_rchunks(max_rows) * 16 * sizeof(double);
-    L.total = L.counts + (((size_t)rs_chunks(max_rows, chunk) * total_hyp * sizeof(int32_t) + 7) & ~(size_t)7);
+    L.counts = L.partials + (size_t)n_jobs * sga_chunks(max_rows, RS_RCHUNK) * 16 * sizeof(double);
+    L.total = L.counts + (((size_t)sga_chunks(max_rows, chunk) * total_hyp * sizeof(int32_t) + 7) & ~(size_t)7);
     return L;
 }
 
@@ -471,17 +468,14 @@ extern "C" int sga_ransac_rigid(const double* corr, const int32_t* offsets, int 
     const SgaPrefix HYP_OFFSETS{"hyp_offsets", "decrease", "job", "total_hyp", "hypotheses", "max_hyp"};
     if (int rc = sga_check_prefix("sga_ransac_rigid", OFFSETS, offsets_host, n_jobs, total_rows, max_rows)) return rc;
     if (int rc = sga_check_prefix("sga_ransac_rigid", HYP_OFFSETS, hyp_offsets_host, n_jobs, total_hyp, max_hyp)) return rc;
-    const long n_chunks = rs_chunks(max_rows, chunk), r_chunks = rs_rchunks(max_rows);
+    const long n_chunks = sga_chunks(max_rows, chunk), r_chunks = sga_chunks(max_rows, RS_RCHUNK);
     const long h_tiles = ((long)max_hyp + RS_HTILE - 1) / RS_HTILE, g_tiles = ((long)max_hyp + RS_THREADS - 1) / RS_THREADS;
     const char* advice = "raise chunk or split the job list";
     if (int rc = sga_check_grid("sga_ransac_rigid", h_tiles, n_chunks, n_jobs, advice)) return rc;
     if (int rc = sga_check_grid("sga_ransac_rigid", g_tiles, 1, n_jobs, advice)) return rc;
     if (int rc = sga_check_grid("sga_ransac_rigid", r_chunks, 1, n_jobs, advice)) return rc;
     const RSLayout L = rs_layout(n_jobs, total_hyp, max_rows, chunk);
-    if (!workspace || workspace_bytes < L.total) {
-        sga_set_error("sga_ransac_rigid: workspace of %zu bytes needed, %zu given", L.total, workspace ? workspace_bytes : (size_t)0);
-        return SGA_ERR_WORKSPACE;
-    }
+    if (int rc = sga_check_workspace("sga_ransac_rigid", L.total, workspace, workspace_bytes)) return rc;     // L.total > 0: a state per job
     hipStream_t s = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
     double* model = reinterpret_cast<double*>(ws + L.model);

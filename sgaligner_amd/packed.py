@@ -1,7 +1,7 @@
 """The packed-segment contract of the batched geometry ops, host side: segments (objects, clouds, jobs, scans) packed back to back, an
 [n + 1] prefix array that is validated here before the C ABI validates its host copy again (csrc/packed.h), tensors that must already live
-on the device, and small host arrays that travel in ONE upload.  Used by utils/point_cloud.py, utils/registration.py,
-preprocessing/subscans.py and preprocessing/scene_graphs.py."""
+on the device, and small host arrays that travel in ONE upload; on top of it the job list of the nearest-neighbour searches (PairJobs,
+csrc/pair_jobs.h) and the one chunk rule (split_chunk).  Used by utils/point_cloud, registration, features and preprocessing/subscans, scene_graphs."""
 from __future__ import annotations
 
 import numpy as np
@@ -45,13 +45,68 @@ def upload(parts, device):
     return [d_buf[o:o + a.nbytes].view(torch.from_numpy(a[:0]).dtype) for a, o in zip(parts, starts)]
 
 
+def check_finite(t, name: str, noun: str):
+    """The ops.VALIDATE guard of a float device tensor: RuntimeError when it holds a NaN or an infinity (`noun`: "coordinates", "values")."""
+    from . import ops
+    if ops.VALIDATE and t.numel() and not bool(torch.isfinite(t).all()):
+        raise RuntimeError(f'sgaligner_amd: `{name}` holds NaN or infinite {noun}')
+
+
+def workspace(nbytes: int, device):
+    """An 8-byte-aligned device workspace of at least `nbytes` bytes (never empty: its pointer is always valid)."""
+    return torch.empty((max((int(nbytes) + 7) // 8, 1),), device=device, dtype=torch.float64)
+
+
+def split_chunk(tiles, longest, cus, per_cu, min_chunk, round_to=1, whole_rounds=False) -> int:
+    """The one chunk rule of the kernels that split their long axis over workgroups: `tiles` workgroups cover the job list's other axis; the
+    longest segment (`longest` rows) is split just far enough that the grid holds about `per_cu` workgroups per CU, never finer than
+    `min_chunk` rows and in multiples of `round_to`.  whole_rounds: a grid above one workgroup per CU is trimmed to whole rounds of them."""
+    tiles, longest, cus = int(tiles) or 1, int(longest), int(cus)
+    n_chunks = max(1, min(-(-per_cu * cus // tiles), -(-longest // min_chunk)))
+    if whole_rounds and tiles * n_chunks > cus:
+        n_chunks = max(1, (tiles * n_chunks // cus) * cus // tiles)
+    return -(-max(min_chunk, -(-longest // n_chunks)) // round_to) * round_to
+
+
+def resolve_chunk(arg, module_default, rule) -> int:
+    """The caller's `chunk`, else the module's constant (tests set it), else rule(); ValueError below 1."""
+    chunk = int(arg if arg is not None else module_default if module_default is not None else rule())
+    if chunk < 1:
+        raise ValueError(f'chunk must be >= 1, got {chunk}')
+    return chunk
+
+
+class PairJobs:
+    """(query set, support set) jobs over sets packed back to back, what csrc/pair_jobs.h checks again behind the C ABI: off (int64
+    [n_sets + 1] over `total` rows), pr (int64 [n_pairs, 2]), per job nq / ns, out_off (int64 [n_pairs + 1]: job p's results start at
+    out_off[p]), total_q (below 2^31), the int32 host copies h_off / h_pr / h_oo and max_q / max_s.  `what` / `unit` word the refusals."""
+
+    def __init__(self, offsets, total, pairs, what: str, unit: str):
+        self.off = prefix_offsets(offsets, 'offsets', total)
+        self.n_sets = len(self.off) - 1
+        self.pr = np.ascontiguousarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
+        if self.pr.size and (self.pr.min() < 0 or self.pr.max() >= self.n_sets):
+            raise ValueError(f'pairs must name {unit}s in [0, {self.n_sets})')
+        self.nq, self.ns = (np.diff(self.off)[self.pr[:, k]] for k in (0, 1))
+        self.out_off = np.concatenate([[0], np.cumsum(self.nq)]).astype(np.int64)
+        self.n_pairs, self.total_q = len(self.pr), int(self.out_off[-1])
+        if self.total_q >= 2 ** 31:
+            raise ValueError(f'{what} indexes with int32: fewer than 2^31 queries per call')
+        self.h_off, self.h_pr, self.h_oo = self.off.astype(np.int32), self.pr.astype(np.int32), self.out_off[:-1].astype(np.int32)
+        self.max_q, self.max_s = (int(self.nq.max()), int(self.ns.max())) if self.n_pairs else (0, 0)
+
+    def host_parts(self):                                   # what the kernels read, for the caller's ONE upload (it may append its own)
+        return [self.h_off, self.h_pr, self.h_oo]
+
+
 class PackedLayout:
     """Offsets of S scans packed back to back, on the host and on the device.  The base holds the points: pt_off (int64 numpy), h_pt (its
     int32 host copy, what the C ABI checks), total_points, max_points, n_scans.  A subclass adds its second [S + 1] prefix array with
-    _second(), lists in host_parts() the arrays the kernels read, and takes their device views from _device_views()."""
+    _second(), lists in host_parts() the arrays the kernels read, and takes their device views from _device_views().  `name` is what the
+    refusals call the array."""
 
-    def __init__(self, pt_off, total_points=None):
-        self.pt_off = prefix_offsets(pt_off, 'pt_off', total_points)
+    def __init__(self, pt_off, total_points=None, name='pt_off'):
+        self.pt_off = prefix_offsets(pt_off, name, total_points)
         self.h_pt = self.pt_off.astype(np.int32)
         self.n_scans = len(self.pt_off) - 1
         self.total_points, self.max_points = int(self.pt_off[-1]), self._max_len(self.pt_off)

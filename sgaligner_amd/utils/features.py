@@ -17,7 +17,7 @@ import torch
 
 from .. import _lib
 from ..ops import _p, _stream
-from ..packed import check_dtype, device_tensor, prefix_offsets, upload
+from ..packed import PackedLayout, check_dtype, device_tensor, upload
 from .point_cloud import _cloud64, _need_device
 
 MAX_NN = 128          # longest neighbour list of csrc/fpfh.hip
@@ -25,21 +25,21 @@ BINS = 33             # 3 groups of 11
 LD = 36               # row width of the fp32 descriptors: 33 padded to a multiple of 4, what sga_featnn_search reads
 
 
-class _Clouds:
-    """Points and offsets of one call, checked once: pts [total, 3] float64 on the device, off (int64 numpy), h_off (the int32 host copy
-    the C ABI validates), d_off (its device copy: one small upload)."""
+class _Clouds(PackedLayout):
+    """Offsets of one call's clouds, checked once (pt_off, h_pt, n_scans = the clouds, total_points) with their device copy d_off: one small
+    upload.  With `points` it also holds pts [total, 3] float64 on the device; fpfh_from_counts has none and names total and device itself."""
 
-    def __init__(self, points, offsets):
-        self.pts = device_tensor(points, 'points', torch.float64)
-        if self.pts.dim() != 2 or self.pts.shape[1] != 3:
-            raise ValueError(f'points must be [N, 3], got {tuple(self.pts.shape)}')
-        self.off = prefix_offsets(offsets, 'offsets', self.pts.shape[0])
-        self.h_off = self.off.astype(np.int32)
-        self.n_clouds, self.total, self.dev = len(self.off) - 1, int(self.pts.shape[0]), self.pts.device
-        self.d_off, = upload([self.h_off], self.dev)
+    def __init__(self, points, offsets, total=None, device=None):
+        self.pts = None if points is None else device_tensor(points, 'points', torch.float64)
+        if self.pts is not None:
+            if self.pts.dim() != 2 or self.pts.shape[1] != 3:
+                raise ValueError(f'points must be [N, 3], got {tuple(self.pts.shape)}')
+            total, device = self.pts.shape[0], self.pts.device
+        super().__init__(offsets, total, 'offsets')
+        self.dev, (self.d_off,) = device, upload([self.h_pt], device)
 
     def args(self):
-        return _p(self.d_off), self.n_clouds, self.total, self.h_off.ctypes.data
+        return _p(self.d_off), self.n_scans, self.total_points, self.h_pt.ctypes.data
 
 
 def _clouds(points, offsets):
@@ -87,14 +87,14 @@ def neighbour_lists(points, offsets, radius=None, max_nn=30):
     r2 = float('inf') if radius is None else float(radius) * float(radius)
     if not r2 >= 0.0:
         raise ValueError(f'radius must be >= 0 or None, got {radius}')
-    count = torch.empty((C.total,), device=C.dev, dtype=torch.int32)
-    idx = torch.empty((C.total, max_nn), device=C.dev, dtype=torch.int32)
-    d2 = torch.empty((C.total, max_nn), device=C.dev, dtype=torch.float64)
-    if C.total:
+    count = torch.empty((C.total_points,), device=C.dev, dtype=torch.int32)
+    idx = torch.empty((C.total_points, max_nn), device=C.dev, dtype=torch.int32)
+    d2 = torch.empty((C.total_points, max_nn), device=C.dev, dtype=torch.float64)
+    if C.total_points:
         rc = _lib.lib().sga_knn_lists(_p(C.pts), *C.args(), r2, max_nn, _p(count), _p(idx), _p(d2), _stream())
         _lib.check(rc, 'sga_knn_lists')
     out = NeighbourLists((count, idx, d2))
-    out.offsets = C.off
+    out.offsets = C.pt_off
     return out
 
 
@@ -109,18 +109,18 @@ def estimate_normals_batch(points, offsets, radius=None, max_nn=30, viewpoints=N
     C = _clouds(points, offsets)
     if lists is None:
         lists = neighbour_lists(C, None, radius, max_nn)
-    count, idx, _, width = _lists(lists, C.total, C.dev)
+    count, idx, _, width = _lists(lists, C.total_points, C.dev)
     vp = None
     if viewpoints is not None:
         if isinstance(viewpoints, torch.Tensor):
             vp = device_tensor(viewpoints, 'viewpoints', torch.float64)
         else:
             vp = torch.from_numpy(np.ascontiguousarray(viewpoints, dtype=np.float64)).to(C.dev)
-        if tuple(vp.shape) != (C.n_clouds, 3):
-            raise ValueError(f'viewpoints must be [{C.n_clouds}, 3], got {tuple(vp.shape)}')
-    normals = torch.empty((C.total, 3), device=C.dev, dtype=torch.float64)
-    status = torch.empty((C.total,), device=C.dev, dtype=torch.int32)
-    if C.total:
+        if tuple(vp.shape) != (C.n_scans, 3):
+            raise ValueError(f'viewpoints must be [{C.n_scans}, 3], got {tuple(vp.shape)}')
+    normals = torch.empty((C.total_points, 3), device=C.dev, dtype=torch.float64)
+    status = torch.empty((C.total_points,), device=C.dev, dtype=torch.int32)
+    if C.total_points:
         rc = _lib.lib().sga_normals(_p(C.pts), *C.args(), _p(count), _p(idx), width, _p(vp) if vp is not None and vp.numel() else None,
                                     _p(normals), _p(status), _stream())
         _lib.check(rc, 'sga_normals')
@@ -135,11 +135,11 @@ def spfh_counts(points, normals, offsets, lists):
     _list_dtypes(lists)
     C = _clouds(points, offsets)
     nr = device_tensor(normals, 'normals', torch.float64)
-    if tuple(nr.shape) != (C.total, 3):
-        raise ValueError(f'normals must be [{C.total}, 3], got {tuple(nr.shape)}')
-    count, idx, d2, width = _lists(lists, C.total, C.dev)
-    counts = torch.empty((C.total, BINS), device=C.dev, dtype=torch.int32)
-    if C.total:
+    if tuple(nr.shape) != (C.total_points, 3):
+        raise ValueError(f'normals must be [{C.total_points}, 3], got {tuple(nr.shape)}')
+    count, idx, d2, width = _lists(lists, C.total_points, C.dev)
+    counts = torch.empty((C.total_points, BINS), device=C.dev, dtype=torch.int32)
+    if C.total_points:
         rc = _lib.lib().sga_spfh_counts(_p(C.pts), _p(nr), *C.args(), _p(count), _p(idx), _p(d2), width, _p(counts), _stream())
         _lib.check(rc, 'sga_spfh_counts')
     return counts
@@ -159,14 +159,11 @@ def fpfh_from_counts(counts, lists, want_f64=False, offsets=None):
     count, idx, d2, width = _lists(lists, total, dev)
     if offsets is None:
         offsets = getattr(lists, 'offsets', None)
-    off = prefix_offsets([0, total] if offsets is None else offsets, 'offsets', total)
-    h_off = off.astype(np.int32)
-    d_off, = upload([h_off], dev)
+    C = _Clouds(None, [0, total] if offsets is None else offsets, total, dev)
     out32 = torch.empty((total, LD), device=dev, dtype=torch.float32)
     out64 = torch.empty((total, BINS), device=dev, dtype=torch.float64) if want_f64 else None
     if total:
-        rc = _lib.lib().sga_fpfh(_p(cn), _p(d_off), len(off) - 1, total, h_off.ctypes.data, _p(count), _p(idx), _p(d2), width,
-                                 _p(out64) if want_f64 else None, _p(out32), LD, _stream())
+        rc = _lib.lib().sga_fpfh(_p(cn), *C.args(), _p(count), _p(idx), _p(d2), width, _p(out64) if want_f64 else None, _p(out32), LD, _stream())
         _lib.check(rc, 'sga_fpfh')
     return (out32, out64) if want_f64 else out32
 
@@ -182,7 +179,7 @@ def fpfh_batch(points, offsets, normals=None, radius_normal=None, max_nn_normal=
     if normals is None:
         normals, _ = estimate_normals_batch(C, None, radius_normal, max_nn_normal, viewpoints)
     lists = neighbour_lists(C, None, radius_feature, max_nn_feature)
-    return fpfh_from_counts(spfh_counts(C, normals, None, lists), lists, offsets=C.off)
+    return fpfh_from_counts(spfh_counts(C, normals, None, lists), lists, offsets=C.pt_off)
 
 
 def estimate_normals(points, radius=None, max_nn=30, viewpoint=None):

@@ -19,7 +19,7 @@ import torch
 
 from .. import _lib
 from ..ops import _p, _stream
-from ..packed import PackedLayout, check_dtype, device_tensor, prefix_offsets, upload
+from ..packed import PackedLayout, PairJobs, check_dtype, check_finite, device_tensor, prefix_offsets, resolve_chunk, split_chunk, upload, workspace
 
 SMALL_MAX, MID_MAX = 2048, 8192          # register-resident kernel variants (8 / 32 points per lane)
 
@@ -212,13 +212,10 @@ NN_MIN_CHUNK = 2048       # never split a support finer than this: below it the 
 
 
 def _nn_chunk(sizes_q, sizes_s) -> int:
-    """Chunk size for a job list: split the supports just far enough that the grid fills the device a few times over (about 16
-    workgroups per CU), no further -- the partial workspace is 12 B x n_chunks x total queries."""
-    tiles = int(sum(-(-int(q) // NN_QUERY_TILE) for q in sizes_q)) or 1
-    ns_max = int(max(sizes_s, default=0))
-    want = 16 * int(_lib.lib().sga_device_cus())
-    n_chunks = max(1, min(-(-want // tiles), -(-ns_max // NN_MIN_CHUNK)))
-    return max(NN_MIN_CHUNK, -(-ns_max // n_chunks))
+    """Chunk size for a job list, by packed.split_chunk: about 16 workgroups per CU, no further -- the partial workspace is 12 B x n_chunks
+    x total queries."""
+    tiles = sum(-(-int(q) // NN_QUERY_TILE) for q in sizes_q)
+    return split_chunk(tiles, max(sizes_s, default=0), _lib.lib().sga_device_cus(), 16, NN_MIN_CHUNK)
 
 
 def nearest_neighbor_batch(points, offsets, pairs, chunk=None, squared=False):
@@ -230,37 +227,22 @@ def nearest_neighbor_batch(points, offsets, pairs, chunk=None, squared=False):
     pts = device_tensor(points, 'points', torch.float64)
     if pts.dim() != 2 or pts.shape[1] != 3:
         raise ValueError(f'points must be [N,3], got {tuple(pts.shape)}')
-    off = prefix_offsets(offsets, 'offsets', pts.shape[0])
-    n_clouds = len(off) - 1
-    pr = np.ascontiguousarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
-    if pr.size and (pr.min() < 0 or pr.max() >= n_clouds):
-        raise ValueError(f'pairs must name clouds in [0, {n_clouds})')
-    sizes = np.diff(off)
-    nq, ns = sizes[pr[:, 0]], sizes[pr[:, 1]]
-    out_off = np.concatenate([[0], np.cumsum(nq)]).astype(np.int64)
-    total_q = int(out_off[-1])
-    if total_q >= 2 ** 31:
-        raise ValueError('nearest_neighbor_batch indexes with int32: fewer than 2^31 queries per call')
-    from .. import ops
-    if ops.VALIDATE and pts.numel() and not bool(torch.isfinite(pts).all()):
-        raise RuntimeError('sgaligner_amd: `points` holds NaN or infinite coordinates')
+    J = PairJobs(offsets, pts.shape[0], pairs, 'nearest_neighbor_batch', 'cloud')
+    check_finite(pts, 'points', 'coordinates')
     dev = pts.device
-    dist = torch.empty((total_q,), device=dev, dtype=torch.float64)
-    idx = torch.empty((total_q,), device=dev, dtype=torch.int32)
-    if total_q == 0:
-        return dist, idx, out_off
-    chunk = int(chunk if chunk is not None else NN_CHUNK if NN_CHUNK is not None else _nn_chunk(nq, ns))
-    if chunk < 1:
-        raise ValueError(f'chunk must be >= 1, got {chunk}')
+    dist = torch.empty((J.total_q,), device=dev, dtype=torch.float64)
+    idx = torch.empty((J.total_q,), device=dev, dtype=torch.int32)
+    if J.total_q == 0:
+        return dist, idx, J.out_off
+    chunk = resolve_chunk(chunk, NN_CHUNK, lambda: _nn_chunk(J.nq, J.ns))
     L = _lib.lib()
-    h_off, h_pr, h_oo = off.astype(np.int32), np.ascontiguousarray(pr, dtype=np.int32), out_off[:-1].astype(np.int32)
-    d_off, d_pr, d_oo = upload([h_off, h_pr, h_oo], dev)                                      # one small upload
-    ws_bytes = int(L.sga_nn_workspace_bytes(total_q, int(ns.max()), chunk))
-    ws = torch.empty((max((ws_bytes + 7) // 8, 1),), device=dev, dtype=torch.float64)
-    rc = L.sga_nn_search(_p(pts), _p(d_off), n_clouds, int(pts.shape[0]), _p(d_pr), len(pr), _p(d_oo), total_q, int(nq.max()), int(ns.max()),
-                         chunk, h_off.ctypes.data, h_pr.ctypes.data, 1 if squared else 0, _p(dist), _p(idx), _p(ws), ws_bytes, _stream())
+    d_off, d_pr, d_oo = upload(J.host_parts(), dev)                                           # one small upload
+    ws_bytes = int(L.sga_nn_workspace_bytes(J.total_q, J.max_s, chunk))
+    ws = workspace(ws_bytes, dev)
+    rc = L.sga_nn_search(_p(pts), _p(d_off), J.n_sets, int(pts.shape[0]), _p(d_pr), J.n_pairs, _p(d_oo), J.total_q, J.max_q, J.max_s, chunk,
+                         J.h_off.ctypes.data, J.h_pr.ctypes.data, 1 if squared else 0, _p(dist), _p(idx), _p(ws), ws_bytes, _stream())
     _lib.check(rc, 'sga_nn_search')
-    return dist, idx, out_off
+    return dist, idx, J.out_off
 
 
 def _need_device(what: str):

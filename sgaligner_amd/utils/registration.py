@@ -13,7 +13,7 @@ import torch
 
 from .. import _lib
 from ..ops import _p, _stream
-from ..packed import device_tensor, prefix_offsets, upload
+from ..packed import PairJobs, check_finite, device_tensor, prefix_offsets, resolve_chunk, split_chunk, upload, workspace
 from .point_cloud import _cloud64, _need_device, _nn_numpy, apply_transform, get_nearest_neighbor
 
 
@@ -98,17 +98,11 @@ RANSAC_MIN_CHUNK = 128        # never split the rows finer than this: half an LD
 
 
 def _ransac_chunk(sizes_n, sizes_h) -> int:
-    """Chunk size for a job list, by _nn_chunk's rule: split the rows just far enough that the grid fills the device a few times over
-    (about 16 workgroups per CU), no further -- the count workspace is 4 B x n_chunks x total hypotheses.  A grid of more than one
-    workgroup per CU is then trimmed to a whole number of workgroups per CU: the scoring kernel keeps three workgroups resident per CU,
-    and a grid a few workgroups above that (785 on 256 CUs for one 20000 x 5000 job) pays a whole second round for them."""
-    tiles = int(sum(-(-int(h) // RANSAC_HYP_TILE) for h in sizes_h)) or 1
-    n_max = int(max(sizes_n, default=0))
-    cus = int(_lib.lib().sga_device_cus())
-    n_chunks = max(1, min(-(-16 * cus // tiles), -(-n_max // RANSAC_MIN_CHUNK)))
-    if tiles * n_chunks > cus:
-        n_chunks = max(1, (tiles * n_chunks // cus) * cus // tiles)
-    return max(RANSAC_MIN_CHUNK, -(-n_max // n_chunks))
+    """Chunk size for a job list, by packed.split_chunk: about 16 workgroups per CU, no further -- the count workspace is 4 B x n_chunks x
+    total hypotheses -- in whole rounds: the scoring kernel keeps three workgroups resident per CU, and a grid a few workgroups above that
+    (785 on 256 CUs for one 20000 x 5000 job) pays a whole second round for them."""
+    tiles = sum(-(-int(h) // RANSAC_HYP_TILE) for h in sizes_h)
+    return split_chunk(tiles, max(sizes_n, default=0), _lib.lib().sga_device_cus(), 16, RANSAC_MIN_CHUNK, whole_rounds=True)
 
 
 def find_rigid_transform_batch(corr, offsets, samples, hyp_offsets, threshold, refine_rounds=2, chunk=None):
@@ -136,9 +130,7 @@ def find_rigid_transform_batch(corr, offsets, samples, hyp_offsets, threshold, r
         raise ValueError(f'refine_rounds must be >= 0 (or -1: scoring only), got {refine_rounds}')
     if not (np.isfinite(threshold) and threshold >= 0):
         raise ValueError(f'threshold must be finite and >= 0, got {threshold}')
-    from .. import ops
-    if ops.VALIDATE and cr.numel() and not bool(torch.isfinite(cr).all()):
-        raise RuntimeError('sgaligner_amd: `corr` holds NaN or infinite coordinates')
+    check_finite(cr, 'corr', 'coordinates')
     sizes_n, sizes_h = np.diff(off), np.diff(hoff)
     total, total_h = int(cr.shape[0]), int(sm.shape[0])
     out = {'transform': torch.empty((n_jobs, 4, 4), device=dev, dtype=torch.float64),
@@ -149,15 +141,13 @@ def find_rigid_transform_batch(corr, offsets, samples, hyp_offsets, threshold, r
            'hyp_count': torch.empty((total_h,), device=dev, dtype=torch.int32)}
     if n_jobs == 0:
         return out
-    chunk = int(chunk if chunk is not None else RANSAC_CHUNK if RANSAC_CHUNK is not None else _ransac_chunk(sizes_n, sizes_h))
-    if chunk < 1:
-        raise ValueError(f'chunk must be >= 1, got {chunk}')
+    chunk = resolve_chunk(chunk, RANSAC_CHUNK, lambda: _ransac_chunk(sizes_n, sizes_h))
     L = _lib.lib()
     h_off, h_hoff = off.astype(np.int32), hoff.astype(np.int32)
     d_off, d_hoff = upload([h_off, h_hoff], dev)                              # one small upload
     max_n, max_h = int(sizes_n.max()), int(sizes_h.max())
     ws_bytes = int(L.sga_ransac_workspace_bytes(n_jobs, total_h, max_n, chunk))
-    ws = torch.empty((max((ws_bytes + 7) // 8, 1),), device=dev, dtype=torch.float64)
+    ws = workspace(ws_bytes, dev)
     rc = L.sga_ransac_rigid(_p(cr) if total else None, _p(d_off), n_jobs, total, _p(sm) if total_h else None, _p(d_hoff), total_h, max_n, max_h,
                             chunk, h_off.ctypes.data, h_hoff.ctypes.data, threshold, int(refine_rounds), _p(out['transform']),
                             _p(out['inlier_count']), _p(out['best_hyp']), _p(out['status']), _p(out['inlier_mask']) if total else None,
@@ -274,15 +264,10 @@ FEATNN_MIN_CHUNK = 1024       # never split a support finer than this: 8 staged 
 
 
 def _featnn_chunk(sizes_q, sizes_s) -> int:
-    """Chunk size for a job list, by _nn_chunk's rule: split the supports just far enough that the grid fills the device a few times over
-    (about 4 workgroups per CU -- the kernel keeps two resident), no further: the partial workspace is 8 B x n_chunks x total queries.  A
-    whole number of staged tiles, so that only a support's last tile is ragged."""
-    tiles = int(sum(-(-int(q) // FEATNN_QUERY_TILE) for q in sizes_q)) or 1
-    ns_max = int(max(sizes_s, default=0))
-    want = 4 * int(_lib.lib().sga_device_cus())
-    n_chunks = max(1, min(-(-want // tiles), -(-ns_max // FEATNN_MIN_CHUNK)))
-    chunk = max(FEATNN_MIN_CHUNK, -(-ns_max // n_chunks))
-    return -(-chunk // FEATNN_SUPPORT_TILE) * FEATNN_SUPPORT_TILE
+    """Chunk size for a job list, by packed.split_chunk: about 4 workgroups per CU (the kernel keeps two resident), no further -- the partial
+    workspace is 8 B x n_chunks x total queries.  A whole number of staged tiles, so that only a support's last tile is ragged."""
+    tiles = sum(-(-int(q) // FEATNN_QUERY_TILE) for q in sizes_q)
+    return split_chunk(tiles, max(sizes_s, default=0), _lib.lib().sga_device_cus(), 4, FEATNN_MIN_CHUNK, round_to=FEATNN_SUPPORT_TILE)
 
 
 def _featnn_tiles(nq, ns, chunk):
@@ -309,44 +294,29 @@ def feature_nn_batch(feats, offsets, pairs, chunk=None):
     ft = device_tensor(feats, 'feats', torch.float32)
     if ft.dim() != 2 or ft.shape[1] < 1:
         raise ValueError(f'feats must be [N, C] with C >= 1, got {tuple(ft.shape)}')
-    off = prefix_offsets(offsets, 'offsets', ft.shape[0])
-    n_sets = len(off) - 1
-    pr = np.ascontiguousarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
-    if pr.size and (pr.min() < 0 or pr.max() >= n_sets):
-        raise ValueError(f'pairs must name sets in [0, {n_sets})')
-    sizes = np.diff(off)
-    nq, ns = sizes[pr[:, 0]], sizes[pr[:, 1]]
-    out_off = np.concatenate([[0], np.cumsum(nq)]).astype(np.int64)
-    total_q = int(out_off[-1])
-    if total_q >= 2 ** 31:
-        raise ValueError('feature_nn_batch indexes with int32: fewer than 2^31 queries per call')
-    from .. import ops
-    if ops.VALIDATE and ft.numel() and not bool(torch.isfinite(ft).all()):
-        raise RuntimeError('sgaligner_amd: `feats` holds NaN or infinite values')
+    J = PairJobs(offsets, ft.shape[0], pairs, 'feature_nn_batch', 'set')
+    check_finite(ft, 'feats', 'values')
     dev = ft.device
-    idx = torch.empty((total_q,), device=dev, dtype=torch.int32)
-    d2 = torch.empty((total_q,), device=dev, dtype=torch.float64)
-    if total_q == 0:
-        return idx, d2, out_off
+    idx = torch.empty((J.total_q,), device=dev, dtype=torch.int32)
+    d2 = torch.empty((J.total_q,), device=dev, dtype=torch.float64)
+    if J.total_q == 0:
+        return idx, d2, J.out_off
     if ft.shape[1] % 4:
         ft = torch.nn.functional.pad(ft, (0, 4 - ft.shape[1] % 4))
     if ft.data_ptr() % 16:
         ft = ft.clone()
-    chunk = int(chunk if chunk is not None else FEATNN_CHUNK if FEATNN_CHUNK is not None else _featnn_chunk(nq, ns))
-    if chunk < 1:
-        raise ValueError(f'chunk must be >= 1, got {chunk}')
+    chunk = resolve_chunk(chunk, FEATNN_CHUNK, lambda: _featnn_chunk(J.nq, J.ns))
     L = _lib.lib()
-    h_tiles, n_qt = _featnn_tiles(nq, ns, chunk)
-    h_off, h_pr, h_oo = off.astype(np.int32), np.ascontiguousarray(pr, dtype=np.int32), out_off[:-1].astype(np.int32)
-    d_off, d_pr, d_oo, d_tiles = upload([h_off, h_pr, h_oo, h_tiles], dev)                   # one small upload
+    h_tiles, n_qt = _featnn_tiles(J.nq, J.ns, chunk)
+    d_off, d_pr, d_oo, d_tiles = upload(J.host_parts() + [h_tiles], dev)                     # one small upload
     total, C = int(ft.shape[0]), int(ft.shape[1])
-    ws_bytes = int(L.sga_featnn_workspace_bytes(total, total_q, int(ns.max()), chunk))
-    ws = torch.empty((max((ws_bytes + 7) // 8, 1),), device=dev, dtype=torch.float64)
-    rc = L.sga_featnn_search(_p(ft), C, _p(d_off), n_sets, total, _p(d_pr), len(pr), _p(d_oo), _p(d_tiles), len(h_tiles), n_qt, total_q,
-                             int(nq.max()), int(ns.max()), chunk, h_off.ctypes.data, h_pr.ctypes.data, h_tiles.ctypes.data, _p(idx), _p(d2),
-                             _p(ws), ws_bytes, _stream())
+    ws_bytes = int(L.sga_featnn_workspace_bytes(total, J.total_q, J.max_s, chunk))
+    ws = workspace(ws_bytes, dev)
+    rc = L.sga_featnn_search(_p(ft), C, _p(d_off), J.n_sets, total, _p(d_pr), J.n_pairs, _p(d_oo), _p(d_tiles), len(h_tiles), n_qt, J.total_q,
+                             J.max_q, J.max_s, chunk, J.h_off.ctypes.data, J.h_pr.ctypes.data, h_tiles.ctypes.data, _p(idx), _p(d2), _p(ws),
+                             ws_bytes, _stream())
     _lib.check(rc, 'sga_featnn_search')
-    return idx, d2, out_off
+    return idx, d2, J.out_off
 
 
 def _feat32(a, name):
