@@ -36,16 +36,19 @@ int sga_device_cus(void);
 int sga_pointnet_fwd(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
                      const float* w3, const float* b3, float* y, int32_t* argmax, int T, int P, int C3,
                      void* stream);
-/* Same, with a caller-owned workspace of sga_pointnet_fwd_ws_bytes(T, C3) bytes: when the batch has few objects (the reference's
- * own batch sizes, single-pair inference: T < 4 x CUs) every object is split over the 8 waves of a workgroup and the partial
- * (max, arg-max) pairs are folded by a second small kernel -- identical results, per-object latency / 8.  workspace may be NULL
- * (then this is sga_pointnet_fwd). */
+/* Same, with a caller-owned workspace of sga_pointnet_fwd_ws_bytes(T, C3) bytes (the partials buffer): when the batch has few objects of
+ * more than one 32-point tile (the reference's own batch sizes, single-pair inference: T < 4 x CUs and P > 32) every object is split over
+ * the 8 waves of a workgroup and the partial (max, arg-max) pairs are folded by a second small kernel -- identical results, per-object
+ * latency / 8.  workspace may be NULL (then this is sga_pointnet_fwd).  Which form a call takes: sga_pointnet_plan below. */
 size_t sga_pointnet_fwd_ws_bytes(int T, int C3);
 /* mode: the forward's arithmetic.  0 = exact fp32 on v_mfma_f32_32x32x2_f32 (sga_pointnet_fwd is this); 4 = every fp32 operand as THREE exact
  * bf16 terms (8 + 8 + 8 significand bits, fp32's exponent range: the value itself), six bf16 MFMAs per product into fp32 accumulators --
  * fp32 arithmetic on the bf16 matrix pipe, as the default loss sweeps (sga_loss_multi_*_bf16x6), in both launch forms (identical bits);
- * with C3 = 256, T >= 4 x CUs (or no partials workspace) and a workspace of >= 81 920 bytes the kernel keeps the l planes of W2 / W3 there
- * and one workgroup serves whole objects (1.15 x faster).  (pointnet.py:140-161) */
+ * with C3 = 256, a call that is not split (T >= 4 x CUs, or P <= 32, or a workspace smaller than the partials buffer) and a workspace of
+ * >= sga_pointnet_fwd_lg_ws_bytes() = 81 920 bytes, the kernel keeps the l planes of W2 / W3 there and one workgroup serves whole objects
+ * (1.15 x faster).  Any workspace that large will do: a partials buffer offered for a call of P <= 32 serves as that scratch.
+ * (pointnet.py:140-161) */
+size_t sga_pointnet_fwd_lg_ws_bytes(void);
 int sga_pointnet_fwd_ws(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
                         const float* w3, const float* b3, float* y, int32_t* argmax, int T, int P, int C3,
                         void* workspace, size_t ws_bytes, int mode, void* stream);
@@ -57,7 +60,9 @@ int sga_pointnet_fwd_ws(const float* x, const float* w1, const float* b1, const 
  *                     forms mean and variance of the 64 channels from these moments)
  *   [9, 137)          sum z2[c]         [137, 265)          sum z2[c]^2        z2 = W2 relu(z1) + b2
  *   [265, 265 + C3)   sum u[c]          [265 + C3, + 2 C3)  sum u[c]^2         u = z3 - b3 = W3 relu(z2)
- * bn_workspace: sga_pointnet_fwd_bn_ws_bytes(T, C3) bytes, caller-owned.  workspace / ws_bytes as in sga_pointnet_fwd_ws (may be NULL). */
+ * bn_workspace: sga_pointnet_fwd_bn_ws_bytes(T, C3) bytes, caller-owned.  workspace / ws_bytes as in sga_pointnet_fwd_ws (may be NULL).
+ * sga_pointnet_fwd_bn_ws_bytes bounds what every launch form zeroes there (a form that would need more is refused, SGA_ERR_WORKSPACE, before
+ * anything is written). */
 size_t sga_pointnet_fwd_bn_ws_bytes(int T, int C3);
 int sga_pointnet_fwd_bn(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
                         const float* w3, const float* b3, float* y, int32_t* argmax, int T, int P, int C3,
@@ -68,6 +73,32 @@ int sga_pointnet_fwd_bn(const float* x, const float* w1, const float* b1, const 
 int sga_pointnet_bwd(const float* x, const int32_t* argmax, const float* y, const float* gy, const float* w1,
                      const float* b1, const float* w2, const float* b2, const float* w3, float* gw1, float* gb1,
                      float* gw2, float* gb2, float* gw3, float* gb3, int T, int P, int C3, int mode, void* stream);
+/* Which launch form a PointNet call takes -- the launcher's own decision (every condition that chooses a kernel, a grid or a size is in
+ * this one function), for tests that must know what they ran.  Host only: with ncu > 0 (the CU count to plan for) no device is touched;
+ * ncu <= 0 asks the current device.  pass: sga_pointnet_pass (sga_pointnet_fwd / _fwd_ws, sga_pointnet_fwd_bn, sga_pointnet_bwd); ws_bytes:
+ * the bytes of `workspace` the call would offer (0 for none, and for the backward).  plan receives SGA_POINTNET_PLAN_FIELDS int32 (NULL: only
+ * the arguments are checked):
+ *   [0] form (sga_pointnet_form)              [1] workgroups of the main kernel          [2] its dynamic LDS bytes
+ *   [3] what `workspace` holds (sga_pointnet_ws_use)                                     [4] the bytes of it that are used
+ *   [5] bytes of bn_workspace zeroed before the launch (forward with BatchNorm sums only; otherwise 0)
+ *   workgroups of the auxiliary launches, 0 = not launched, in launch order around the main kernel:
+ *   [6] l-plane preparation (before)          [7] combine of the split forms' partials   [8] point moments   [9] BatchNorm reduce
+ * Bad arguments are refused as the entry points refuse them: the message is set, the form is SGA_POINTNET_REFUSED and SGA_ERR_ARG returned. */
+enum sga_pointnet_pass { SGA_POINTNET_FWD = 0, SGA_POINTNET_FWD_BN, SGA_POINTNET_BWD };
+enum sga_pointnet_ws_use { SGA_POINTNET_WS_NONE = 0, SGA_POINTNET_WS_PARTIALS, SGA_POINTNET_WS_LG };
+enum sga_pointnet_form {
+    SGA_POINTNET_EMPTY = 0,       /* T == 0: nothing is launched (the backward still zeroes the gradients) */
+    SGA_POINTNET_F32_WAVE,        /* exact fp32, one wave per object */
+    SGA_POINTNET_F32_SPLIT,       /* exact fp32, one object per workgroup at a time, then the combine kernel */
+    SGA_POINTNET_P3,              /* three planes, one wave per object; at C3 = 256 two half-workgroups share an object */
+    SGA_POINTNET_P3_SPLIT,        /* three planes, split, then the combine kernel */
+    SGA_POINTNET_P3_LG,           /* three planes, C3 = 256, the l planes of W2 / W3 in `workspace` */
+    SGA_POINTNET_BWD_F32,         /* backward, fp32 MFMA: pairs of workgroups */
+    SGA_POINTNET_BWD_P3,          /* backward, three planes: quadruples of workgroups */
+    SGA_POINTNET_REFUSED
+};
+#define SGA_POINTNET_PLAN_FIELDS 10
+int sga_pointnet_plan(int pass, int T, int P, int C3, int mode, size_t ws_bytes, int ncu, int32_t* plan);
 
 /* ---- dense layers -----------------------------------------------------------------------------------
  * C[M,N] (+)= op(A)[M,K] op(B)[K,N] (+ bias[N]);  transX = 0: X stored [rows][K]..., see gemm.hip.

@@ -36,6 +36,8 @@ SIGNATURES = {
     'sga_pointnet_fwd_bn_ws_bytes': (c_size_t, [I, I]),
     'sga_pointnet_fwd_bn': (I, [P, P, P, P, P, P, P, P, P, I, I, I, P, c_size_t, P, c_size_t, P, I, P]),
     'sga_pointnet_bwd': (I, [P] * 15 + [I, I, I, I, P]),
+    'sga_pointnet_fwd_lg_ws_bytes': (c_size_t, []),
+    'sga_pointnet_plan': (I, [I, I, I, I, I, c_size_t, I, P]),
     'sga_gat_complete_flags': (I, [P, P, P, I, P, P]),
     'sga_gat_attn_fwd': (I, [P, P, P, P, P, P, P, I, I, P, P, P, P]),
     'sga_gat_attn_bwd': (I, [P, P, P, P, P, P, P, I, I, P, P, P, P, P]),
@@ -146,6 +148,11 @@ SIGNATURES = {
 # enum sga_gemm_route, in the header's order (sga_gemm_plan's `route`)
 GEMM_ROUTES = ('EMPTY', 'TN_NARROW', 'TN_SPLIT', 'TN_BIG', 'NN', 'NT_128', 'NT_64', 'NT3_128', 'NT3_64', 'SMALL_F32', 'SMALL_F64',
                'GENERIC_F32', 'GENERIC_F64', 'REFUSED')
+# enum sga_pointnet_form / sga_pointnet_pass / sga_pointnet_ws_use, in the header's order (sga_pointnet_plan)
+POINTNET_FORMS = ('EMPTY', 'F32_WAVE', 'F32_SPLIT', 'P3', 'P3_SPLIT', 'P3_LG', 'BWD_F32', 'BWD_P3', 'REFUSED')
+POINTNET_PASSES = ('FWD', 'FWD_BN', 'BWD')
+POINTNET_WS_USES = ('NONE', 'PARTIALS', 'LG')
+POINTNET_PLAN_FIELDS = 10
 
 
 class SgaLibraryError(RuntimeError):

@@ -64,7 +64,7 @@ class PointNetfeat(BaseNetwork):
             w3 = torch.cat([w3, w3.new_zeros((c3k - c3,) + tuple(w3.shape[1:]))])
             b3 = torch.cat([b3, b3.new_zeros(c3k - c3)])
         bn_sums = None
-        if side and ops.pointnet_bn_fusable() and c3k in (64, 128, 256):
+        if side and c3k in (64, 128, 256):
             bn_sums = torch.empty((265 + 2 * c3k,), device=xt.device, dtype=torch.float64)
         y = ops.pointnet(xt.float() if xt.dtype != torch.float32 else xt, self.conv1.weight, self.conv1.bias,
                          self.conv2.weight, self.conv2.bias, w3, b3, bn_sums=bn_sums)

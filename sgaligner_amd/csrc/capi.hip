@@ -13,5 +13,5 @@ void sga_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* sga_last_error(void) { return g_err; }
-extern "C" int sga_version(void) { return 103; }  // 0.1.3: + FPFH descriptors (sga_knn_lists, sga_normals, sga_spfh_counts, sga_fpfh)
+extern "C" int sga_version(void) { return 104; }  // 0.1.4: + the PointNet launch plan (sga_pointnet_plan, sga_pointnet_fwd_lg_ws_bytes)
 extern "C" int sga_device_cus(void) { return sga_num_cus(); }

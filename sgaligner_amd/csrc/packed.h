@@ -1,6 +1,6 @@
 // The packed-segment contract of the batched geometry ops (visibility.hip, scenegraph.hip, nnsearch.hip, ransac.hip, featnn.hip, fpfh.hip):
 // segments packed back to back, an [n + 1] int32 prefix array on the device, and a host copy of it that is checked before any launch: prefix
-// check, pointer alignment, zero-fill and the grid limit, all on the host.  pair_jobs.h adds the searches' job list and the device lookup.
+// check, pointer alignment and the grid limit, all on the host (the zero-fill they share, sga_zero, is sga_common.h's).  pair_jobs.h adds the searches' job list and the device lookup.
 #pragma once
 #include "sga_common.h"
 
@@ -38,15 +38,6 @@ static inline int sga_check_prefix(const char* who, const SgaPrefix& d, const in
 // Every pointer of the list sits on a multiple of `bytes` (a null pointer does).
 template <typename... P>
 static inline bool sga_aligned(size_t bytes, const P*... p) { return ((((uintptr_t)p % bytes) == 0) && ...); }
-
-// Zero `bytes` bytes of device memory on `stream`.
-static inline int sga_zero(const char* who, void* p, size_t bytes, hipStream_t stream) {
-    if (hipMemsetAsync(p, 0, bytes, stream) != hipSuccess) {
-        sga_set_error("%s: memset failed", who);
-        return SGA_ERR_HIP;
-    }
-    return SGA_OK;
-}
 
 // A one-dimensional grid of tiles x chunks x n workgroups (chunks = 1 where nothing is split) holds fewer than 2^31 of them; `advice`
 // says what the caller can do about a larger one.

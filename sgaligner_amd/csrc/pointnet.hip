@@ -679,166 +679,7 @@ __global__ __launch_bounds__(256) void pointnet_p3_lplanes_kernel(const float* _
     out[d] = pl;
 }
 
-// Forward arithmetic, chosen PER CALL (the library keeps no mode): 0 = exact fp32 (v_mfma_f32_32x32x2_f32); 4 = three exact bf16 planes, six
-// bf16 MFMAs per product (fp32 arithmetic on the bf16 matrix pipe; both launch forms).
-template <int C3>
-int launch_fwd(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
-               const float* w3, const float* b3, float* y, int* argmax, int T, int P, hipStream_t stream,
-               void* workspace, size_t ws_bytes, int mode, double* bn_part = nullptr, double* bn_out = nullptr) {
-    const size_t lds_bytes = (size_t)(8192 + C3 * 128) * sizeof(float);
-    int grid = (T + PN_WAVES - 1) / PN_WAVES;
-    const int ncu = sga_num_cus();
-    if (grid > ncu) grid = ncu;
-    const bool split_small = workspace && ws_bytes >= (size_t)T * PN_WAVES * C3 * sizeof(float2) && T < 4 * ncu && P > 32;
-    // mode 4: three exact bf16 planes (pointnet_fwd_p3_kernel); at C3 = 256 a workgroup holds half of W3's channels, two share an object
-    constexpr int P3_HALVES = C3 == 256 ? 2 : 1;
-    const size_t p3_lds = (size_t)(3 * 16 * 64 + 3 * (C3 / P3_HALVES / 32) * 8 * 64) * 16;
-    const int p3_slots_max = P3_HALVES == 2 ? (ncu / 2 > 0 ? ncu / 2 : 1) : ncu;
-    const int p3_want = split_small ? T : grid;              // split form: one object per workgroup (pair) at a time
-    // C3 = 256, many objects, a scratch of PN_P3_LG_BYTES in `workspace`: one workgroup per object, the l planes from global memory (LG)
-    const bool p3_lg = C3 == 256 && !split_small && workspace && ws_bytes >= PN_P3_LG_BYTES;
-    const int p3_grid = p3_lg ? grid : P3_HALVES * (p3_want < p3_slots_max ? p3_want : p3_slots_max);
-    auto go_p3 = [&](double* bnp) {
-        if constexpr (C3 == 256) {
-            if (p3_lg) {
-                u32x4* wlg = static_cast<u32x4*>(workspace);
-                hipLaunchKernelGGL(pointnet_p3_lplanes_kernel<C3>, dim3((1024 + 8 * 512 + 255) / 256), dim3(256), 0, stream, w2, w3, wlg);
-                const size_t lg_lds = (size_t)(2 * 16 * 64 + 2 * 8 * 8 * 64) * 16;
-                auto launch = [&](auto k) {
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lg_lds);
-                    hipLaunchKernelGGL(k, dim3(p3_grid), dim3(PN_THREADS), lg_lds, stream, x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, bnp, static_cast<float2*>(nullptr),
-                                       static_cast<const u32x4*>(wlg));
-                };
-                if (bnp) { if (argmax) launch(pointnet_fwd_p3_kernel<C3, true, true, false, true>); else launch(pointnet_fwd_p3_kernel<C3, false, true, false, true>); }
-                else { if (argmax) launch(pointnet_fwd_p3_kernel<C3, true, false, false, true>); else launch(pointnet_fwd_p3_kernel<C3, false, false, false, true>); }
-                return;
-            }
-        }
-        float2* part = split_small ? static_cast<float2*>(workspace) : nullptr;
-        auto launch = [&](auto k) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p3_lds);
-            hipLaunchKernelGGL(k, dim3(p3_grid), dim3(PN_THREADS), p3_lds, stream, x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, bnp, part, static_cast<const u32x4*>(nullptr));
-        };
-        if (split_small) {
-            if (bnp) { if (argmax) launch(pointnet_fwd_p3_kernel<C3, true, true, true>); else launch(pointnet_fwd_p3_kernel<C3, false, true, true>); }
-            else { if (argmax) launch(pointnet_fwd_p3_kernel<C3, true, false, true>); else launch(pointnet_fwd_p3_kernel<C3, false, false, true>); }
-            hipLaunchKernelGGL(pointnet_combine_kernel, dim3((T * C3 + 255) / 256), dim3(256), 0, stream, part, b3, y, argmax, T, C3, P);
-        } else {
-            if (bnp) { if (argmax) launch(pointnet_fwd_p3_kernel<C3, true, true>); else launch(pointnet_fwd_p3_kernel<C3, false, true>); }
-            else { if (argmax) launch(pointnet_fwd_p3_kernel<C3, true, false>); else launch(pointnet_fwd_p3_kernel<C3, false, false>); }
-        }
-    };
-    if (bn_out) {
-        // the forward with the batch statistics of the three pre-activations (the reference's BatchNorm side effect): exact fp32 or mode 4
-        const bool p3 = mode == 4;
-        const bool split = split_small && !p3;
-        const int g = p3 ? p3_grid : split ? (T < ncu ? T : ncu) : grid;
-        float2* part = split ? static_cast<float2*>(workspace) : nullptr;
-        if (hipError_t me = hipMemsetAsync(bn_part, 0, (size_t)g * PN_WAVES * (9 + 8 + 2 * (C3 / 32)) * 64 * sizeof(double), stream); me != hipSuccess) {
-            sga_set_error("sga_pointnet_fwd_bn: memset of %zu bytes at %p failed: %s", (size_t)g * PN_WAVES * (9 + 8 + 2 * (C3 / 32)) * 64 * sizeof(double), (void*)bn_part, hipGetErrorString(me));
-            return SGA_ERR_HIP;
-        }
-        auto go = [&](auto k) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-            hipLaunchKernelGGL(k, dim3(g), dim3(PN_THREADS), lds_bytes, stream, x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, part, bn_part);
-        };
-        if (p3) go_p3(bn_part);
-        else if (split) { if (argmax) go(pointnet_fwd_kernel<C3, true, true, true>); else go(pointnet_fwd_kernel<C3, false, true, true>); }
-        else { if (argmax) go(pointnet_fwd_kernel<C3, true, false, true>); else go(pointnet_fwd_kernel<C3, false, false, true>); }
-        if (split) hipLaunchKernelGGL(pointnet_combine_kernel, dim3((T * C3 + 255) / 256), dim3(256), 0, stream, part, b3, y, argmax, T, C3, P);
-        hipLaunchKernelGGL(pointnet_xmoments_kernel, dim3(g), dim3(PN_THREADS), 0, stream, x, (size_t)T * P, C3, bn_part);
-        hipLaunchKernelGGL(pointnet_bn_reduce_kernel, dim3(265 + 2 * C3), dim3(64), 0, stream, bn_part, g * PN_WAVES, C3, bn_out);
-        SGA_CHECK_LAUNCH("sga_pointnet_fwd_bn");
-        return SGA_OK;
-    }
-    // few objects: one object per workgroup, its tiles dealt to the 8 waves (exact fp32 kernel only; needs the partials workspace)
-    if (mode == 0 && split_small) {
-        float2* part = static_cast<float2*>(workspace);
-        const int g2 = T < ncu ? T : ncu;
-        if (argmax) {
-            auto k = pointnet_fwd_kernel<C3, true, true>;
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-            hipLaunchKernelGGL(k, dim3(g2), dim3(PN_THREADS), lds_bytes, stream, x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, part, static_cast<double*>(nullptr));
-        } else {
-            auto k = pointnet_fwd_kernel<C3, false, true>;
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-            hipLaunchKernelGGL(k, dim3(g2), dim3(PN_THREADS), lds_bytes, stream, x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, part, static_cast<double*>(nullptr));
-        }
-        hipLaunchKernelGGL(pointnet_combine_kernel, dim3((T * C3 + 255) / 256), dim3(256), 0, stream, part, b3, y, argmax, T, C3, P);
-        SGA_CHECK_LAUNCH("sga_pointnet_fwd");
-        return SGA_OK;
-    }
-    if (mode == 4) {
-        go_p3(nullptr);
-    } else if (argmax) {
-        auto k = pointnet_fwd_kernel<C3, true>;
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        hipLaunchKernelGGL(k, dim3(grid), dim3(PN_THREADS), lds_bytes, stream, x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, static_cast<float2*>(nullptr), static_cast<double*>(nullptr));
-    } else {
-        auto k = pointnet_fwd_kernel<C3, false>;
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        hipLaunchKernelGGL(k, dim3(grid), dim3(PN_THREADS), lds_bytes, stream, x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, static_cast<float2*>(nullptr), static_cast<double*>(nullptr));
-    }
-    SGA_CHECK_LAUNCH("sga_pointnet_fwd");
-    return SGA_OK;
-}
-
 }  // namespace
-
-extern "C" size_t sga_pointnet_fwd_ws_bytes(int T, int C3) { return (size_t)(T > 0 ? T : 0) * PN_WAVES * (C3 > 0 ? C3 : 0) * sizeof(float2); }
-
-static int pointnet_fwd_impl(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
-                             const float* b3, float* y, int32_t* argmax, int T, int P, int C3, void* workspace, size_t ws_bytes,
-                             int mode, void* stream, double* bn_part = nullptr, double* bn_out = nullptr) {
-    SGA_CHECK_ARG(T >= 0 && P >= 1, "sga_pointnet_fwd: need T >= 0 and P >= 1 (got T=%d P=%d)", T, P);
-    SGA_CHECK_ARG(mode == 0 || mode == 4, "sga_pointnet_fwd: mode %d (0 = exact fp32, 4 = three exact bf16 planes)", mode);
-    // a zero-object shard (T == 0: empty tensors carry null data pointers) is a valid no-op
-    SGA_CHECK_ARG((T == 0 || (x && y)) && w1 && b1 && w2 && b2 && w3 && b3, "sga_pointnet_fwd: null pointer");
-    if (T == 0) return SGA_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (C3) {
-        case 256: return launch_fwd<256>(x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, s, workspace, ws_bytes, mode, bn_part, bn_out);
-        case 128: return launch_fwd<128>(x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, s, workspace, ws_bytes, mode, bn_part, bn_out);
-        case 64: return launch_fwd<64>(x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, s, workspace, ws_bytes, mode, bn_part, bn_out);
-        default:
-            sga_set_error("sga_pointnet_fwd: out_size C3=%d unsupported (64, 128 or 256: W3 must fit the 160 KiB LDS)", C3);
-            return SGA_ERR_ARG;
-    }
-}
-
-extern "C" int sga_pointnet_fwd_ws(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
-                                   const float* w3, const float* b3, float* y, int32_t* argmax, int T, int P, int C3,
-                                   void* workspace, size_t ws_bytes, int mode, void* stream) {
-    return pointnet_fwd_impl(x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, C3, workspace, ws_bytes, mode, stream);
-}
-
-/* The exact-fp32 forward that also delivers the batch statistics the reference's three discarded BatchNorm calls fold into their running
- * buffers (pointnet.py:141-142,154-155,158-159): bn_sums[265 + 2 C3] doubles (layout: pointnet_bn_reduce_kernel). */
-extern "C" size_t sga_pointnet_fwd_bn_ws_bytes(int T, int C3) {
-    if (T <= 0 || C3 <= 0) return 0;
-    const int ncu = sga_num_cus();
-    const int g = 2 * T < ncu ? 2 * T : ncu;              // an upper bound of every launch form's workgroup count
-    return (size_t)g * PN_WAVES * (9 + 8 + 2 * (C3 / 32)) * 64 * sizeof(double);
-}
-extern "C" int sga_pointnet_fwd_bn(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
-                                   const float* w3, const float* b3, float* y, int32_t* argmax, int T, int P, int C3,
-                                   void* workspace, size_t ws_bytes, void* bn_workspace, size_t bn_ws_bytes, double* bn_sums, int mode, void* stream) {
-    SGA_CHECK_ARG(bn_sums != nullptr, "sga_pointnet_fwd_bn: bn_sums is null");
-    SGA_CHECK_ARG(mode == 0 || mode == 4, "sga_pointnet_fwd_bn: mode %d (0 = exact fp32, 4 = three exact bf16 planes)", mode);
-    SGA_CHECK_ARG(T == 0 || (bn_workspace && bn_ws_bytes >= sga_pointnet_fwd_bn_ws_bytes(T, C3)),
-                  "sga_pointnet_fwd_bn: bn_workspace must hold sga_pointnet_fwd_bn_ws_bytes(T, C3) = %zu bytes (got %zu)", sga_pointnet_fwd_bn_ws_bytes(T, C3), bn_ws_bytes);
-    if (T == 0) {
-        if (C3 == 64 || C3 == 128 || C3 == 256) hipMemsetAsync(bn_sums, 0, (size_t)(265 + 2 * C3) * sizeof(double), static_cast<hipStream_t>(stream));
-    }
-    return pointnet_fwd_impl(x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, C3, workspace, ws_bytes, mode, stream, static_cast<double*>(bn_workspace), bn_sums);
-}
-
-/* the no-workspace entry: always the exact-fp32 kernel */
-extern "C" int sga_pointnet_fwd(const float* x, const float* w1, const float* b1, const float* w2,
-                                const float* b2, const float* w3, const float* b3, float* y,
-                                int32_t* argmax, int T, int P, int C3, void* stream) {
-    return pointnet_fwd_impl(x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, C3, nullptr, 0, 0, stream);
-}
 
 // =================================================================================================
 // Backward (sparse through the max-pool).
@@ -1409,38 +1250,246 @@ __global__ __launch_bounds__(256) void pointnet_bwd_p3_kernel(
 
 }  // namespace
 
+// =================================================================================================
+// Host side: one plan (pn_plan) for every launch form of the forward and the backward, and one launch path that does what the plan says.
+// =================================================================================================
+namespace {
+
+constexpr bool pn_c3_ok(int C3) { return C3 == 64 || C3 == 128 || C3 == 256; }
+// the BN partials of g workgroups: [g * PN_WAVES waves][9 + 8 + 2 C3 / 32 slots][64 lanes] doubles
+constexpr size_t pn_bn_bytes(int g, int C3) { return (size_t)g * PN_WAVES * (9 + 8 + 2 * (C3 / 32)) * 64 * sizeof(double); }
+
+// What one call launches.  Filled by pn_plan, reported by sga_pointnet_plan (the layout of its int32 array is this struct's order).
+struct PnPlan {
+    int form = SGA_POINTNET_REFUSED;
+    int grid = 0, lds = 0;                                  // the main kernel: workgroups, dynamic LDS bytes
+    int ws_use = SGA_POINTNET_WS_NONE;                      // what `workspace` holds ...
+    size_t ws_used = 0;                                     // ... and how many bytes of it
+    size_t bn_bytes = 0;                                    // bytes of bn_workspace zeroed (forward with BatchNorm sums)
+    int lplanes_grid = 0, combine_grid = 0, xmoments_grid = 0, reduce_grid = 0;      // the auxiliary launches (0: not launched)
+};
+
+// The launch decision of sga_pointnet_fwd / _fwd_ws / _fwd_bn and sga_pointnet_bwd: every condition that chooses a form, a grid or a size lives
+// here and nowhere else.  ws_bytes: what the caller offers in `workspace` (0: none).  Touches no device unless ncu <= 0 (then the CU count is
+// asked for).  Forward arithmetic, chosen PER CALL (the library keeps no mode): 0 = exact fp32 (v_mfma_f32_32x32x2_f32); 4 = three exact bf16
+// planes, six bf16 MFMAs per product (fp32 arithmetic on the bf16 matrix pipe; every launch form).
+int pn_plan(int pass, int T, int P, int C3, int mode, size_t ws_bytes, int ncu, PnPlan* p) {
+    *p = PnPlan{};
+    SGA_CHECK_ARG(pass == SGA_POINTNET_FWD || pass == SGA_POINTNET_FWD_BN || pass == SGA_POINTNET_BWD,
+                  "sga_pointnet_plan: pass %d (0 = forward, 1 = forward with BatchNorm sums, 2 = backward)", pass);
+    if (pass == SGA_POINTNET_BWD) {
+        SGA_CHECK_ARG(C3 == 256, "sga_pointnet_bwd: out_size C3=%d unsupported (256 only)", C3);
+        SGA_CHECK_ARG(mode == 0 || mode == 4, "sga_pointnet_bwd: mode %d (0 = exact fp32 MFMA, 4 = three exact bf16 planes)", mode);
+        SGA_CHECK_ARG(T >= 0 && P >= 1, "sga_pointnet_bwd: bad sizes");
+        if (T == 0) { p->form = SGA_POINTNET_EMPTY; return SGA_OK; }
+        if (ncu <= 0) ncu = sga_num_cus();
+        if (mode == 4) {
+            // workgroups come in quadruples: (tiles 0-3 | 4-7) x (half of the layer-2 channels)
+            p->form = SGA_POINTNET_BWD_P3;
+            p->grid = 4 * T < ncu ? 4 * T : (ncu & ~3);
+            p->lds = (int)((size_t)2 * 3 * 512 * 16 + (4 * 32 * TRS + 128 * W3S + 384) * sizeof(float));
+        } else {
+            // ... here in (tiles 0-3, tiles 4-7) pairs
+            p->form = SGA_POINTNET_BWD_F32;
+            p->grid = 2 * T < ncu ? 2 * T : (ncu & ~1);
+            p->lds = (int)((3 * 8192 + 384) * sizeof(float));
+        }
+        return SGA_OK;
+    }
+    const bool bn = pass == SGA_POINTNET_FWD_BN;
+    SGA_CHECK_ARG(T >= 0 && P >= 1, "sga_pointnet_fwd: need T >= 0 and P >= 1 (got T=%d P=%d)", T, P);
+    SGA_CHECK_ARG(mode == 0 || mode == 4, "%s: mode %d (0 = exact fp32, 4 = three exact bf16 planes)", bn ? "sga_pointnet_fwd_bn" : "sga_pointnet_fwd", mode);
+    if (T == 0) { p->form = SGA_POINTNET_EMPTY; return SGA_OK; }    // a zero-object shard is a valid no-op
+    SGA_CHECK_ARG(pn_c3_ok(C3), "sga_pointnet_fwd: out_size C3=%d unsupported (64, 128 or 256: W3 must fit the 160 KiB LDS)", C3);
+    if (ncu <= 0) ncu = sga_num_cus();
+    int grid = (T + PN_WAVES - 1) / PN_WAVES;               // one wave per object, persistent workgroups
+    if (grid > ncu) grid = ncu;
+    // few objects: one object per workgroup (pair) at a time, its tiles dealt to the 8 waves (needs the partials workspace)
+    const bool split = ws_bytes >= sga_pointnet_fwd_ws_bytes(T, C3) && T < 4 * ncu && P > 32;
+    if (mode == 0) {
+        p->form = split ? SGA_POINTNET_F32_SPLIT : SGA_POINTNET_F32_WAVE;
+        p->grid = split ? (T < ncu ? T : ncu) : grid;
+        p->lds = (int)((size_t)(8192 + C3 * 128) * sizeof(float));
+    } else if (C3 == 256 && !split && ws_bytes >= PN_P3_LG_BYTES) {
+        // C3 = 256, not split, a scratch of PN_P3_LG_BYTES in `workspace`: one workgroup per object, the l planes from global memory (LG)
+        p->form = SGA_POINTNET_P3_LG;
+        p->grid = grid;
+        p->lds = (2 * 16 * 64 + 2 * 8 * 8 * 64) * 16;
+        p->ws_use = SGA_POINTNET_WS_LG;
+        p->ws_used = PN_P3_LG_BYTES;
+        p->lplanes_grid = (1024 + 8 * 512 + 255) / 256;
+    } else {
+        // three exact bf16 planes (pointnet_fwd_p3_kernel); at C3 = 256 a workgroup holds half of W3's channels, two share an object
+        const int halves = C3 == 256 ? 2 : 1;
+        const int slots_max = halves == 2 ? (ncu / 2 > 0 ? ncu / 2 : 1) : ncu;
+        const int want = split ? T : grid;
+        p->form = split ? SGA_POINTNET_P3_SPLIT : SGA_POINTNET_P3;
+        p->grid = halves * (want < slots_max ? want : slots_max);
+        p->lds = (3 * 16 * 64 + 3 * (C3 / halves / 32) * 8 * 64) * 16;
+    }
+    if (split) {
+        p->ws_use = SGA_POINTNET_WS_PARTIALS;
+        p->ws_used = sga_pointnet_fwd_ws_bytes(T, C3);
+        p->combine_grid = (T * C3 + 255) / 256;
+    }
+    if (bn) {
+        // the batch statistics of the three pre-activations (the reference's BatchNorm side effect): per-wave partials of the main grid,
+        // the point moments on the same grid, then one 64-thread block per output sum
+        p->bn_bytes = pn_bn_bytes(p->grid, C3);
+        p->xmoments_grid = p->grid;
+        p->reduce_grid = 265 + 2 * C3;
+    }
+    return SGA_OK;
+}
+
+// Run-time bools to compile-time ones: pn_bools(f, a, b, ...) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...).
+template <typename F>
+int pn_bools(F&& f) { return f(); }
+template <typename F, typename... Rest>
+int pn_bools(F&& f, bool b, Rest... rest) {
+    return b ? pn_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
+             : pn_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+
+// Allow `lds` bytes of dynamic LDS to `kernel` and launch it.
+template <typename... KA, typename... A>
+int pn_launch(const char* who, const char* form, void (*kernel)(KA...), int grid, int threads, int lds, hipStream_t stream, A... args) {
+    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds); e != hipSuccess) {
+        sga_set_error("%s: the %s kernel cannot have %d bytes of dynamic LDS: %s", who, form, lds, hipGetErrorString(e));
+        return SGA_ERR_HIP;
+    }
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, stream, static_cast<KA>(args)...);
+    return SGA_OK;
+}
+
+// The forward as planned: zero what the plan says, launch what the plan says, in this order.
+template <int C3>
+int launch_fwd(const PnPlan& p, const char* who, const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+               const float* w3, const float* b3, float* y, int* argmax, int T, int P, hipStream_t stream, void* workspace,
+               double* bn_part, double* bn_out) {
+    float2* part = p.ws_use == SGA_POINTNET_WS_PARTIALS ? static_cast<float2*>(workspace) : nullptr;
+    u32x4* wlg = p.ws_use == SGA_POINTNET_WS_LG ? static_cast<u32x4*>(workspace) : nullptr;
+    if (p.bn_bytes)
+        if (int rc = sga_zero(who, bn_part, p.bn_bytes, stream)) return rc;
+    int rc = SGA_OK;
+    if (p.form == SGA_POINTNET_F32_WAVE || p.form == SGA_POINTNET_F32_SPLIT) {
+        rc = pn_bools([&](auto am, auto sp, auto bn) {
+            return pn_launch(who, "fp32", pointnet_fwd_kernel<C3, decltype(am)::value, decltype(sp)::value, decltype(bn)::value>, p.grid, PN_THREADS, p.lds,
+                             stream, x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, part, bn_part);
+        }, argmax != nullptr, part != nullptr, bn_part != nullptr);
+    } else if (p.form == SGA_POINTNET_P3_LG) {
+        if constexpr (C3 == 256) {
+            hipLaunchKernelGGL(pointnet_p3_lplanes_kernel<C3>, dim3(p.lplanes_grid), dim3(256), 0, stream, w2, w3, wlg);
+            rc = pn_bools([&](auto am, auto bn) {
+                return pn_launch(who, "three-plane LG", pointnet_fwd_p3_kernel<C3, decltype(am)::value, decltype(bn)::value, false, true>, p.grid, PN_THREADS,
+                                 p.lds, stream, x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, bn_part, part, wlg);
+            }, argmax != nullptr, bn_part != nullptr);
+        }
+    } else {
+        rc = pn_bools([&](auto am, auto bn, auto sp) {
+            return pn_launch(who, "three-plane", pointnet_fwd_p3_kernel<C3, decltype(am)::value, decltype(bn)::value, decltype(sp)::value, false>, p.grid,
+                             PN_THREADS, p.lds, stream, x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, bn_part, part, wlg);
+        }, argmax != nullptr, bn_part != nullptr, part != nullptr);
+    }
+    if (rc != SGA_OK) return rc;
+    if (p.combine_grid) hipLaunchKernelGGL(pointnet_combine_kernel, dim3(p.combine_grid), dim3(256), 0, stream, part, b3, y, argmax, T, C3, P);
+    if (p.xmoments_grid) hipLaunchKernelGGL(pointnet_xmoments_kernel, dim3(p.xmoments_grid), dim3(PN_THREADS), 0, stream, x, (size_t)T * P, C3, bn_part);
+    if (p.reduce_grid) hipLaunchKernelGGL(pointnet_bn_reduce_kernel, dim3(p.reduce_grid), dim3(64), 0, stream, bn_part, p.grid * PN_WAVES, C3, bn_out);
+    SGA_CHECK_LAUNCH(who);
+    return SGA_OK;
+}
+
+// The three forward entry points.  bn_sums non-null: sga_pointnet_fwd_bn.
+int pointnet_fwd_impl(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
+                      float* y, int32_t* argmax, int T, int P, int C3, void* workspace, size_t ws_bytes, int mode, void* stream,
+                      void* bn_workspace = nullptr, size_t bn_ws_bytes = 0, double* bn_sums = nullptr) {
+    const char* who = bn_sums ? "sga_pointnet_fwd_bn" : "sga_pointnet_fwd";
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PnPlan p;
+    if (int rc = pn_plan(bn_sums ? SGA_POINTNET_FWD_BN : SGA_POINTNET_FWD, T, P, C3, mode, workspace ? ws_bytes : 0, 0, &p)) return rc;
+    SGA_CHECK_ARG(!bn_sums || T == 0 || (bn_workspace && bn_ws_bytes >= sga_pointnet_fwd_bn_ws_bytes(T, C3)),
+                  "sga_pointnet_fwd_bn: bn_workspace must hold sga_pointnet_fwd_bn_ws_bytes(T, C3) = %zu bytes (got %zu)", sga_pointnet_fwd_bn_ws_bytes(T, C3), bn_ws_bytes);
+    // a zero-object shard (T == 0: empty tensors carry null data pointers) is a valid no-op
+    SGA_CHECK_ARG((T == 0 || (x && y)) && w1 && b1 && w2 && b2 && w3 && b3, "sga_pointnet_fwd: null pointer");
+    if (p.form == SGA_POINTNET_EMPTY) return bn_sums && pn_c3_ok(C3) ? sga_zero(who, bn_sums, (size_t)(265 + 2 * C3) * sizeof(double), s) : SGA_OK;
+    if (p.bn_bytes > bn_ws_bytes) {                          // sga_pointnet_fwd_bn_ws_bytes is a bound of every form: nothing has been written yet
+        sga_set_error("%s: the launch form needs %zu bytes of bn_workspace (got %zu)", who, p.bn_bytes, bn_ws_bytes);
+        return SGA_ERR_WORKSPACE;
+    }
+    double* bn_part = static_cast<double*>(bn_workspace);
+    switch (C3) {
+        case 256: return launch_fwd<256>(p, who, x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, s, workspace, bn_part, bn_sums);
+        case 128: return launch_fwd<128>(p, who, x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, s, workspace, bn_part, bn_sums);
+        default: return launch_fwd<64>(p, who, x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, s, workspace, bn_part, bn_sums);
+    }
+}
+
+}  // namespace
+
+extern "C" size_t sga_pointnet_fwd_ws_bytes(int T, int C3) { return (size_t)(T > 0 ? T : 0) * PN_WAVES * (C3 > 0 ? C3 : 0) * sizeof(float2); }
+extern "C" size_t sga_pointnet_fwd_lg_ws_bytes(void) { return PN_P3_LG_BYTES; }
+
+extern "C" int sga_pointnet_plan(int pass, int T, int P, int C3, int mode, size_t ws_bytes, int ncu, int32_t* plan) {
+    PnPlan p;
+    const int rc = pn_plan(pass, T, P, C3, mode, ws_bytes, ncu, &p);
+    const size_t f[SGA_POINTNET_PLAN_FIELDS] = {(size_t)p.form, (size_t)p.grid, (size_t)p.lds, (size_t)p.ws_use, p.ws_used, p.bn_bytes, (size_t)p.lplanes_grid,
+                                                (size_t)p.combine_grid, (size_t)p.xmoments_grid, (size_t)p.reduce_grid};
+    for (int i = 0; plan && i < SGA_POINTNET_PLAN_FIELDS; ++i) plan[i] = f[i] < INT32_MAX ? (int32_t)f[i] : INT32_MAX;
+    return rc;
+}
+
+/* the no-workspace entry: always the exact-fp32 kernel */
+extern "C" int sga_pointnet_fwd(const float* x, const float* w1, const float* b1, const float* w2,
+                                const float* b2, const float* w3, const float* b3, float* y,
+                                int32_t* argmax, int T, int P, int C3, void* stream) {
+    return pointnet_fwd_impl(x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, C3, nullptr, 0, 0, stream);
+}
+
+extern "C" int sga_pointnet_fwd_ws(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                                   const float* w3, const float* b3, float* y, int32_t* argmax, int T, int P, int C3,
+                                   void* workspace, size_t ws_bytes, int mode, void* stream) {
+    return pointnet_fwd_impl(x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, C3, workspace, ws_bytes, mode, stream);
+}
+
+/* The forward that also delivers the batch statistics the reference's three discarded BatchNorm calls fold into their running buffers
+ * (pointnet.py:141-142,154-155,158-159): bn_sums[265 + 2 C3] doubles (layout: pointnet_bn_reduce_kernel).  Its workspace bound is the
+ * partials of min(2 T, CUs) workgroups, which no launch form of pn_plan exceeds on a card of two or more CUs: one wave per object runs
+ * min(ceil(T / 8), CUs), the fp32 split min(T, CUs), the channel-halves forms 2 min(T, CUs / 2) at most. */
+extern "C" size_t sga_pointnet_fwd_bn_ws_bytes(int T, int C3) {
+    if (T <= 0 || C3 <= 0) return 0;
+    const int ncu = sga_num_cus();
+    return pn_bn_bytes(2 * T < ncu ? 2 * T : ncu, C3);
+}
+extern "C" int sga_pointnet_fwd_bn(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                                   const float* w3, const float* b3, float* y, int32_t* argmax, int T, int P, int C3,
+                                   void* workspace, size_t ws_bytes, void* bn_workspace, size_t bn_ws_bytes, double* bn_sums, int mode, void* stream) {
+    SGA_CHECK_ARG(bn_sums != nullptr, "sga_pointnet_fwd_bn: bn_sums is null");
+    return pointnet_fwd_impl(x, w1, b1, w2, b2, w3, b3, y, argmax, T, P, C3, workspace, ws_bytes, mode, stream, bn_workspace, bn_ws_bytes, bn_sums);
+}
+
 extern "C" int sga_pointnet_bwd(const float* x, const int32_t* argmax, const float* y, const float* gy,
                                 const float* w1, const float* b1, const float* w2, const float* b2,
                                 const float* w3, float* gw1, float* gb1, float* gw2, float* gb2, float* gw3,
                                 float* gb3, int T, int P, int C3, int mode, void* stream) {
-    SGA_CHECK_ARG(C3 == 256, "sga_pointnet_bwd: out_size C3=%d unsupported (256 only)", C3);
-    SGA_CHECK_ARG(mode == 0 || mode == 4, "sga_pointnet_bwd: mode %d (0 = exact fp32 MFMA, 4 = three exact bf16 planes)", mode);
-    SGA_CHECK_ARG(T >= 0 && P >= 1, "sga_pointnet_bwd: bad sizes");
+    const char* who = "sga_pointnet_bwd";
+    PnPlan p;
+    if (int rc = pn_plan(SGA_POINTNET_BWD, T, P, C3, mode, 0, 0, &p)) return rc;
     SGA_CHECK_ARG((T == 0 || (x && argmax && y && gy)) && w1 && b1 && w2 && b2 && w3 && gw1 && gb1 && gw2 && gb2 && gw3 && gb3,
                   "sga_pointnet_bwd: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (gb1 == gw1 + 192 && gw2 == gb1 + 64 && gb2 == gw2 + 8192 && gw3 == gb2 + 128 && gb3 == gw3 + 32768) {
-        hipMemsetAsync(gw1, 0, (192 + 64 + 8192 + 128 + 32768 + 256) * sizeof(float), s);      // one flat buffer (ops.py): one launch
-    } else {
-        hipMemsetAsync(gw1, 0, 64 * 3 * sizeof(float), s);
-        hipMemsetAsync(gb1, 0, 64 * sizeof(float), s);
-        hipMemsetAsync(gw2, 0, 128 * 64 * sizeof(float), s);
-        hipMemsetAsync(gb2, 0, 128 * sizeof(float), s);
-        hipMemsetAsync(gw3, 0, 256 * 128 * sizeof(float), s);
-        hipMemsetAsync(gb3, 0, 256 * sizeof(float), s);
-    }
-    if (T == 0) return SGA_OK;
-    const int g2 = 2 * T < sga_num_cus() ? 2 * T : (sga_num_cus() & ~1);      // workgroups come in (tiles 0-3, tiles 4-7) pairs
-    if (mode == 4) {
-        const int g4 = 4 * T < sga_num_cus() ? 4 * T : (sga_num_cus() & ~3);  // ... here in quadruples: (tile group) x (half of the layer-2 channels)
-        const size_t lds_b = (size_t)2 * 3 * 512 * 16 + (4 * 32 * TRS + 128 * W3S + 384) * sizeof(float);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(pointnet_bwd_p3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-        hipLaunchKernelGGL(pointnet_bwd_p3_kernel, dim3(g4), dim3(256), lds_b, s, x, argmax, y, gy, w1, b1, w2, b2, w3, gw1, gb1, gw2, gb2, gw3, gb3, T, P);
-    } else {
-        const size_t lds_f = (3 * 8192 + 384) * sizeof(float);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(pointnet_bwd_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f);
-        hipLaunchKernelGGL(pointnet_bwd_fused_kernel, dim3(g2), dim3(256), lds_f, s, x, argmax, y, gy, w1, b1, w2, b2, w3, gw1, gb1, gw2, gb2, gw3, gb3, T, P);
-    }
-    SGA_CHECK_LAUNCH("sga_pointnet_bwd");
+    // the kernels add into the six gradients: zeroed first, in one launch where they are one flat buffer (ops.py)
+    float* const g[6] = {gw1, gb1, gw2, gb2, gw3, gb3};
+    const size_t n[6] = {64 * 3, 64, 128 * 64, 128, 256 * 128, 256};
+    size_t all = 0;
+    bool flat = true;
+    for (int i = 0; i < 6; ++i) { flat = flat && g[i] == gw1 + all; all += n[i]; }
+    for (int i = 0; i < (flat ? 1 : 6); ++i)
+        if (int rc = sga_zero(who, g[i], (flat ? all : n[i]) * sizeof(float), s)) return rc;
+    if (p.form == SGA_POINTNET_EMPTY) return SGA_OK;
+    const int rc = p.form == SGA_POINTNET_BWD_P3
+        ? pn_launch(who, "three-plane", pointnet_bwd_p3_kernel, p.grid, 256, p.lds, s, x, argmax, y, gy, w1, b1, w2, b2, w3, gw1, gb1, gw2, gb2, gw3, gb3, T, P)
+        : pn_launch(who, "fp32", pointnet_bwd_fused_kernel, p.grid, 256, p.lds, s, x, argmax, y, gy, w1, b1, w2, b2, w3, gw1, gb1, gw2, gb2, gw3, gb3, T, P);
+    if (rc != SGA_OK) return rc;
+    SGA_CHECK_LAUNCH(who);
     return SGA_OK;
 }

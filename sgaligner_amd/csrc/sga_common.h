@@ -48,6 +48,15 @@ static inline int sga_num_cus() {
     return n;
 }
 
+// Zero `bytes` bytes of device memory on `stream`.
+static inline int sga_zero(const char* who, void* p, size_t bytes, hipStream_t stream) {
+    if (hipMemsetAsync(p, 0, bytes, stream) != hipSuccess) {
+        sga_set_error("%s: memset failed", who);
+        return SGA_ERR_HIP;
+    }
+    return SGA_OK;
+}
+
 // row of C/D register r for lane-half h in the 32x32 MFMA accumulator layout
 // (col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5))
 __device__ __forceinline__ int mfma32_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }

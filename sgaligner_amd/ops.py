@@ -493,7 +493,10 @@ def _stash_bytes():
 
 
 # ---- run-time switches of the kernels whose autograd nodes live in pointnet_ops / loss_ops / gat_ops / rank_ops (read there as ops.<FLAG>)
-POINTNET_SPLIT_MAX_OBJECTS = 1023      # the library uses the split form below 4 x CUs objects; above that a workspace is not allocated
+# The caller's half of the PointNet forward's split rule: up to this many objects pointnet_forward OFFERS the library a partials buffer
+# (pointnet_ops.pointnet_workspace_bytes); whether a call is then split is the library's decision (T < 4 x CUs and P > 32: sga_pointnet_plan).
+# 1023 is that 4 x CUs - 1 on a 256-CU card.  0: never offer one (tools/fuzz_parity.py).
+POINTNET_SPLIT_MAX_OBJECTS = 1023
 # 'bf16x6' forward sums: all six partial products (False), or the h and m planes only (True: h h + h m + m h, 11 of 20 MFMAs, no l-plane traffic; every similarity
 # with an unbiased 2^-16 rounding).  None (default) = lite only when the smallest of the four global sums has >= BF16X6_SUMS_LITE_MIN_TERMS terms:
 # the roundings average out (relative 1e-4 per term / sqrt(terms), bias 1e-8) far below the fp32 rounding of the sums' own accumulation.
@@ -506,7 +509,7 @@ SIMRANK_F16 = False      # opt-in: fp16-input MFMA similarity (BASELINE.json con
 
 # ---- the autograd nodes, by kernel family; `sgaligner_amd.ops.<name>` resolves to them lazily (any import order works)
 _REEXPORT = {
-    'pointnet_ops': ('pointnet_bn_fusable', 'pointnet_forward', 'PointNetFn', 'pointnet'),
+    'pointnet_ops': ('pointnet_workspace_bytes', 'pointnet_plan', 'PointNetPlan', 'pointnet_forward', 'PointNetFn', 'pointnet'),
     'loss_ops': ('_anchor_chunks', '_sym_chunks', '_sym_jobs', 'SWEEP_GRAD_INFO', 'SWEEP_SUMS_INFO', 'TAU_ICL', 'TAU_IAL', 'ALPHA', 'ContrastiveTermsFn',
                  'contrastive_terms', 'LossHeadFn', 'LossGroups', 'GroupedContrastiveFn', 'grouped_contrastive_terms', 'group_data_dicts',
                  '_allreduce_sum', 'FusedContrastiveFn', 'fused_contrastive_terms'),

@@ -5,6 +5,7 @@ working).  The run-time switches live in ops.py and are read through the module 
 caller or a test takes effect here."""
 from __future__ import annotations
 
+import collections as _collections
 import ctypes as _ct
 
 import numpy as _np
@@ -16,30 +17,42 @@ from .ops import (_SmallCache, _ev_start, _ev_stop, _fingerprint, _h2d, _p, _ptr
                   _POINTNET_MODE, _stash_bytes, cast_f32, colsum, gemm)
 
 # ------------------------------------------------------------------------------------------ PointNet
-def pointnet_bn_fusable() -> bool:
-    """Both forward kernels (exact fp32, three exact bf16 planes) deliver the BatchNorm batch statistics of the reference's training forward
-    from inside the kernel (sga_pointnet_fwd_bn)."""
-    return True
+PointNetPlan = _collections.namedtuple('PointNetPlan', 'form workgroups lds ws_use ws_bytes bn_bytes lplanes combine xmoments reduce')
+
+
+def pointnet_workspace_bytes(T, C3, mode) -> int:
+    """The bytes of `workspace` pointnet_forward offers the library for T objects in kernel mode 0 / 4: the caller's half of the launch rule
+    (what the library does with them is its own decision: pointnet_plan)."""
+    L = _lib.lib()
+    if 0 < T <= _o.POINTNET_SPLIT_MAX_OBJECTS:      # few objects: a partials buffer, so that every object can be split over a workgroup's 8 waves
+        return int(L.sga_pointnet_fwd_ws_bytes(T, C3))
+    if T > 0 and mode == 4 and C3 == 256:           # many objects on three planes: scratch for the l planes of W2 / W3 (one workgroup then serves whole objects)
+        return int(L.sga_pointnet_fwd_lg_ws_bytes())
+    return 0
+
+
+def pointnet_plan(which, T, P, C3=256, mode=0, ws_bytes=0, ncu=0) -> PointNetPlan:
+    """What the PointNet call so described launches -- sga_pointnet_plan, the launcher's own decision (fields: include/sgaligner_hip.h).
+    which: 'FWD', 'FWD_BN' or 'BWD'; ws_bytes: the workspace offered (pointnet_workspace_bytes for pointnet_forward's own calls).
+    ncu > 0: plan for that CU count on the host alone; 0: ask the current device."""
+    out = (_ct.c_int32 * _lib.POINTNET_PLAN_FIELDS)()
+    rc = _lib.lib().sga_pointnet_plan(_lib.POINTNET_PASSES.index(which), T, P, C3, mode, ws_bytes, ncu, out)
+    _lib.check(rc, 'sga_pointnet_plan')
+    return PointNetPlan(_lib.POINTNET_FORMS[out[0]], out[1], out[2], _lib.POINTNET_WS_USES[out[3]], *out[4:])
 
 
 def pointnet_forward(x_tp3, w1, b1, w2, b2, w3, b3, want_argmax: bool, bn_sums=None):
     """x_tp3 [T,P,3] (point-major, as in data_dict['tot_obj_pts']).  Returns (y [T,C3], argmax|None).
     bn_sums: a float64 tensor of 265 + 2 C3 elements to receive the batch-statistic sums of the three pre-activations (layout:
-    include/sgaligner_hip.h, sga_pointnet_fwd_bn) -- exact-fp32 forward only."""
+    include/sgaligner_hip.h, sga_pointnet_fwd_bn) -- from inside the forward kernel, in either arithmetic."""
     T, P, _ = x_tp3.shape
     C3 = w3.shape[0]
     y = torch.empty((T, C3), device=x_tp3.device, dtype=torch.float32)
     am = torch.empty((T, C3), device=x_tp3.device, dtype=torch.int32) if want_argmax else None
     ev = _ev_start()
     L = _lib.lib()
-    ws, ws_bytes = None, 0
-    if 0 < T <= _o.POINTNET_SPLIT_MAX_OBJECTS:      # few objects: split every object over a workgroup's 8 waves (needs a partials buffer)
-        ws_bytes = int(L.sga_pointnet_fwd_ws_bytes(T, C3))
-        ws = torch.empty((ws_bytes,), device=x_tp3.device, dtype=torch.uint8)
-    elif T > 0 and _POINTNET_MODE[get_mfma_mode()] == 4 and C3 == 256:
-        # many objects on three planes: 80 KiB of scratch for the l planes of W2 / W3 in operand order (one workgroup then serves whole objects)
-        ws_bytes = 81920
-        ws = torch.empty((ws_bytes,), device=x_tp3.device, dtype=torch.uint8)
+    ws_bytes = pointnet_workspace_bytes(T, C3, _POINTNET_MODE[get_mfma_mode()])
+    ws = torch.empty((ws_bytes,), device=x_tp3.device, dtype=torch.uint8) if ws_bytes else None
     if bn_sums is not None:
         if bn_sums.dtype != torch.float64 or bn_sums.numel() != 265 + 2 * C3 or not bn_sums.is_contiguous() or bn_sums.device != x_tp3.device:
             raise RuntimeError('sgaligner_amd.pointnet_forward: bn_sums must be a contiguous float64 tensor of 265 + 2 C3 elements on the input device')

@@ -376,8 +376,28 @@ def gate_ok(kernel, yard, r):
 
 
 def forward_shapes(split_max):
-    """(form, T, P): objects split over a workgroup's waves, and one wave per object (the Python layer's threshold + 77 objects)."""
-    return [('split', 9, 33), ('wave', split_max + 77, 33)]
+    """(case, T, P): objects split over a workgroup's waves; one wave per object (the Python layer's threshold + 77 objects); few objects of one
+    32-point tile, which are not split -- three of them (their partials buffer is too small to serve as LG scratch: at C3 = 256 two half-workgroups
+    share an object), and nine (at C3 = 256 in mode 4 the partials buffer becomes the LG scratch)."""
+    return [('split', 9, 33), ('wave', split_max + 77, 33), ('halves', 3, 31), ('lg', 9, 32)]
+
+
+# What each case of forward_shapes is there for: (case, kernel mode) -> (launch form, what the workspace holds) at C3 = 64, 128, 256, as
+# sga_pointnet_plan names them.  The GPU tests assert this of every call before they compare numbers: a moved threshold fails here, not silently.
+_ALL = lambda form, use='NONE': {c3: (form, use) for c3 in (64, 128, 256)}
+FORWARD_FORMS = {
+    ('split', 0): _ALL('F32_SPLIT', 'PARTIALS'), ('split', 4): _ALL('P3_SPLIT', 'PARTIALS'),
+    ('wave', 0): _ALL('F32_WAVE'), ('wave', 4): {**_ALL('P3'), 256: ('P3_LG', 'LG')},
+    ('halves', 0): _ALL('F32_WAVE'), ('halves', 4): _ALL('P3'),
+    ('lg', 0): _ALL('F32_WAVE'), ('lg', 4): {**_ALL('P3'), 256: ('P3_LG', 'LG')},
+}
+BACKWARD_FORMS = {0: 'BWD_F32', 4: 'BWD_P3'}
+
+
+def planned_forward(C3, T, P, mode, bn=False):
+    """The plan of the call ops.pointnet_forward makes for this shape on this card (the workspace it would offer included)."""
+    from sgaligner_amd import ops
+    return ops.pointnet_plan('FWD_BN' if bn else 'FWD', T, P, C3, mode, ws_bytes=ops.pointnet_workspace_bytes(T, C3, mode))
 
 
 def measure_backward(T, P, mode):

@@ -1,6 +1,7 @@
 """PointNet kernels on the card against the fp64 winner-row reference of tests/pointnet_gate.py: bit for bit on integer lattices (both forward
-families in both launch forms, both backward kernels across the sizes at which their launch geometry changes), and within the measured
-multiple of plain fp32's own error on guarded random inputs."""
+families in every launch form, both backward kernels across the sizes at which their launch geometry changes), and within the measured
+multiple of plain fp32's own error on guarded random inputs.  Every forward call and the backward gate first assert, through
+sga_pointnet_plan on this card, the launch form they reach (pointnet_gate.FORWARD_FORMS / BACKWARD_FORMS)."""
 import pytest
 import torch
 
@@ -66,7 +67,12 @@ def test_pointnet_bwd_exact_separate_gradient_buffers(mode):
 def test_pointnet_bwd_gate(big, mode):
     """Guarded random inputs: every gradient's envelope-relative error (max and rms, in u) within r x the float32 CPU yardstick's, r per
     output and mode from profiles/pointnet_accuracy_vs_fp32.json."""
+    from sgaligner_amd import ops
     T, P = PG.gate_shapes(_cus())[int(big)]
+    plan = ops.pointnet_plan('BWD', T, P, 256, mode)
+    assert plan.form == PG.BACKWARD_FORMS[mode], plan
+    # gate_shapes' first case: one more object than the three-plane kernel has workgroup quadruples, as the plan reports them
+    assert PG.gate_shapes(_cus())[0][0] == ops.pointnet_plan('BWD', PG.gate_shapes(_cus())[0][0], P, 256, 4).workgroups // 4 + 1
     res = PG.measure_backward(T, P, mode)
     bad = []
     for k, (ke, ye) in res.items():
@@ -83,13 +89,21 @@ def _forward_cases():
     return PG.forward_shapes(ops.POINTNET_SPLIT_MAX_OBJECTS)
 
 
-@pytest.mark.parametrize('form', [0, 1])
+def _assert_form(case, C3, T, P, mode, bn):
+    """The call ops.pointnet_forward is about to make reaches, on this card, the launch form the case is named for."""
+    plan = PG.planned_forward(C3, T, P, mode, bn)
+    assert (plan.form, plan.ws_use) == PG.FORWARD_FORMS[case, mode][C3], f'{case} C3={C3} T={T} P={P} mode={mode} bn={bn}: {plan}'
+    assert (plan.bn_bytes > 0) == bn
+
+
+@pytest.mark.parametrize('form', [0, 1, 2, 3])
 @pytest.mark.parametrize('C3', [64, 128, 256])
 def test_pointnet_fwd_exact_narrow_lattice(C3, form):
-    """Both forward families (mode 0, mode 4), with and without arg-max, with and without the fused BatchNorm sums, in the split form (T = 9)
-    and with one wave per object: y equals the fp64 reference bit for bit, EVERY returned index is a maximiser of the reference's Z3 (ties are
-    dense here), and the BatchNorm sums are the reference's integers."""
-    _, T, P = _forward_cases()[form]
+    """Both forward families (mode 0, mode 4), with and without arg-max, with and without the fused BatchNorm sums, in every launch form (the
+    cases of pointnet_gate.forward_shapes; each call is first asserted to reach the form its case is named for): y equals the fp64 reference
+    bit for bit, EVERY returned index is a maximiser of the reference's Z3 (ties are dense here), and the BatchNorm sums are the reference's
+    integers."""
+    case, T, P = _forward_cases()[form]
     x, ws, ref = PG.lattice('narrow', T, P, C3, backward=False, keep_z3=True)
     z3 = ref['z3']
     assert ((z3 == z3.amax(1, keepdim=True)).sum(1) > 1).float().mean() > 0.1 and (ref['y'] == 0).any()        # ties and exact zeros are there
@@ -97,6 +111,7 @@ def test_pointnet_fwd_exact_narrow_lattice(C3, form):
         for want_am in (True, False):
             for bn in (False, True):
                 what = f'C3={C3} T={T} mode={mode} argmax={want_am} bn={bn}'
+                _assert_form(case, C3, T, P, mode, bn)
                 y, am, sums = PG.run_forward(x, ws, mode, want_am, bn)
                 assert torch.equal(y.cpu().double(), ref['y']), what
                 if want_am:
@@ -111,13 +126,14 @@ def test_pointnet_fwd_exact_narrow_lattice(C3, form):
                     assert len(wrong) == 0, f'{what}: BatchNorm sums differ at {wrong[:8].flatten().tolist()}'
 
 
-@pytest.mark.parametrize('form', [0, 1])
+@pytest.mark.parametrize('form', [0, 1, 2, 3])
 @pytest.mark.parametrize('C3', [64, 128, 256])
 def test_pointnet_fwd_gate(C3, form):
-    """Random inputs: y against e3 at the reference's arg-max point, within r x the float32 CPU yardstick's error, both modes."""
-    _, T, P = _forward_cases()[form]
+    """Random inputs: y against e3 at the reference's arg-max point, within r x the float32 CPU yardstick's error, both modes, every launch form."""
+    case, T, P = _forward_cases()[form]
     for mode in (0, 4):
         for want_am, bn in ((True, False), (False, True)):
+            _assert_form(case, C3, T, P, mode, bn)
             ke, ye = PG.measure_forward(C3, T, P, mode, want_am, bn)
             r = PG.R[mode]['y']
             print(f'[gate] fwd C3={C3} T={T} P={P} mode={mode}: kernel max {ke[0]:.3f} u rms {ke[1]:.4f} u | yardstick max {ye[0]:.3f} u rms {ye[1]:.4f} u | r = {r}')
