@@ -597,6 +597,69 @@ int sga_spfh_counts(const double* pts, const double* normals, const int32_t* off
 int sga_fpfh(const int32_t* counts, const int32_t* offsets, int n_clouds, int total_points, const int32_t* offsets_host,
              const int32_t* count, const int32_t* idx, const double* d2, int max_nn, double* out64, float* out32, int ld, void* stream);
 
+/* ---- voxel grid: cells of a packed batch, voxel down-sampling, grid neighbour lists (fp64; csrc/voxel.hip) -------------------------
+ * utils/open3d.py:68-76 (voxel_downsample) and an accelerator for sga_knn_lists.  Open3D is not a dependency and equality with its output
+ * is not tested: the text below is the definition (tests/voxel_ref.py restates it in numpy).  Clouds are packed back to back as above:
+ * pts [total_points, 3] f64, offsets [n_clouds + 1] DEVICE int32, offsets_host (nullable) validated before anything is launched.  The
+ * kernels re-check every offset, index and count they read: a bad one makes them do nothing, never read or write out of bounds.  No
+ * atomics: every output is a pure function of the input.  Every fp64 operation below is rounded on its own.  Stream-ordered.
+ *
+ * The grid.  cell [n_clouds] f64 DEVICE: the cell edge h_c of each cloud; cell_host (nullable) is a host copy, refused unless every h_c
+ * is > 0 and finite.  A point with a non-finite coordinate is DROPPED: it belongs to no cell, takes no part in the bounds and never
+ * enters a voxel.  origin_c[a] = (min over the cloud's kept points of p[a]) - 0.5 * h_c: the min bound minus half a voxel (Open3D's rule
+ * as remembered; not tested against it); (0, 0, 0) for a cloud without a kept point.  k[a] = floor((p[a] - origin_c[a]) / h_c): sub,
+ * div, floor.  dims_c[a] = k[a] of the cloud's max bound + 1 (0 without a kept point): k is monotone in p, so every kept point has
+ * 0 <= k[a] < dims_c[a].  A cloud is valid when h_c > 0 is finite, every k[a] < 65535 and n_clouds <= 32767; otherwise status 2 ("grid
+ * too fine"), dims 0, no cells, and nothing of it is read further.  key = cloud << 48 | kx << 32 | ky << 16 | kz (int64, non-negative);
+ * a dropped point and every point of a status-2 cloud take the cell (65535, 65535, 65535) of their cloud, so they sort to its end.
+ * sga_voxel_keys writes origin [n_clouds, 3] f64, dims [n_clouds, 3] int32, keys [total_points] int64 and status [n_clouds] int32.
+ * sga_cloud_bounds writes only the bounds the origin comes from: box [n_clouds, 6] f64 = min xyz | max xyz over each cloud's kept points,
+ * +inf | -inf for a cloud without one, and with edge [n_clouds] f64 (nullable) the cell edge at which an occupied cell of a SURFACE
+ * spread across the cloud's box holds about per_cell points: with the extents e1 >= e2 >= e3 and n the cloud's point count,
+ * sqrt(e1 e2 per_cell / n), e1 per_cell / n for points on a line, never below e1 / 60000, 1 for a cloud without extent.  The edge is a
+ * speed choice for sga_knn_lists_grid and never part of a result; its arithmetic is not pinned.
+ *
+ * order [total_points] int32 is the STABLE ascending argsort of keys, an INPUT of everything below (the 64-bit sort is borrowed: the
+ * Python wrapper takes it from torch.sort(keys, stable=True)).  The cloud id is the top field and clouds are packed in ascending order,
+ * so the sorted positions of cloud c are exactly [offsets[c], offsets[c + 1]) and the points of a cell come in ascending original index.
+ * sga_voxel_cells verifies that in O(n): every entry of a cloud's range lies in the cloud and the pairs (key, index) are strictly
+ * increasing along it -- together a proof of the stable permutation.  A cloud that fails gets status 3 and produces nothing (status 2
+ * stays 2).  It writes sorted_keys [total_points] int64 (keys[order[t]]; the cloud's dropped key where order[t] is outside the cloud).
+ * A sorted position is a HEAD when its point is kept and it is the first of its cloud or its key differs from its predecessor's; voxel
+ * ids are the exclusive prefix sum of the heads (a block scan plus one workgroup over the block totals, no atomics), cloud-local after
+ * subtracting the cloud's first.  Voxels are therefore numbered in ascending (kx, ky, kz) -- NOT Open3D's hash-map order.
+ * voxel_of_point [total_points] int32: the cloud-local voxel of each point, -1 for a dropped point and for clouds of status 2 / 3.
+ * voxel_offsets [n_clouds + 1] int32: the prefix of voxels per cloud.  voxel_first [total_points + 1] int32: entry voxel_offsets[c] + v is
+ * the sorted position of the head of voxel v of cloud c; the run of a voxel ends where sorted_keys changes or the cloud ends (for all but
+ * a cloud's last voxel that is the next entry); entry voxel_offsets[n_clouds] holds total_points, later entries are not written.
+ * status [n_clouds] is read (0 / 2 from sga_voxel_keys) and updated.  workspace: sga_voxel_workspace_bytes(n_clouds, total_points).
+ *
+ * sga_voxel_downsample: voxel g (global id) with sorted run [s, e): sum = 0, then sum += pts[order[t]] for t ascending -- ascending
+ * original index --, out_pts[g] = sum / (e - s), out_count[g] = e - s; normals [total_points, 3] f64 (nullable, with out_normals):
+ * out_normals[g] is the same mean, NOT re-normalised.  The caller sizes out_pts / out_normals / out_count for total_points voxels;
+ * voxel_offsets[n_clouds] of them are written, packed by cloud.  Colours are not carried.
+ *
+ * sga_knn_lists_grid: count / idx / d2 of sga_knn_lists, bit for bit, for every input and every cell size: the grid decides how much of
+ * a cloud is looked at, never what comes out.  Per query, the blocks of cells |k - c|inf <= R, R = 1, 2, 4, 8, 16, are scanned until no point
+ * outside the block can enter the list (the proof is at the head of csrc/voxel.hip); a query that stays undecided, a dropped query, and
+ * every query of a cloud whose status is not 0 walks its whole cloud as sga_knn_lists does.  cell / origin / dims / status / order /
+ * sorted_keys are the arrays of sga_voxel_keys and sga_voxel_cells for the same pts and offsets.  r2 and max_nn as in sga_knn_lists. */
+size_t sga_voxel_workspace_bytes(int n_clouds, int total_points);
+int sga_cloud_bounds(const double* pts, const int32_t* offsets, int n_clouds, int total_points, const int32_t* offsets_host, double* box,
+                     double per_cell, double* edge, void* stream);
+int sga_voxel_keys(const double* pts, const int32_t* offsets, int n_clouds, int total_points, const int32_t* offsets_host,
+                   const double* cell, const double* cell_host, double* origin, int32_t* dims, int64_t* keys, int32_t* status, void* stream);
+int sga_voxel_cells(const int32_t* offsets, int n_clouds, int total_points, const int32_t* offsets_host, const int64_t* keys,
+                    const int32_t* order, int64_t* sorted_keys, int32_t* voxel_of_point, int32_t* voxel_offsets, int32_t* voxel_first,
+                    int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int sga_voxel_downsample(const double* pts, const double* normals, const int32_t* offsets, int n_clouds, int total_points,
+                         const int32_t* offsets_host, const int32_t* order, const int64_t* sorted_keys, const int32_t* voxel_offsets,
+                         const int32_t* voxel_first, const int32_t* status, double* out_pts, double* out_normals, int32_t* out_count,
+                         void* stream);
+int sga_knn_lists_grid(const double* pts, const int32_t* offsets, int n_clouds, int total_points, const int32_t* offsets_host,
+                       const double* cell, const double* origin, const int32_t* dims, const int32_t* status, const int32_t* order,
+                       const int64_t* sorted_keys, double r2, int max_nn, int32_t* count, int32_t* idx, double* d2, void* stream);
+
 /* ---- batched RANSAC rigid registration from point correspondences, fp64 -------------------------------------------------------
  * the estimator of src/engine/registration_evaluator.py:129-208 (pygcransac.findRigidTransform with min_iters == max_iters and
  * spatial_coherence_weight == 0: a fixed number of three-point hypotheses, scored against every correspondence, then least-squares refits

@@ -40,6 +40,8 @@ FILE_FLAGS = {'contrastive.hip': ['-fno-slp-vectorize'],
               'featnn.hip': ['-ffp-contract=off'],
               # fpfh.hip: neighbour-list distances bit-identical to nnsearch.hip's, and the FPFH weighting's pinned fp64 operation order (no FMA)
               'fpfh.hip': ['-ffp-contract=off'],
+              # voxel.hip: cell coordinates and voxel means bit-identical to their NumPy restatement, list distances to fpfh.hip's (no FMA)
+              'voxel.hip': ['-ffp-contract=off'],
               # visibility.hip: same -- the frustum tests are bit-identical to the NumPy restatement of the reference's projection
               'visibility.hip': ['-ffp-contract=off']}
 

@@ -78,6 +78,12 @@ SIGNATURES = {
     'sga_normals': (I, [P, P, I, I, P, P, P, I, P, P, P, P]),
     'sga_spfh_counts': (I, [P, P, P, I, I, P, P, P, P, I, P, P]),
     'sga_fpfh': (I, [P, P, I, I, P, P, P, P, I, P, P, I, P]),
+    'sga_voxel_workspace_bytes': (c_size_t, [I, I]),
+    'sga_cloud_bounds': (I, [P, P, I, I, P, P, c_double, P, P]),
+    'sga_voxel_keys': (I, [P, P, I, I, P, P, P, P, P, P, P, P]),
+    'sga_voxel_cells': (I, [P, I, I, P, P, P, P, P, P, P, P, P, c_size_t, P]),
+    'sga_voxel_downsample': (I, [P, P, P, I, I, P, P, P, P, P, P, P, P, P, P]),
+    'sga_knn_lists_grid': (I, [P, P, I, I, P, P, P, P, P, P, P, c_double, I, P, P, P, P]),
     'sga_ransac_workspace_bytes': (c_size_t, [I, I, I, I]),
     'sga_ransac_rigid': (I, [P, P, I, I, P, P, I, I, I, I, P, P, c_double, I, P, P, P, P, P, P, P, c_size_t, P]),
     'sga_subscan_lds_slots': (I, []),

@@ -64,7 +64,7 @@ class RegistrationEvaluator:
     RESULT_KEYS = ('CD', 'IR', 'RRE', 'RTE', 'recall', 'FMR')
 
     def __init__(self, point_matcher, num_p2p_corrs=20000, ransac_threshold=0.03, ransac_iters=5000, inlier_ratio_thresh=0.05,
-                 rmse_thresh=0.2, min_object_points=50, seed=0):
+                 rmse_thresh=0.2, min_object_points=50, seed=0, voxel_size=None):
         if not callable(point_matcher):
             raise TypeError('point_matcher must be callable: (src_pts, ref_pts, gt_transform) -> dict or None')
         self.point_matcher = point_matcher
@@ -75,6 +75,12 @@ class RegistrationEvaluator:
         self.rmse_thresh = rmse_thresh
         self.min_object_points = int(min_object_points)
         self.seed = int(seed)
+        # voxel_size: clouds are down-sampled by voxels of this edge on the device (utils/voxel.py) before they are matched -- the two
+        # whole clouds of run_normal_registration instead of the random draw of 10 000 rows, every eligible object cloud of
+        # collect_correspondences in one call.  None: no voxel step anywhere.
+        self.voxel_size = None if voxel_size is None else float(voxel_size)
+        if self.voxel_size is not None and not (self.voxel_size > 0.0 and np.isfinite(self.voxel_size)):
+            raise ValueError(f'voxel_size must be > 0 and finite, or None (got {voxel_size})')
 
     def evaluate_registration(self, src_points, ref_points, raw_points, est_transform, gt_transform, src_corr_points, ref_corr_points,
                               gt_src_corr_points, gt_ref_corr_points):
@@ -99,6 +105,10 @@ class RegistrationEvaluator:
             if min(obj_src.shape[0], obj_ref.shape[0]) < self.min_object_points:
                 continue
             eligible.append((obj_src, obj_ref))
+        if self.voxel_size is not None and eligible:                                 # min_object_points was tested on the raw counts
+            from .utils.voxel import voxel_downsample_many
+            flat = voxel_downsample_many([c for pair in eligible for c in pair], self.voxel_size)
+            eligible = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(eligible))]
         if hasattr(self.point_matcher, 'match_many'):
             results = self.point_matcher.match_many(eligible)                       # all node pairs of the call in one launch set
         else:
@@ -138,15 +148,20 @@ class RegistrationEvaluator:
 
     def run_normal_registration(self, reg_data_dict, evaluate_registration=True):
         """src/engine/registration_evaluator.py:92-127: registration of the two WHOLE clouds, without the aligner's node matches.  Each
-        cloud is subsampled to 10 000 rows when larger (numpy.random.default_rng(self.seed)), the matcher's match_many matches them, and
+        cloud is subsampled to 10 000 rows when larger (numpy.random.default_rng(self.seed)) -- or, with voxel_size, down-sampled by voxels
+        instead --, the matcher's match_many matches them, and
         the transform is estimated by RANSAC on those correspondences with the evaluator's threshold and iteration count.  (The reference
         takes GeoTransformer's own estimate, output_dict['estimated_transform'], at this point; a matcher here yields correspondences
         only.)  -> None (no correspondences or no model), (transform, mean correspondence score) with evaluate_registration=False, or the
         dict of CD / IR / RRE / RTE / recall / FMR."""
         if not hasattr(self.point_matcher, 'match_many'):
             raise TypeError('run_normal_registration matches whole clouds: the point matcher needs match_many (FeatureMatcher has it)')
-        rng = np.random.default_rng(self.seed)
-        src, ref = self._subsample(reg_data_dict['src_points'], rng), self._subsample(reg_data_dict['ref_points'], rng)
+        if self.voxel_size is not None:
+            from .utils.voxel import voxel_downsample_many
+            src, ref = voxel_downsample_many([reg_data_dict['src_points'], reg_data_dict['ref_points']], self.voxel_size)
+        else:
+            rng = np.random.default_rng(self.seed)
+            src, ref = self._subsample(reg_data_dict['src_points'], rng), self._subsample(reg_data_dict['ref_points'], rng)
         matched, = self.point_matcher.match_many([(src, ref)])
         if matched is None:
             return None

@@ -76,17 +76,35 @@ def _lists(lists, total, dev):
     return count, idx, d2, _check_max_nn(idx.shape[1])
 
 
-def neighbour_lists(points, offsets, radius=None, max_nn=30):
+SEARCHES = ('brute', 'grid')
+
+
+def _check_search(search) -> str:
+    if search not in SEARCHES:
+        raise ValueError(f'search must be one of {SEARCHES}, got {search!r}')
+    return search
+
+
+def neighbour_lists(points, offsets, radius=None, max_nn=30, search='brute', cell=None):
     """points [sum N, 3] float64 HIP tensor (clouds packed back to back), offsets [n_clouds + 1] host ints.  For every point the first
     `max_nn` of the points of ITS cloud within `radius` (None: no radius, pure k-NN), sorted ascending by (squared distance, index); the
     point itself is entry 0 unless a duplicate with a lower index precedes it.  -> (count [total] int32, idx [total, max_nn] int32
     cloud-local, -1 past count, d2 [total, max_nn] float64, +inf past count), HIP tensors.  Exact (brute force): d2 = (dx*dx + dy*dy) +
-    dz*dz with every operation rounded on its own, the arithmetic of nearest_neighbor_batch; a NaN distance never enters a list."""
+    dz*dz with every operation rounded on its own, the arithmetic of nearest_neighbor_batch; a NaN distance never enters a list.
+    search='grid' looks only at the cells around each point (csrc/voxel.hip through utils/voxel.py) and gives the SAME lists, bit for
+    bit, whatever `cell` is: the cell edge, one for all clouds or one per cloud; None: voxel.default_cell (the radius where one is
+    given, else a per-cloud edge from the bounding box, the point count and max_nn: half a list per cell of a surface).  It is the route for clouds far above 20 000 points."""
     C = _clouds(points, offsets)
     max_nn = _check_max_nn(max_nn)
+    _check_search(search)
     r2 = float('inf') if radius is None else float(radius) * float(radius)
     if not r2 >= 0.0:
         raise ValueError(f'radius must be >= 0 or None, got {radius}')
+    if search == 'grid':
+        from . import voxel
+        out = NeighbourLists(voxel.grid_lists(C, None, r2, max_nn, cell, radius))
+        out.offsets = C.pt_off
+        return out
     count = torch.empty((C.total_points,), device=C.dev, dtype=torch.int32)
     idx = torch.empty((C.total_points, max_nn), device=C.dev, dtype=torch.int32)
     d2 = torch.empty((C.total_points, max_nn), device=C.dev, dtype=torch.float64)
@@ -98,17 +116,18 @@ def neighbour_lists(points, offsets, radius=None, max_nn=30):
     return out
 
 
-def estimate_normals_batch(points, offsets, radius=None, max_nn=30, viewpoints=None, lists=None):
+def estimate_normals_batch(points, offsets, radius=None, max_nn=30, viewpoints=None, lists=None, search='brute', cell=None):
     """Normals of every point from its neighbour list (`lists`, or neighbour_lists(points, offsets, radius, max_nn)): the unit eigenvector
     of the smallest eigenvalue of the neighbours' covariance.  viewpoints [n_clouds, 3] (HIP float64 tensor or host array): the normal is
     turned towards its cloud's viewpoint; None: turned so that its component of largest magnitude is positive.  A point with fewer than 3
-    neighbours gets (0, 0, 1) and status 1.  -> (normals [total, 3] float64, status [total] int32), HIP tensors."""
+    neighbours gets (0, 0, 1) and status 1.  search / cell: how neighbour_lists builds the lists when none are given.
+    -> (normals [total, 3] float64, status [total] int32), HIP tensors."""
     check_dtype(points, 'points', torch.float64)
     if lists is not None:
         _list_dtypes(lists)
     C = _clouds(points, offsets)
     if lists is None:
-        lists = neighbour_lists(C, None, radius, max_nn)
+        lists = neighbour_lists(C, None, radius, max_nn, search, cell)
     count, idx, _, width = _lists(lists, C.total_points, C.dev)
     vp = None
     if viewpoints is not None:
@@ -168,21 +187,23 @@ def fpfh_from_counts(counts, lists, want_f64=False, offsets=None):
     return (out32, out64) if want_f64 else out32
 
 
-def fpfh_batch(points, offsets, normals=None, radius_normal=None, max_nn_normal=30, radius_feature=None, max_nn_feature=100, viewpoints=None):
+def fpfh_batch(points, offsets, normals=None, radius_normal=None, max_nn_normal=30, radius_feature=None, max_nn_feature=100, viewpoints=None,
+               search='brute', cell=None):
     """The whole chain for clouds packed back to back: points [sum N, 3] float64 HIP tensor, offsets [n_clouds + 1] host ints.  Normals
     (when none are given) from lists of (radius_normal, max_nn_normal), oriented by `viewpoints`; features from lists of (radius_feature,
-    max_nn_feature).  -> [total, 36] float32 HIP tensor, bitwise what the four stages give when called one by one."""
+    max_nn_feature).  search / cell: the route of both neighbour_lists calls; the result does not depend on them.
+    -> [total, 36] float32 HIP tensor, bitwise what the four stages give when called one by one."""
     check_dtype(points, 'points', torch.float64)
     if normals is not None:
         check_dtype(normals, 'normals', torch.float64)
     C = _clouds(points, offsets)
     if normals is None:
-        normals, _ = estimate_normals_batch(C, None, radius_normal, max_nn_normal, viewpoints)
-    lists = neighbour_lists(C, None, radius_feature, max_nn_feature)
+        normals, _ = estimate_normals_batch(C, None, radius_normal, max_nn_normal, viewpoints, search=search, cell=cell)
+    lists = neighbour_lists(C, None, radius_feature, max_nn_feature, search, cell)
     return fpfh_from_counts(spfh_counts(C, normals, None, lists), lists, offsets=C.pt_off)
 
 
-def estimate_normals(points, radius=None, max_nn=30, viewpoint=None):
+def estimate_normals(points, radius=None, max_nn=30, viewpoint=None, search='brute', cell=None):
     """utils/open3d.py:61-66 for one cloud: points [n, 3] numpy -> normals [n, 3] float64 numpy.  The defaults are the reference's
     (pcd.estimate_normals(): the 30 nearest neighbours, no radius)."""
     _need_device('estimate_normals')
@@ -190,16 +211,18 @@ def estimate_normals(points, radius=None, max_nn=30, viewpoint=None):
     if len(p) == 0:
         return np.zeros((0, 3))
     vp = None if viewpoint is None else np.asarray(viewpoint, dtype=np.float64).reshape(1, 3)
-    normals, _ = estimate_normals_batch(torch.from_numpy(p).cuda(), [0, len(p)], radius, max_nn, vp)
+    normals, _ = estimate_normals_batch(torch.from_numpy(p).cuda(), [0, len(p)], radius, max_nn, vp, search=search, cell=cell)
     return normals.cpu().numpy()
 
 
 class FPFHDescriptor:
     """descriptor(points [n, 3]) -> [n, 33] float32 numpy, the callable FeatureMatcher wants.  Normals from (radius_normal,
     max_nn_normal), oriented towards `viewpoint` (one fixed point for every cloud -- the evaluator's two clouds share one frame -- or
-    None), features from (radius_feature, max_nn_feature).  `many` computes a list of clouds in one launch set and one download."""
+    None), features from (radius_feature, max_nn_feature).  `many` computes a list of clouds in one launch set and one download.
+    search / cell: the route of the neighbour lists ('grid' for large clouds); the descriptors do not depend on them."""
 
-    def __init__(self, radius_normal=None, max_nn_normal=30, radius_feature=None, max_nn_feature=100, viewpoint=None):
+    def __init__(self, radius_normal=None, max_nn_normal=30, radius_feature=None, max_nn_feature=100, viewpoint=None, search='brute', cell=None):
+        self.search, self.cell = _check_search(search), cell
         self.radius_normal, self.max_nn_normal = radius_normal, _check_max_nn(max_nn_normal)
         self.radius_feature, self.max_nn_feature = radius_feature, _check_max_nn(max_nn_feature)
         self.viewpoint = None if viewpoint is None else np.asarray(viewpoint, dtype=np.float64).reshape(3)
@@ -214,7 +237,8 @@ class FPFHDescriptor:
             return [np.zeros((0, BINS), dtype=np.float32) for _ in clouds]
         pts = torch.from_numpy(np.concatenate(clouds) if len(clouds) > 1 else clouds[0]).cuda()
         vps = None if self.viewpoint is None else np.tile(self.viewpoint, (len(clouds), 1))
-        feats = fpfh_batch(pts, off, None, self.radius_normal, self.max_nn_normal, self.radius_feature, self.max_nn_feature, vps)
+        feats = fpfh_batch(pts, off, None, self.radius_normal, self.max_nn_normal, self.radius_feature, self.max_nn_feature, vps,
+                           self.search, self.cell)
         feats = feats[:, :BINS].cpu().numpy()
         return [np.ascontiguousarray(feats[off[i]:off[i + 1]]) for i in range(len(clouds))]
 
