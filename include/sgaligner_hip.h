@@ -660,6 +660,71 @@ int sga_knn_lists_grid(const double* pts, const int32_t* offsets, int n_clouds, 
                        const double* cell, const double* origin, const int32_t* dims, const int32_t* status, const int32_t* order,
                        const int64_t* sorted_keys, double r2, int max_nn, int32_t* count, int32_t* idx, double* d2, void* stream);
 
+/* ---- cross-cloud nearest neighbour through the support cloud's grid (fp64; csrc/icp.hip) --------------------------------------------
+ * The search under ICP refinement and under the geometric score of a transform (Open3D's evaluate_registration): for every query of one
+ * cloud, moved by a transform, the nearest point of ANOTHER cloud within a radius, without nq x ns work.  tests/icp_ref.py restates the
+ * text below in numpy.
+ * pts / offsets / pairs / out_offsets / total_queries / max_queries / offsets_host / pairs_host / squared / out_dist / out_idx: as in
+ * sga_nn_search (a job is a (query cloud, support cloud) pair; csrc/pair_jobs.h).  cell / origin / dims / status / order / sorted_keys:
+ * the arrays of sga_voxel_keys and sga_voxel_cells for the same pts and offsets (every cloud that is a support has its grid there).
+ * transforms [n_pairs, 12] f64 DEVICE, nullable: row-major [R | t] per job, m[0..8] = R, m[9..11] = t (sga_ransac_rigid's model layout).
+ * r2 >= 0, +inf: no radius.
+ * The moved query: without transforms q' = q.  With them x' = ((m0*x + m1*y) + m2*z) + m9, y' = ((m3*x + m4*y) + m5*z) + m10,
+ * z' = ((m6*x + m7*y) + m8*z) + m11, every operation rounded on its own (no FMA).
+ * The result: among the support points with d2 <= r2 the one of minimal d2, the LOWEST support-cloud-local index among exactly equal
+ * minima; d2 = (dx*dx + dy*dy) + dz*dz, dx = x' - s.x ...: sga_nn_search's arithmetic and its rules -- a NaN never wins, an empty support
+ * gives +inf, -1 -- and nothing within r2 gives +inf, -1 as well.  out_dist = d2 when squared != 0, else the correctly rounded sqrt(d2).
+ * The grid decides how much of the support is looked at, never what comes out: for every input and every cell size out_dist / out_idx
+ * equal, as bit patterns, what sga_nn_search gives on the moved points, masked by d2 <= r2.  Per query the cell coordinate relative to
+ * the support's origin / cell is clamped (in fp64) into the support's cell box, the blocks |k - c|inf <= R, R = 1, 2, 4, 8, 16, around the
+ * clamped cell are scanned until no point outside the block can win (the proof, also for a centre outside the box, is at the head of
+ * csrc/icp.hip) or the block covers the box; a query that stays undecided, a query with a non-finite moved coordinate and every query
+ * against a support whose status is not 0 walks the whole support.  One wave per query; no atomics, no workspace, stream-ordered; the
+ * kernel re-checks every id, offset and index it reads. */
+int sga_nn_search_grid(const double* pts, const int32_t* offsets, int n_clouds, int total_points, const int32_t* pairs, int n_pairs,
+                       const int32_t* out_offsets, int total_queries, int max_queries, const int32_t* offsets_host, const int32_t* pairs_host,
+                       const double* cell, const double* origin, const int32_t* dims, const int32_t* status, const int32_t* order,
+                       const int64_t* sorted_keys, const double* transforms, double r2, int squared, double* out_dist, int32_t* out_idx,
+                       void* stream);
+
+/* ---- batched ICP refinement, point-to-point and point-to-plane (fp64; csrc/icp.hip) -------------------------------------------------
+ * Open3D's registration_icp loop -- evaluate; then repeat { update, evaluate, stop when both changes are small } -- for every job of a
+ * list at once, and with max_iters = 0 its evaluate_registration: fitness, inlier RMSE and the correspondence set of a transform at a
+ * distance.  Open3D is not a dependency and equality with its output is not tested: the text below is the definition
+ * (tests/icp_ref.py restates it in numpy, with SVD Kabsch and numpy.linalg.solve as the yardstick solvers).
+ * Jobs, clouds and grid arrays as in sga_nn_search_grid: job p aligns its query cloud (the source) to its support cloud (the reference).
+ * r2: the squared maximal correspondence distance.  method: 0 point-to-point, 1 point-to-plane.  normals [total_points, 3] f64: the
+ * normals of every cloud that is a support (method 1; nullable for method 0).  pivot [n_pairs, 3] f64: a point near the job's clouds (the
+ * Python layer passes the support cloud's box minimum from sga_cloud_bounds); all sums are taken about it, so that coordinates of order
+ * 10^3 cost no digits.  max_iters >= 0; rel_fitness, rel_rmse: the stop thresholds.
+ * transform [n_pairs, 12] f64, IN / OUT: row-major [R | t] per job, the initial estimate on entry, the final one on return.
+ * Out, per job: fitness, inlier_rmse (f64), iters, status (int32), trace [n_pairs, max_iters + 1, 2] f64 (fitness and RMSE of every
+ * evaluation made, NaN after the last), and out_idx / out_d2 [total_queries] laid out by out_offsets: sga_nn_search_grid's outputs
+ * (squared distances) for the FINAL transform.
+ * Evaluation k = 0, 1, ... of a job: the search with the current transform T; count = #{out_idx >= 0}; fitness = count / nq (0 for an
+ * empty query cloud); rmse = sqrt(sum d2 / count), 0 without a pair; both go to trace[k]; iters = k.  The job is done with status 0 when
+ * k == max_iters, or when k >= 1 and |fitness - previous| < rel_fitness and |rmse - previous| < rel_rmse.  Otherwise an update U is
+ * computed from the pairs and T <- U T (R <- R_U R, t <- R_U t + t_U):
+ *   fewer than 3 pairs (method 0) or fewer than 6 (method 1): status 1, the job is done and T is kept.
+ *   method 0: U = the least-squares proper rotation + translation of the pairs (x', s), x' the moved query: Horn's quaternion from the 15
+ *     moments sum a, sum b, sum a b^T, a = x' - pivot, b = s - pivot (sga_ransac_rigid's solver).
+ *   method 1: with n the partner's normal, r = (a - b) . n and J = [a x n, n] (6 entries): (sum J J^T) x = -sum J r by Cholesky without
+ *     pivoting; a pivot that is <= 0 or not finite gives status 2, the job is done and T is kept.  R_U = Rz(x2) Ry(x1) Rx(x0),
+ *     t_U = (x3, x4, x5) + pivot - R_U pivot.
+ *   a non-finite U or U T: status 2, done, T kept.
+ * A job whose ids or offsets are out of range on the device: status 3, nothing else of it is written but fitness = rmse = 0, iters = 0.
+ * The sums are a fixed fold (csrc/icp.hip: lanes in row order, wave butterfly, waves in order, slices of 1024 query rows counted from the
+ * job's first row, ascending): no atomics, two calls give the same bits, and a job in a batch gives the bits of the same job alone.
+ * One stream, no host synchronisation inside the call: max_iters + 1 rounds of three kernels (search, accumulate, step); a finished job
+ * sets a flag in the workspace and later rounds skip its workgroups.  workspace: sga_icp_workspace_bytes(n_pairs, max_queries). */
+size_t sga_icp_workspace_bytes(int n_pairs, int max_queries);
+int sga_icp(const double* pts, const int32_t* offsets, int n_clouds, int total_points, const int32_t* pairs, int n_pairs,
+            const int32_t* out_offsets, int total_queries, int max_queries, const int32_t* offsets_host, const int32_t* pairs_host,
+            const double* cell, const double* origin, const int32_t* dims, const int32_t* grid_status, const int32_t* order,
+            const int64_t* sorted_keys, double r2, int method, const double* normals, const double* pivot, int max_iters, double rel_fitness,
+            double rel_rmse, double* transform, double* fitness, double* inlier_rmse, int32_t* iters, int32_t* status, double* trace,
+            int32_t* out_idx, double* out_d2, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- batched RANSAC rigid registration from point correspondences, fp64 -------------------------------------------------------
  * the estimator of src/engine/registration_evaluator.py:129-208 (pygcransac.findRigidTransform with min_iters == max_iters and
  * spatial_coherence_weight == 0: a fixed number of three-point hypotheses, scored against every correspondence, then least-squares refits

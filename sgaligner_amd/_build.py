@@ -42,6 +42,8 @@ FILE_FLAGS = {'contrastive.hip': ['-fno-slp-vectorize'],
               'fpfh.hip': ['-ffp-contract=off'],
               # voxel.hip: cell coordinates and voxel means bit-identical to their NumPy restatement, list distances to fpfh.hip's (no FMA)
               'voxel.hip': ['-ffp-contract=off'],
+              # icp.hip: moved queries and distances bit-identical to their NumPy restatement and to nnsearch.hip's (no FMA)
+              'icp.hip': ['-ffp-contract=off'],
               # visibility.hip: same -- the frustum tests are bit-identical to the NumPy restatement of the reference's projection
               'visibility.hip': ['-ffp-contract=off']}
 

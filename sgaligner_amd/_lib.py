@@ -84,6 +84,10 @@ SIGNATURES = {
     'sga_voxel_cells': (I, [P, I, I, P, P, P, P, P, P, P, P, P, c_size_t, P]),
     'sga_voxel_downsample': (I, [P, P, P, I, I, P, P, P, P, P, P, P, P, P, P]),
     'sga_knn_lists_grid': (I, [P, P, I, I, P, P, P, P, P, P, P, c_double, I, P, P, P, P]),
+    'sga_nn_search_grid': (I, [P, P, I, I, P, I, P, I, I, P, P, P, P, P, P, P, P, P, c_double, I, P, P, P]),
+    'sga_icp_workspace_bytes': (c_size_t, [I, I]),
+    'sga_icp': (I, [P, P, I, I, P, I, P, I, I, P, P, P, P, P, P, P, P, c_double, I, P, P, I, c_double, c_double, P, P, P, P, P, P, P, P, P,
+                    c_size_t, P]),
     'sga_ransac_workspace_bytes': (c_size_t, [I, I, I, I]),
     'sga_ransac_rigid': (I, [P, P, I, I, P, P, I, I, I, I, P, P, c_double, I, P, P, P, P, P, P, P, c_size_t, P]),
     'sga_subscan_lds_slots': (I, []),

@@ -64,7 +64,7 @@ class RegistrationEvaluator:
     RESULT_KEYS = ('CD', 'IR', 'RRE', 'RTE', 'recall', 'FMR')
 
     def __init__(self, point_matcher, num_p2p_corrs=20000, ransac_threshold=0.03, ransac_iters=5000, inlier_ratio_thresh=0.05,
-                 rmse_thresh=0.2, min_object_points=50, seed=0, voxel_size=None):
+                 rmse_thresh=0.2, min_object_points=50, seed=0, voxel_size=None, refine=None, refine_distance=None):
         if not callable(point_matcher):
             raise TypeError('point_matcher must be callable: (src_pts, ref_pts, gt_transform) -> dict or None')
         self.point_matcher = point_matcher
@@ -81,6 +81,33 @@ class RegistrationEvaluator:
         self.voxel_size = None if voxel_size is None else float(voxel_size)
         if self.voxel_size is not None and not (self.voxel_size > 0.0 and np.isfinite(self.voxel_size)):
             raise ValueError(f'voxel_size must be > 0 and finite, or None (got {voxel_size})')
+        # refine: ICP ('point' or 'plane', utils.registration.icp_pairs) on the RANSAC transform -- in run_normal_registration on the
+        # clouds the matcher saw, in run_aligner_registration[_batch] on the whole src_points / ref_points down-sampled by the same rule
+        # (voxels, or the draw of 10 000 rows).  refine_distance: ICP's maximal correspondence distance; None: ransac_threshold, the
+        # evaluator's own "this close counts as matched".  None: no refinement, every result as without the argument.
+        if refine not in (None, 'point', 'plane'):
+            raise ValueError(f"refine must be None, 'point' or 'plane' (got {refine!r})")
+        self.refine = refine
+        self.refine_distance = self.ransac_threshold if refine_distance is None else float(refine_distance)
+        if not self.refine_distance > 0.0:
+            raise ValueError(f'refine_distance must be > 0 (got {refine_distance})')
+
+    def _refine_clouds(self, list_of_clouds):
+        """The clouds ICP refines on: down-sampled by the rule run_normal_registration applies before matching."""
+        if self.voxel_size is not None:
+            from .utils.voxel import voxel_downsample_many
+            return voxel_downsample_many(list_of_clouds, self.voxel_size)
+        out = []
+        for k in range(0, len(list_of_clouds), 2):                                   # per pair: the generator starts afresh, as there
+            rng = np.random.default_rng(self.seed)
+            out += [self._subsample(c, rng) for c in list_of_clouds[k:k + 2]]
+        return out
+
+    def _refine(self, pairs, transforms):
+        """[(src, ref), ...] and their RANSAC transforms -> the ICP-refined transforms, all pairs in ONE icp_pairs call.  A pair whose ICP
+        stops early (too few correspondences, an unsolvable update) keeps the last transform it reached."""
+        res = registration.icp_pairs(pairs, transforms, self.refine_distance, method=self.refine)
+        return [r['transformation'] for r in res]
 
     def evaluate_registration(self, src_points, ref_points, raw_points, est_transform, gt_transform, src_corr_points, ref_corr_points,
                               gt_src_corr_points, gt_ref_corr_points):
@@ -169,6 +196,8 @@ class RegistrationEvaluator:
         (est_transform, _), = self._solve([corr])
         if est_transform is None:
             return None
+        if self.refine is not None:
+            est_transform, = self._refine([(src, ref)], [est_transform])
         if not evaluate_registration:
             return est_transform, np.mean(matched['corr_scores'])
         return self._finish(reg_data_dict, corr, est_transform, True)
@@ -188,6 +217,9 @@ class RegistrationEvaluator:
         if corr is None:
             return None
         (est_transform, _), = self._solve([corr])
+        if self.refine is not None and est_transform is not None:
+            src, ref = self._refine_clouds([reg_data_dict['src_points'], reg_data_dict['ref_points']])
+            est_transform, = self._refine([(src, ref)], [est_transform])
         return self._finish(reg_data_dict, corr, est_transform, evaluate_registration)
 
     def run_aligner_registration_batch(self, list_of_reg_data_dicts, evaluate_registration=True):
@@ -195,5 +227,11 @@ class RegistrationEvaluator:
         corrs = [self.collect_correspondences(d) for d in list_of_reg_data_dicts]
         live = [i for i, c in enumerate(corrs) if c is not None]
         solved = dict(zip(live, self._solve([corrs[i] for i in live]))) if live else {}
+        found = [i for i in live if solved[i][0] is not None]
+        if self.refine is not None and found:                                        # every solved pair in one icp_pairs call
+            flat = self._refine_clouds([list_of_reg_data_dicts[i][k] for i in found for k in ('src_points', 'ref_points')])
+            refined = self._refine([(flat[2 * j], flat[2 * j + 1]) for j in range(len(found))], [solved[i][0] for i in found])
+            for i, T in zip(found, refined):
+                solved[i] = (T, solved[i][1])
         return [None if i not in solved else self._finish(d, corrs[i], solved[i][0], evaluate_registration)
                 for i, d in enumerate(list_of_reg_data_dicts)]

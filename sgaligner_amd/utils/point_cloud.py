@@ -8,7 +8,8 @@ one launch.
 
 `get_nearest_neighbor`, `compute_pcl_overlap` and `apply_transform` keep the reference signatures (utils/point_cloud.py:136-157,
 91-103); `nearest_neighbor_batch` / `compute_pcl_overlap_pairs` are the batched forms (csrc/nnsearch.hip: exact fp64 brute force,
-distances bit-identical to cKDTree's, ties to the lowest index).
+distances bit-identical to cKDTree's, ties to the lowest index; search='grid': the same answers through the support cloud's cell grid,
+with a radius and a transform per job, csrc/icp.hip).
 
 `inverse_relative` and `get_visible_pts_from_cam_pose` keep the reference signatures (utils/point_cloud.py:105-134);
 `visible_masks_batch` is the packed form (csrc/visibility.hip: every frame of every scan in one launch, bit masks out)."""
@@ -218,12 +219,60 @@ def _nn_chunk(sizes_q, sizes_s) -> int:
     return split_chunk(tiles, max(sizes_s, default=0), _lib.lib().sga_device_cus(), 16, NN_MIN_CHUNK)
 
 
-def nearest_neighbor_batch(points, offsets, pairs, chunk=None, squared=False):
+NN_SEARCHES = ('brute', 'grid')
+NN_GRID_POINTS_PER_CELL = 16     # the default cell of the cross-cloud grid search: the fastest of 0.5 .. 64 measured on surfaces
+
+
+def nn_grid_cell(clouds, radius=None):
+    """The cell edge the cross-cloud grid search takes when none is given -- a speed choice only, the results do not depend on it: per
+    cloud the edge at which an occupied cell of a surface holds about NN_GRID_POINTS_PER_CELL points (voxel.default_cell), capped at the
+    radius where one is given (beyond it the 3 x 3 x 3 block holds more than the ball).  -> [n_clouds] float64 HIP tensor, no download."""
+    from . import voxel
+    edge = voxel.default_cell(clouds, None, None, int(NN_GRID_POINTS_PER_CELL / voxel.POINTS_PER_CELL))
+    if radius is not None and float(radius) > 0.0 and np.isfinite(float(radius)):
+        edge = torch.clamp(edge, max=float(radius))
+    return edge
+
+
+def _nn_grid(pts, J, radius, transforms, cell, squared, dist, idx):
+    """The grid route of nearest_neighbor_batch (csrc/icp.hip): the grid of every cloud of the call (utils/voxel.build_grid), then one
+    launch for all jobs.  The cell edge is a speed choice only (nn_grid_cell)."""
+    from . import voxel
+    from .features import _Clouds
+    r2 = float('inf') if radius is None else float(radius) * float(radius)
+    if not r2 >= 0.0:
+        raise ValueError(f'radius must be >= 0 or None, got {radius}')
+    tr = None
+    if transforms is not None:
+        tr = device_tensor(transforms, 'transforms', torch.float64)
+        if tuple(tr.shape) != (J.n_pairs, 12):
+            raise ValueError(f'transforms must be [{J.n_pairs}, 12] (row-major R | t per job), got {tuple(tr.shape)}')
+    C = _Clouds(pts, J.off)
+    G = voxel.build_grid(C, None, nn_grid_cell(C, radius) if cell is None else cell)
+    _, d_pr, d_oo = upload(J.host_parts(), pts.device)
+    rc = _lib.lib().sga_nn_search_grid(_p(pts), _p(C.d_off), J.n_sets, int(pts.shape[0]), _p(d_pr), J.n_pairs, _p(d_oo), J.total_q, J.max_q,
+                                       J.h_off.ctypes.data, J.h_pr.ctypes.data, _p(G.cell), _p(G.origin), _p(G.dims), _p(G.status), _p(G.order),
+                                       _p(G.sorted_keys), _p(tr) if tr is not None else None, r2, 1 if squared else 0, _p(dist), _p(idx),
+                                       _stream())
+    _lib.check(rc, 'sga_nn_search_grid')
+
+
+def nearest_neighbor_batch(points, offsets, pairs, chunk=None, squared=False, search='brute', radius=None, transforms=None, cell=None):
     """points [sum N, 3] float64 CUDA tensor (clouds packed back to back), offsets [n_clouds+1] host ints, pairs [n_pairs, 2] host ints
     (query cloud, support cloud).  One launch for all jobs.  Returns (dist [sum nq] float64, idx [sum nq] int32, out_offsets
     [n_pairs+1] int64 numpy): job p's results are dist[out_offsets[p]:out_offsets[p+1]]; idx is support-cloud-local, the LOWEST index among
     exactly equal minima; an empty support gives (+inf, -1).  dist is the correctly rounded sqrt of (dx*dx + dy*dy) + dz*dz (bit-identical
-    to cKDTree(s).query(q)[0]); squared=True returns that sum itself."""
+    to cKDTree(s).query(q)[0]); squared=True returns that sum itself.
+    search='grid' looks only at the cells of the support cloud's grid around each query (csrc/icp.hip) and gives the SAME outputs, bit for
+    bit, whatever `cell` is (one edge for all clouds or one per cloud; None: nn_grid_cell -- about 16 points per occupied cell of a surface,
+    never above the radius).  Only that route takes radius (a query without a support point within it gets (+inf, -1); None: no radius) and transforms
+    ([n_pairs, 12] float64 HIP tensor, row-major R | t: job p's queries are moved by it first, ((m0 x + m1 y) + m2 z) + m9 ..., no fma)."""
+    if search not in NN_SEARCHES:
+        raise ValueError(f'search must be one of {NN_SEARCHES}, got {search!r}')
+    if search == 'brute' and (radius is not None or transforms is not None or cell is not None):
+        raise ValueError("radius, transforms and cell belong to search='grid'")
+    if transforms is not None:
+        check_dtype(transforms, 'transforms', torch.float64)
     pts = device_tensor(points, 'points', torch.float64)
     if pts.dim() != 2 or pts.shape[1] != 3:
         raise ValueError(f'points must be [N,3], got {tuple(pts.shape)}')
@@ -233,6 +282,9 @@ def nearest_neighbor_batch(points, offsets, pairs, chunk=None, squared=False):
     dist = torch.empty((J.total_q,), device=dev, dtype=torch.float64)
     idx = torch.empty((J.total_q,), device=dev, dtype=torch.int32)
     if J.total_q == 0:
+        return dist, idx, J.out_off
+    if search == 'grid':
+        _nn_grid(pts, J, radius, transforms, cell, squared, dist, idx)
         return dist, idx, J.out_off
     chunk = resolve_chunk(chunk, NN_CHUNK, lambda: _nn_chunk(J.nq, J.ns))
     L = _lib.lib()

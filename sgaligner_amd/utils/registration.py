@@ -4,7 +4,8 @@ every mean is taken by numpy on the host from those arrays, so the figures equal
 metrics judge comes from the second half of the file: RANSAC rigid registration from point correspondences, batched over pairs
 (csrc/ransac.hip), with the shift and composition of src/engine/registration_evaluator.py:176-192 around it.  The last part is registration from per-point
 descriptors (utils/open3d.py:137-170): an exact nearest-neighbour search in feature space on the fp32 matrix cores (csrc/featnn.hip),
-the mutual filter and Open3D's edge-length checker as gathers and compares on the device, then the same RANSAC.  Nothing here falls back
+the mutual filter and Open3D's edge-length checker as gathers and compares on the device, then the same RANSAC; and ICP refinement with
+the geometric score of a transform (csrc/icp.hip: a nearest-neighbour search across clouds through a cell grid, batched over pairs).  Nothing here falls back
 to the host: without a HIP device the functions that need one raise."""
 from __future__ import annotations
 
@@ -14,7 +15,7 @@ import torch
 from .. import _lib
 from ..ops import _p, _stream
 from ..packed import PairJobs, check_finite, device_tensor, prefix_offsets, resolve_chunk, split_chunk, upload, workspace
-from .point_cloud import _cloud64, _need_device, _nn_numpy, apply_transform, get_nearest_neighbor
+from .point_cloud import _cloud64, _need_device, _nn_numpy, apply_transform, get_nearest_neighbor, nn_grid_cell
 
 
 def compute_modified_chamfer_distance(src_points, ref_points, raw_points, est_transform, gt_transform):
@@ -438,3 +439,164 @@ def registration_with_ransac_from_feats(src_points, ref_points, src_feats, ref_f
     brings within distance_threshold), not on a geometric nearest-neighbour search of all source points as Open3D's evaluation does."""
     return registration_with_ransac_from_feats_pairs([(src_points, ref_points, src_feats, ref_feats)], distance_threshold, ransac_n,
                                                      num_iterations, val_iterations, mutual, seed)[0]
+
+
+# ---- ICP refinement and the geometric score of a transform (csrc/icp.hip) ------------------------------------------------------------------
+ICP_METHODS = {'point': 0, 'plane': 1}
+ICP_STATUS_TEXT = {0: 'ok', 1: 'too few correspondences for an update', 2: 'the update could not be solved', 3: 'bad job'}
+
+
+def _model12(T):
+    """4x4 (or 3x4) transforms [..., 4, 4] -> the kernels' row-major [R | t] rows [..., 12]."""
+    T = np.asarray(T, dtype=np.float64)
+    return np.concatenate([T[..., :3, :3].reshape(T.shape[:-2] + (9,)), T[..., :3, 3]], axis=-1)
+
+
+def _matrix44(m):
+    """[n, 12] model rows -> [n, 4, 4]."""
+    m = np.asarray(m, dtype=np.float64).reshape(-1, 12)
+    T = np.tile(np.eye(4), (len(m), 1, 1))
+    T[:, :3, :3] = m[:, :9].reshape(-1, 3, 3)
+    T[:, :3, 3] = m[:, 9:]
+    return T
+
+
+def icp_batch(points, offsets, pairs, transforms, max_distance, method='point', normals=None, max_iters=30, relative_fitness=1e-6,
+              relative_rmse=1e-6, cell=None):
+    """The device-resident form of icp_pairs: points [sum N, 3] float64 HIP tensor (clouds packed back to back), offsets [n_clouds + 1] host
+    ints, pairs [n_pairs, 2] host ints (source cloud, reference cloud), transforms [n_pairs, 12] float64 HIP tensor (row-major R | t, the
+    initial estimates; not modified), normals [sum N, 3] float64 HIP tensor (read at the reference clouds' rows; method 'plane').  The grid
+    of every cloud is built once (cell: None = point_cloud.nn_grid_cell), the pivots are the reference clouds' box minima, then ONE sga_icp call: 3
+    (max_iters + 1) launches on torch's current stream and no synchronisation.  -> dict of HIP tensors: transform [n_pairs, 12], fitness,
+    inlier_rmse [n_pairs] float64, iterations, status [n_pairs] int32, trace [n_pairs, max_iters + 1, 2], idx [sum nq] int32, d2 [sum nq]
+    float64 (the correspondences of the FINAL transform, reference-cloud-local, -1 / +inf without one), and out_offsets (host)."""
+    from . import voxel
+    from .features import _Clouds
+    if method not in ICP_METHODS:
+        raise ValueError(f'method must be one of {tuple(ICP_METHODS)}, got {method!r}')
+    max_iters, max_distance = int(max_iters), float(max_distance)
+    if max_iters < 0:
+        raise ValueError(f'max_iters must be >= 0, got {max_iters}')
+    if not max_distance > 0.0:
+        raise ValueError(f'max_distance must be > 0 (inf: no limit), got {max_distance}')
+    if method == 'plane' and normals is None:
+        raise ValueError("method 'plane' needs the reference clouds' normals")
+    pts = device_tensor(points, 'points', torch.float64)
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f'points must be [N, 3], got {tuple(pts.shape)}')
+    J = PairJobs(offsets, pts.shape[0], pairs, 'icp_batch', 'cloud')
+    T = device_tensor(transforms, 'transforms', torch.float64).reshape(-1, 12).clone()
+    if T.shape[0] != J.n_pairs:
+        raise ValueError(f'transforms must be [{J.n_pairs}, 12], got {tuple(transforms.shape)}')
+    nr = None
+    if normals is not None:
+        nr = device_tensor(normals, 'normals', torch.float64)
+        if tuple(nr.shape) != tuple(pts.shape):
+            raise ValueError(f'normals must be {tuple(pts.shape)}, got {tuple(nr.shape)}')
+    check_finite(pts, 'points', 'coordinates')
+    dev, n = pts.device, J.n_pairs
+    out = {'transform': T, 'fitness': torch.zeros((n,), device=dev, dtype=torch.float64),
+           'inlier_rmse': torch.zeros((n,), device=dev, dtype=torch.float64), 'iterations': torch.zeros((n,), device=dev, dtype=torch.int32),
+           'status': torch.zeros((n,), device=dev, dtype=torch.int32),
+           'trace': torch.full((n, max_iters + 1, 2), float('nan'), device=dev, dtype=torch.float64),
+           'idx': torch.full((J.total_q,), -1, device=dev, dtype=torch.int32),
+           'd2': torch.full((J.total_q,), float('inf'), device=dev, dtype=torch.float64), 'out_offsets': J.out_off}
+    if n == 0:
+        return out
+    L = _lib.lib()
+    C = _Clouds(pts, J.off)
+    G = voxel.build_grid(C, None, nn_grid_cell(C, max_distance) if cell is None else cell)
+    _, d_pr, d_oo = upload(J.host_parts(), dev)
+    box = torch.empty((J.n_sets, 6), device=dev, dtype=torch.float64)
+    _lib.check(L.sga_cloud_bounds(_p(pts), *C.args(), _p(box), 1.0, None, _stream()), 'sga_cloud_bounds')
+    pivot = box[d_pr.view(-1, 2)[:, 1].long(), :3]
+    pivot = torch.where(torch.isfinite(pivot), pivot, torch.zeros_like(pivot)).contiguous()       # a reference cloud without a kept point
+    ws_bytes = int(L.sga_icp_workspace_bytes(n, J.max_q))
+    ws = workspace(ws_bytes, dev)
+    rc = L.sga_icp(_p(pts), _p(C.d_off), J.n_sets, int(pts.shape[0]), _p(d_pr), n, _p(d_oo), J.total_q, J.max_q, J.h_off.ctypes.data,
+                   J.h_pr.ctypes.data, _p(G.cell), _p(G.origin), _p(G.dims), _p(G.status), _p(G.order), _p(G.sorted_keys),
+                   max_distance * max_distance, ICP_METHODS[method], _p(nr), _p(pivot), max_iters, float(relative_fitness), float(relative_rmse),
+                   _p(T), _p(out['fitness']), _p(out['inlier_rmse']), _p(out['iterations']), _p(out['status']), _p(out['trace']), _p(out['idx']),
+                   _p(out['d2']), _p(ws), ws_bytes, _stream())
+    _lib.check(rc, 'sga_icp')
+    return out
+
+
+def icp_pairs(list_of_pairs, init_transforms=None, max_distance=0.05, method='point', ref_normals=None, max_iters=30, relative_fitness=1e-6,
+              relative_rmse=1e-6, cell=None):
+    """ICP refinement of many (source, reference) cloud pairs at once -- Open3D's registration_icp loop, point-to-point or point-to-plane:
+    list_of_pairs = [(src_points [n, 3], ref_points [m, 3]), ...] numpy; init_transforms: one 4x4 per pair (None: identity); ref_normals:
+    one [m, 3] array per pair for method 'plane' (None: estimated on the device from the reference clouds' 30 nearest neighbours through the
+    grid, features.estimate_normals_batch(search='grid')).  One upload, one launch set, one download.  -> per pair a dict: transformation
+    [4, 4] with apply_transform(src, T) ~ ref, fitness (share of source points with a reference point within max_distance), inlier_rmse,
+    correspondence_set [k, 2] int64 (source index, reference index) of the final transform, iterations, status (0 ok; 1 too few
+    correspondences and 2 an unsolvable update: the transform is the last good one), trace [evaluations, 2] (fitness, rmse of each)."""
+    _need_device('icp_pairs')
+    if method not in ICP_METHODS:
+        raise ValueError(f'method must be one of {tuple(ICP_METHODS)}, got {method!r}')
+    if int(max_iters) < 0:
+        raise ValueError(f'max_iters must be >= 0, got {max_iters}')
+    prs = [(_cloud64(s, f'list_of_pairs[{i}][0]'), _cloud64(r, f'list_of_pairs[{i}][1]')) for i, (s, r) in enumerate(list_of_pairs)]
+    n = len(prs)
+    if n == 0:
+        return []
+    init = np.tile(np.eye(4), (n, 1, 1)) if init_transforms is None else np.asarray(init_transforms, dtype=np.float64).reshape(-1, 4, 4)
+    if len(init) != n:
+        raise ValueError(f'init_transforms must hold one 4x4 per pair ({n}), got {len(init)}')
+    clouds = [c for p in prs for c in p]
+    off = np.concatenate([[0], np.cumsum([len(c) for c in clouds])]).astype(np.int64)
+    parts = [np.concatenate(clouds), _model12(init)]
+    if method == 'plane' and ref_normals is not None:
+        if len(ref_normals) != n:
+            raise ValueError(f'ref_normals must hold one array per pair ({n}), got {len(ref_normals)}')
+        nrm = []
+        for i, (s, r) in enumerate(prs):
+            nr = _cloud64(ref_normals[i], f'ref_normals[{i}]')
+            if nr.shape != r.shape:
+                raise ValueError(f'ref_normals[{i}] must be {r.shape}, got {nr.shape}')
+            nrm += [np.zeros_like(s), nr]
+        parts.append(np.concatenate(nrm))
+    dev = torch.device('cuda', torch.cuda.current_device())
+    d_parts = upload(parts, dev)                                                                   # one upload
+    pts, T0 = d_parts[0].view(-1, 3), d_parts[1].view(-1, 12)
+    normals = None
+    if method == 'plane':
+        if ref_normals is not None:
+            normals = d_parts[2].view(-1, 3)
+        else:
+            from .features import estimate_normals_batch
+            normals = estimate_normals_batch(pts, off, None, 30, search='grid')[0]
+    res = icp_batch(pts, off, [(2 * p, 2 * p + 1) for p in range(n)], T0, max_distance, method, normals, max_iters, relative_fitness,
+                    relative_rmse, cell)
+    keys = ('transform', 'fitness', 'inlier_rmse', 'iterations', 'status', 'trace', 'idx', 'd2')
+    flat = torch.cat([res[k].reshape(-1).double() for k in keys]).cpu().numpy()                    # one download (int32 is exact in fp64)
+    host, at = {}, 0
+    for k in keys:
+        host[k] = flat[at:at + res[k].numel()].reshape(tuple(res[k].shape))
+        at += res[k].numel()
+    oo, T = res['out_offsets'], _matrix44(host['transform'])
+    out = []
+    for p in range(n):
+        idx = host['idx'][oo[p]:oo[p + 1]].astype(np.int64)
+        src = np.flatnonzero(idx >= 0)
+        evals = int(host['iterations'][p]) + 1
+        out.append({'transformation': T[p], 'fitness': float(host['fitness'][p]), 'inlier_rmse': float(host['inlier_rmse'][p]),
+                    'correspondence_set': np.stack([src, idx[src]], axis=1), 'iterations': int(host['iterations'][p]),
+                    'status': int(host['status'][p]), 'trace': host['trace'][p][:evals].copy()})
+    return out
+
+
+def icp(src_points, ref_points, init=None, max_distance=0.05, method='point', ref_normals=None, max_iters=30, relative_fitness=1e-6,
+        relative_rmse=1e-6, cell=None):
+    """icp_pairs for one pair: -> the dict of that pair."""
+    _need_device('icp')
+    return icp_pairs([(src_points, ref_points)], None if init is None else [init], max_distance, method,
+                     None if ref_normals is None else [ref_normals], max_iters, relative_fitness, relative_rmse, cell)[0]
+
+
+def evaluate_registration_pairs(list_of_pairs, transforms, max_distance):
+    """Open3D's evaluate_registration for many pairs: the geometric score of given transforms -- fitness, inlier_rmse and the
+    correspondence set at max_distance, by a nearest-neighbour search of every moved source point in its reference cloud's grid.  It is
+    icp_pairs with max_iters = 0: same dicts, the transformation returned as given."""
+    _need_device('evaluate_registration_pairs')
+    return icp_pairs(list_of_pairs, transforms, max_distance, max_iters=0)
