@@ -748,6 +748,47 @@ int sga_ransac_rigid(const double* corr, const int32_t* offsets, int n_jobs, int
                      int32_t* best_hyp, int32_t* status, unsigned char* inlier_mask, int32_t* hyp_count, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ---- feature-matching RANSAC scored geometrically: hypothesis models and the score of many transforms (fp64; csrc/ransac_geo.hip) ----
+ * Open3D's registration_ransac_based_on_feature_matching judges a validated hypothesis by evaluate_registration: a nearest-neighbour
+ * search of ALL moved source points in the reference cloud.  These two entries are its device half; the selection between them is
+ * utils/registration.py's ransac_geometric_batch.  tests/ransac_geo_ref.py restates the text below in numpy.
+ *
+ * sga_ransac_models: corr / offsets / samples / hyp_offsets / total_rows / total_hyp / max_hyp / offsets_host / hyp_offsets_host as in
+ * sga_ransac_rigid.  Out, per hypothesis h (packed by hyp_offsets): models [total_hyp, 12] f64, row-major [R | t], m[0..8] = R,
+ * m[9..11] = t -- sga_ransac_rigid's three-point model: the least-squares proper rotation + translation of the three sampled pairs about
+ * the first of them, Horn's quaternion by at most 10 cyclic Jacobi sweeps, the same validity rules; valid [total_hyp] int32; resid2
+ * [total_hyp] f64 = the largest of the three sampled rows' |R s + t - r|^2, taken in sga_nn_search_grid's arithmetic:
+ * x' = ((m0*x + m1*y) + m2*z) + m9 (y', z' with rows 1, 2), dx = x' - r.x ..., d2 = (dx*dx + dy*dy) + dz*dz, every operation rounded on its
+ * own (no FMA), so that a host recomputes resid2 bit for bit from the downloaded model and rows.  Invalid -- a repeated or out-of-range
+ * index, a non-finite model, a NaN residual --: valid = 0, resid2 = +inf, all twelve model entries NaN.  One lane per hypothesis; no
+ * atomics, no workspace, stream-ordered: the outputs are a pure function of the inputs.  The kernel re-checks every offset and index it
+ * reads; a job whose offsets are out of range on the device writes nothing.  With n_jobs, total_hyp or max_hyp 0 nothing is launched.
+ *
+ * sga_score_transforms_grid: pts / offsets / n_clouds / total_points / pairs / n_pairs / max_queries / offsets_host / pairs_host and
+ * cell / origin / dims / status / order / sorted_keys as in sga_nn_search_grid (a job is a (query cloud, support cloud) pair; there is
+ * no out_offsets: nothing is written per query).  transforms [n_pairs, 12] f64 DEVICE, required: job p's [R | t].  live [n_pairs] int32
+ * DEVICE, nullable: a job with live[p] == 0 is not searched.  r2 >= 0, +inf: no radius.
+ * Out: count [n_pairs] int32 = the number of queries of job p for which sga_nn_search_grid (same arrays, same transform, same r2) returns
+ * an index >= 0; sum_d2 [n_pairs] f64 = the sum of their d2, in this fixed order: a slice is 1024 query rows counted from the job's first
+ * row; wave w = 0..3 of a slice's workgroup adds the d2 of rows w, w + 4, w + 8, ... of the slice in ascending order, starting from +0.0;
+ * the four wave sums are added in order, starting from wave 0's; the slice sums are added in ascending order, starting from +0.0.  Every
+ * addition is one fp64 rounding.  A job with live == 0, or whose ids or offsets are out of range on the device, gets count 0 and sum_d2 0.
+ * The search -- moved query, clamp, blocks R = 1, 2, 4, 8, 16, stop rule, whole walk -- is sga_nn_search_grid's, unchanged, one wave per
+ * query; the grid decides how much of the support is looked at, never what comes out.  No atomics: count and sum_d2 have the same bits
+ * in two calls, for a job alone or in a batch, and for every cell size.  Two launches (search + fold of a slice; fold of the slices),
+ * stream-ordered, no synchronisation.  workspace: sga_score_transforms_workspace_bytes(n_pairs, max_queries) = 16 bytes per (job, slice
+ * of the longest query cloud); it need not be zeroed.  A job list with ceil(max_queries / 1024) x n_pairs >= 2^24 workgroups (2^32 threads
+ * in one launch; far below the point where the count would overflow an int) is refused with a message before anything is launched. */
+int sga_ransac_models(const double* corr, const int32_t* offsets, int n_jobs, int total_rows, const int32_t* samples,
+                      const int32_t* hyp_offsets, int total_hyp, int max_hyp, const int32_t* offsets_host, const int32_t* hyp_offsets_host,
+                      double* models, int32_t* valid, double* resid2, void* stream);
+size_t sga_score_transforms_workspace_bytes(int n_pairs, int max_queries);
+int sga_score_transforms_grid(const double* pts, const int32_t* offsets, int n_clouds, int total_points, const int32_t* pairs, int n_pairs,
+                              int max_queries, const int32_t* offsets_host, const int32_t* pairs_host, const double* cell,
+                              const double* origin, const int32_t* dims, const int32_t* status, const int32_t* order,
+                              const int64_t* sorted_keys, const double* transforms, const int32_t* live, double r2, int32_t* count,
+                              double* sum_d2, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- batched subscan generation: frame visibility, frustum walk, per-object counts (fp64 tests, integer walk) ----------------------
  * replaces the per-frame loop of preprocessing/scan3r/subgenscan3r.py:188-234: utils/point_cloud.py:112-134 get_visible_pts_from_cam_pose
  * for every frame, the running OR of the masks with a subscan closed whenever the union reaches the point budget, and the per-object

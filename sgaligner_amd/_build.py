@@ -44,6 +44,8 @@ FILE_FLAGS = {'contrastive.hip': ['-fno-slp-vectorize'],
               'voxel.hip': ['-ffp-contract=off'],
               # icp.hip: moved queries and distances bit-identical to their NumPy restatement and to nnsearch.hip's (no FMA)
               'icp.hip': ['-ffp-contract=off'],
+              # ransac_geo.hip: the search's arithmetic, and a residual that NumPy recomputes bit for bit from the stored model (no FMA)
+              'ransac_geo.hip': ['-ffp-contract=off'],
               # visibility.hip: same -- the frustum tests are bit-identical to the NumPy restatement of the reference's projection
               'visibility.hip': ['-ffp-contract=off']}
 

@@ -90,6 +90,9 @@ SIGNATURES = {
                     c_size_t, P]),
     'sga_ransac_workspace_bytes': (c_size_t, [I, I, I, I]),
     'sga_ransac_rigid': (I, [P, P, I, I, P, P, I, I, I, I, P, P, c_double, I, P, P, P, P, P, P, P, c_size_t, P]),
+    'sga_ransac_models': (I, [P, P, I, I, P, P, I, I, P, P, P, P, P, P]),
+    'sga_score_transforms_workspace_bytes': (c_size_t, [I, I]),
+    'sga_score_transforms_grid': (I, [P, P, I, I, P, I, I, P, P, P, P, P, P, P, P, P, P, c_double, P, P, P, c_size_t, P]),
     'sga_subscan_lds_slots': (I, []),
     'sga_frame_visibility': (I, [P, P, P, P, P, P, I, I, I, c_int64, I, I, P, P, P, P, P]),
     'sga_subscan_walk': (I, [P, P, P, P, P, P, I, I, I, c_int64, P, P, P, P, P, P, P, P]),

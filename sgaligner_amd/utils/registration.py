@@ -5,7 +5,8 @@ metrics judge comes from the second half of the file: RANSAC rigid registration 
 (csrc/ransac.hip), with the shift and composition of src/engine/registration_evaluator.py:176-192 around it.  The last part is registration from per-point
 descriptors (utils/open3d.py:137-170): an exact nearest-neighbour search in feature space on the fp32 matrix cores (csrc/featnn.hip),
 the mutual filter and Open3D's edge-length checker as gathers and compares on the device, then the same RANSAC; and ICP refinement with
-the geometric score of a transform (csrc/icp.hip: a nearest-neighbour search across clouds through a cell grid, batched over pairs).  Nothing here falls back
+the geometric score of a transform (csrc/icp.hip: a nearest-neighbour search across clouds through a cell grid, batched over pairs);
+and that score as RANSAC's own criterion, fused over thousands of hypotheses (csrc/ransac_geo.hip).  Nothing here falls back
 to the host: without a HIP device the functions that need one raise."""
 from __future__ import annotations
 
@@ -393,11 +394,14 @@ def edge_length_filter(corr, offsets, samples, hyp_offsets, similarity=0.9):
 
 
 def registration_with_ransac_from_feats_pairs(list_of_clouds, distance_threshold=0.05, ransac_n=3, num_iterations=50000, val_iterations=1000,
-                                              mutual=False, seed=0):
+                                              mutual=False, seed=0, score='correspondence', return_info=False):
     """registration_with_ransac_from_feats for many pairs: list_of_clouds = [(src_points, ref_points, src_feats, ref_feats), ...].  One
-    matching launch set and one RANSAC launch set for all of them.  -> [4x4 transform, ...] in the order given."""
+    matching launch set and one RANSAC launch set for all of them.  -> [4x4 transform, ...] in the order given; with return_info
+    [(transform, info), ...]."""
     if ransac_n != 3:
         raise ValueError(f'registration_with_ransac_from_feats: only ransac_n == 3 is implemented (got {ransac_n})')
+    if score not in RANSAC_SCORES:
+        raise ValueError(f'score must be one of {RANSAC_SCORES}, got {score!r}')
     _need_device('registration_with_ransac_from_feats')
     clouds = [(_cloud64(s, f'list_of_clouds[{i}][0]'), _cloud64(r, f'list_of_clouds[{i}][1]'), sf, rf)
               for i, (s, r, sf, rf) in enumerate(list_of_clouds)]
@@ -418,27 +422,49 @@ def registration_with_ransac_from_feats_pairs(list_of_clouds, distance_threshold
     samples, hoff = draw_samples(sizes, num_iterations, seed)
     corr = torch.cat(rows)
     checked = edge_length_filter(corr, off, torch.from_numpy(samples).to(dev), hoff)
-    res = find_rigid_transform_batch(corr, off, checked, hoff, distance_threshold)
+    if score == 'geometric':
+        # cloud 2p is pair p's source (the queries), cloud 2p + 1 its reference (the support): `pts` is packed that way
+        c_off = np.concatenate([[0], np.cumsum([len(c) for s, r, _, _ in clouds for c in (s, r)])]).astype(np.int64)
+        res = ransac_geometric_batch(pts, c_off, [(2 * p, 2 * p + 1) for p in range(len(clouds))], corr, off, checked, hoff, distance_threshold,
+                                     val_iterations)
+        keys = ('fitness', 'inlier_rmse', 'best_hyp', 'n_validated')
+    else:
+        res = find_rigid_transform_batch(corr, off, checked, hoff, distance_threshold)
+        keys = ('inlier_count', 'best_hyp')
     status, transform = res['status'].cpu().numpy(), res['transform'].cpu().numpy()
-    return [np.eye(4) if status[j] != 0 else transform[j] for j in range(len(clouds))]
+    out = [np.eye(4) if status[j] != 0 else transform[j] for j in range(len(clouds))]
+    if not return_info:
+        return out
+    host = {k: res[k].cpu().numpy() for k in keys}
+    return [(T, {'status': int(status[j]), **{k: host[k][j].item() for k in keys}}) for j, T in enumerate(out)]
 
 
 def registration_with_ransac_from_feats(src_points, ref_points, src_feats, ref_feats, distance_threshold=0.05, ransac_n=3,
-                                        num_iterations=50000, val_iterations=1000, mutual=False, seed=0):
+                                        num_iterations=50000, val_iterations=1000, mutual=False, seed=0, score='correspondence',
+                                        return_info=False):
     """utils/open3d.py:137-170 (Open3D's registration_ransac_based_on_feature_matching) on the device: the reference signature plus
-    `mutual` and `seed`.  src_points / ref_points [N, 3], src_feats / ref_feats [N, C] (numpy, or float32 HIP tensors for the features).
-    -> 4x4 transform with apply_transform(src, T) ~ ref, identity when no model is found.
+    `mutual`, `seed`, `score` and `return_info`.  src_points / ref_points [N, 3], src_feats / ref_feats [N, C] (numpy, or float32 HIP
+    tensors for the features).  -> 4x4 transform with apply_transform(src, T) ~ ref, identity when no model is found; with return_info
+    (transform, info).
       1. correspondences from match_features_pairs: every source row with its nearest reference row in feature space (mutual=False, as
          the reference's call), or the mutual nearest neighbours only;
       2. `num_iterations` sample triples of correspondences from draw_samples (numpy.random.default_rng(seed));
       3. Open3D's edge-length checker (0.9) on the triples (edge_length_filter), before scoring;
-      4. find_rigid_transform_batch with threshold = distance_threshold.
-    ransac_n != 3 raises.  val_iterations is accepted and unused: the iteration count is fixed, as in
-    registration_with_ransac_from_correspondences.  Open3D's distance checker is an early reject before its costly evaluation; it is not
-    reproduced because every hypothesis is scored in full here.  A model is scored on the feature correspondences (the rows its transform
-    brings within distance_threshold), not on a geometric nearest-neighbour search of all source points as Open3D's evaluation does."""
+      4. score='correspondence' (the default): find_rigid_transform_batch with threshold = distance_threshold;
+         score='geometric': ransac_geometric_batch with max_validation = val_iterations.
+    ransac_n != 3 and an unknown score raise ValueError.
+    Against Open3D.  score='geometric' is Open3D's rule: a hypothesis must also pass the distance checker (its three sampled pairs within
+    distance_threshold under its own model); the first val_iterations hypotheses that pass both checkers, in the order drawn, are each
+    scored by a nearest-neighbour search of ALL source points against the reference cloud (evaluate_registration at distance_threshold);
+    the best fitness wins, then the smaller inlier RMSE, then the earlier hypothesis; and the three-point model is returned as it is,
+    without a refit.  What remains different: the iteration count is fixed -- all num_iterations triples are drawn and checked, Open3D's
+    confidence-based early stop is not reproduced -- and the random numbers are numpy's, so single results differ from Open3D's run by run.
+    score='correspondence' departs further, as it always has: a model is scored on the feature correspondences (the rows its transform
+    brings within distance_threshold), every hypothesis is scored in full so the distance checker is not needed and not applied,
+    val_iterations is unused, and the winner is refitted on its inliers (find_rigid_transform_batch).
+    info (return_info=True): status, best_hyp, and fitness / inlier_rmse / n_validated ('geometric') or inlier_count ('correspondence')."""
     return registration_with_ransac_from_feats_pairs([(src_points, ref_points, src_feats, ref_feats)], distance_threshold, ransac_n,
-                                                     num_iterations, val_iterations, mutual, seed)[0]
+                                                     num_iterations, val_iterations, mutual, seed, score, return_info)[0]
 
 
 # ---- ICP refinement and the geometric score of a transform (csrc/icp.hip) ------------------------------------------------------------------
@@ -600,3 +626,188 @@ def evaluate_registration_pairs(list_of_pairs, transforms, max_distance):
     icp_pairs with max_iters = 0: same dicts, the transformation returned as given."""
     _need_device('evaluate_registration_pairs')
     return icp_pairs(list_of_pairs, transforms, max_distance, max_iters=0)
+
+
+# ---- feature-matching RANSAC scored geometrically (csrc/ransac_geo.hip) ---------------------------------------------------------------------
+RANSAC_SCORES = ('correspondence', 'geometric')
+
+
+def hypothesis_models_batch(corr, offsets, samples, hyp_offsets):
+    """The three-point models of a packed hypothesis list as an output of their own (arguments as find_rigid_transform_batch takes them;
+    sga_ransac_models).  -> dict of HIP tensors: models [sum H, 12] float64 (row-major R | t; NaN where invalid), valid [sum H] int32,
+    resid2 [sum H] float64 -- the largest |R s + t - r|^2 of the three sampled rows in the grid search's arithmetic (no fma), +inf where
+    invalid: what Open3D's distance checker compares with the threshold."""
+    cr = device_tensor(corr, 'corr', torch.float64)
+    if cr.dim() != 2 or cr.shape[1] != 6:
+        raise ValueError(f'corr must be [N,6], got {tuple(cr.shape)}')
+    dev = cr.device
+    sm = device_tensor(samples, 'samples', torch.int32).reshape(-1, 3)
+    off = prefix_offsets(offsets, 'offsets', int(cr.shape[0]))
+    hoff = prefix_offsets(hyp_offsets, 'hyp_offsets', int(sm.shape[0]))
+    n_jobs = len(off) - 1
+    if len(hoff) != n_jobs + 1:
+        raise ValueError(f'offsets names {n_jobs} jobs, hyp_offsets {len(hoff) - 1}')
+    if cr.shape[0] >= 2 ** 31 // 6 or sm.shape[0] >= 2 ** 31 // 12:
+        raise ValueError('hypothesis_models_batch indexes with int32: fewer than 2^31 / 6 rows and 2^31 / 12 hypotheses per call')
+    check_finite(cr, 'corr', 'coordinates')
+    total, total_h = int(cr.shape[0]), int(sm.shape[0])
+    out = {'models': torch.full((total_h, 12), float('nan'), device=dev, dtype=torch.float64),
+           'valid': torch.zeros((total_h,), device=dev, dtype=torch.int32),
+           'resid2': torch.full((total_h,), float('inf'), device=dev, dtype=torch.float64)}
+    if n_jobs == 0 or total_h == 0:
+        return out
+    h_off, h_hoff = off.astype(np.int32), hoff.astype(np.int32)
+    d_off, d_hoff = upload([h_off, h_hoff], dev)                              # one small upload
+    rc = _lib.lib().sga_ransac_models(_p(cr) if total else None, _p(d_off), n_jobs, total, _p(sm), _p(d_hoff), total_h, int(np.diff(hoff).max()),
+                                      h_off.ctypes.data, h_hoff.ctypes.data, _p(out['models']), _p(out['valid']), _p(out['resid2']), _stream())
+    _lib.check(rc, 'sga_ransac_models')
+    return out
+
+
+def score_transforms_batch(points, offsets, pairs, transforms, max_distance, live=None, cell=None, _checked=False):
+    """Open3D's evaluate_registration for MANY transforms per cloud pair, without the per-query results (sga_score_transforms_grid): points
+    [sum N, 3] float64 HIP tensor (clouds packed back to back), offsets [n_clouds + 1] host ints, pairs [n_jobs, 2] host ints (source cloud,
+    reference cloud; any number of jobs may share both), transforms [n_jobs, 12] float64 HIP tensor (row-major R | t), live [n_jobs] int32
+    HIP tensor or None (0: the job is skipped and scores 0).  The grid of every cloud is built once (cell: None = point_cloud.nn_grid_cell;
+    a speed choice only).  -> (count [n_jobs] int32, sum_d2 [n_jobs] float64) HIP tensors: the number of moved source points with a
+    reference point within max_distance (inf: no limit) and the sum of their squared distances to the nearest, in a fixed order -- the same
+    bits in two calls, for a job alone or in a batch, and for every cell.  No synchronisation."""
+    from . import voxel
+    from .features import _Clouds
+    max_distance = float(max_distance)
+    if not max_distance > 0.0:
+        raise ValueError(f'max_distance must be > 0 (inf: no limit), got {max_distance}')
+    pts = device_tensor(points, 'points', torch.float64)
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f'points must be [N, 3], got {tuple(pts.shape)}')
+    dev = pts.device
+    off = prefix_offsets(offsets, 'offsets', int(pts.shape[0]))
+    n_sets = len(off) - 1
+    pr = np.ascontiguousarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
+    if pr.size and (pr.min() < 0 or pr.max() >= n_sets):
+        raise ValueError(f'pairs must name clouds in [0, {n_sets})')
+    n = len(pr)
+    T = device_tensor(transforms, 'transforms', torch.float64)
+    if tuple(T.shape) != (n, 12):
+        raise ValueError(f'transforms must be [{n}, 12] (row-major R | t per job), got {tuple(T.shape)}')
+    lv = None
+    if live is not None:
+        lv = device_tensor(live, 'live', torch.int32)
+        if tuple(lv.shape) != (n,):
+            raise ValueError(f'live must be [{n}], got {tuple(lv.shape)}')
+    if not _checked:                                                                       # ransac_geometric_batch has looked already
+        check_finite(pts, 'points', 'coordinates')
+    count = torch.zeros((n,), device=dev, dtype=torch.int32)
+    sum_d2 = torch.zeros((n,), device=dev, dtype=torch.float64)
+    if n == 0:
+        return count, sum_d2
+    max_q = int(np.diff(off)[pr[:, 0]].max())
+    if -(-max_q // 1024) * n >= 2 ** 24:
+        raise ValueError(f'score_transforms_batch: {n} jobs of up to {max_q} queries exceed the grid limit; split the job list')
+    L = _lib.lib()
+    C = _Clouds(pts, off)
+    G = voxel.build_grid(C, None, nn_grid_cell(C, max_distance) if cell is None else cell)
+    h_off, h_pr = off.astype(np.int32), pr.astype(np.int32)
+    d_pr, = upload([h_pr], dev)
+    ws_bytes = int(L.sga_score_transforms_workspace_bytes(n, max_q))
+    ws = workspace(ws_bytes, dev)
+    rc = L.sga_score_transforms_grid(_p(pts), _p(C.d_off), n_sets, int(pts.shape[0]), _p(d_pr), n, max_q, h_off.ctypes.data, h_pr.ctypes.data,
+                                     _p(G.cell), _p(G.origin), _p(G.dims), _p(G.status), _p(G.order), _p(G.sorted_keys), _p(T),
+                                     _p(lv) if lv is not None else None, max_distance * max_distance, _p(count), _p(sum_d2), _p(ws), ws_bytes,
+                                     _stream())
+    _lib.check(rc, 'sga_score_transforms_grid')
+    return count, sum_d2
+
+
+def ransac_geometric_batch(points, offsets, pairs, corr, corr_offsets, samples, hyp_offsets, distance_threshold, max_validation, cell=None):
+    """Open3D's registration_ransac_based_on_feature_matching from given sample triples, for many cloud pairs at once and device-resident
+    (no host synchronisation between the stages).  points / offsets / pairs: the clouds and one (source cloud, reference cloud) job per
+    pair, as score_transforms_batch takes them; corr [sum n, 6] / corr_offsets / samples [sum H, 3] / hyp_offsets: job j's correspondences
+    and sample triples, as find_rigid_transform_batch takes them (the caller has applied edge_length_filter).  Per job:
+      1. the three-point model of every hypothesis (hypothesis_models_batch);
+      2. Open3D's distance checker: valid and resid2 <= distance_threshold^2;
+      3. the validated set: the first `max_validation` passing hypotheses in ascending index (Open3D's max_validation);
+      4. every validated model scored on ALL source points against the reference cloud at distance_threshold (score_transforms_batch;
+         the evaluation is sized by min(H_j, max_validation) slots per job, unused ones are not searched);
+      5. selected: the largest count; among equal counts the smallest sum_d2; then the lowest index;
+      6. the transform is that hypothesis' model, bit for bit -- no refit, as in Open3D (icp_pairs refines).
+    -> dict of HIP tensors: transform [n_jobs, 4, 4] float64, fitness (count / source points), inlier_rmse (sqrt(sum_d2 / count), 0 without
+    a pair) [n_jobs] float64, best_hyp (job-local), n_validated, status [n_jobs] int32 (1: no validated hypothesis or a best count below
+    3 -- identity, fitness 0, rmse 0, best_hyp -1), hyp_count [sum H] int32 (-1 where the hypothesis was not validated), hyp_sum_d2 [sum H]
+    float64 (+inf there), and models / valid / resid2 of step 1."""
+    distance_threshold, max_validation = float(distance_threshold), int(max_validation)
+    if not (np.isfinite(distance_threshold) and distance_threshold > 0):
+        raise ValueError(f'distance_threshold must be finite and > 0, got {distance_threshold}')
+    if max_validation < 1:
+        raise ValueError(f'max_validation must be >= 1, got {max_validation}')
+    pts = device_tensor(points, 'points', torch.float64)
+    dev = pts.device
+    check_finite(pts, 'points', 'coordinates')                                             # the only download, before the first stage
+    M = hypothesis_models_batch(corr, corr_offsets, samples, hyp_offsets)
+    hoff = prefix_offsets(hyp_offsets, 'hyp_offsets', int(M['valid'].shape[0]))
+    off = prefix_offsets(offsets, 'offsets', int(pts.shape[0]))
+    pr = np.ascontiguousarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
+    n_jobs, total_h = len(hoff) - 1, int(hoff[-1])
+    if len(pr) != n_jobs:
+        raise ValueError(f'pairs names {len(pr)} jobs, hyp_offsets {n_jobs}')
+    if pr.size and (pr.min() < 0 or pr.max() >= len(off) - 1):
+        raise ValueError(f'pairs must name clouds in [0, {len(off) - 1})')
+    H = np.diff(hoff)
+    K = np.minimum(H, max_validation)                                                      # evaluation slots per job: a host-side bound
+    slot_off = np.concatenate([[0], np.cumsum(K)]).astype(np.int64)
+    S, k_max = int(slot_off[-1]), int(K.max()) if n_jobs else 0
+    nq = np.diff(off)[pr[:, 0]].astype(np.float64) if n_jobs else np.zeros(0)
+    eye = torch.eye(4, device=dev, dtype=torch.float64)
+    out = {'transform': eye.repeat(n_jobs, 1, 1), 'fitness': torch.zeros((n_jobs,), device=dev, dtype=torch.float64),
+           'inlier_rmse': torch.zeros((n_jobs,), device=dev, dtype=torch.float64),
+           'best_hyp': torch.full((n_jobs,), -1, device=dev, dtype=torch.int32), 'n_validated': torch.zeros((n_jobs,), device=dev, dtype=torch.int32),
+           'status': torch.ones((n_jobs,), device=dev, dtype=torch.int32),
+           'hyp_count': torch.full((total_h,), -1, device=dev, dtype=torch.int32),
+           'hyp_sum_d2': torch.full((total_h,), float('inf'), device=dev, dtype=torch.float64), **M}
+    if S == 0:
+        return out
+    # host-known index arrays, one upload: the job and base of every hypothesis, the job of every slot, the slot of every (job, k)
+    job_of_h = np.repeat(np.arange(n_jobs, dtype=np.int64), H)
+    pad = slot_off[:-1, None] + np.arange(k_max, dtype=np.int64)[None, :]
+    pad = np.where(np.arange(k_max)[None, :] < K[:, None], pad, S)                         # S: the dummy slot
+    d_job, d_hbase, d_sbase, d_pad, d_nq, d_hoff = upload([job_of_h, hoff[:-1][job_of_h], slot_off[:-1][job_of_h], pad, nq, hoff[:-1].copy()], dev)
+    d_pad = d_pad.view(n_jobs, k_max)
+    # 2. + 3.: the distance checker, the rank of a passing hypothesis within its job, the first max_validation of them
+    passing = (M['valid'] != 0) & (M['resid2'] <= distance_threshold * distance_threshold)
+    incl = torch.cumsum(passing.to(torch.int64), 0)
+    before = torch.cat([incl.new_zeros(1), incl])[d_hbase]                                 # passing hypotheses before the job's first
+    rank = incl - passing.to(torch.int64) - before
+    validated = passing & (rank < max_validation)
+    slot = torch.where(validated, d_sbase + rank, torch.full_like(rank, S))                # a validated hypothesis' slot, else the dummy
+    hyp_of_slot = torch.zeros((S + 1,), device=dev, dtype=torch.int64).scatter_(0, slot, torch.arange(total_h, device=dev, dtype=torch.int64))
+    live = torch.zeros((S + 1,), device=dev, dtype=torch.int32).scatter_(0, slot, torch.ones((total_h,), device=dev, dtype=torch.int32))
+    live[S] = 0
+    hyp_of_slot, live = hyp_of_slot[:S], live[:S].contiguous()
+    # 4.: one job per slot
+    count, sum_d2 = score_transforms_batch(pts, off, np.repeat(pr, K, axis=0), M['models'][hyp_of_slot].contiguous(), distance_threshold, live, cell,
+                                           _checked=True)
+    cnt_x = torch.cat([torch.where(live != 0, count, torch.full_like(count, -1)), count.new_full((1,), -1)])
+    sd2_x = torch.cat([torch.where(live != 0, sum_d2, torch.full_like(sum_d2, float('inf'))), sum_d2.new_full((1,), float('inf'))])
+    out['hyp_count'], out['hyp_sum_d2'] = cnt_x[slot], sd2_x[slot]
+    # 5.: lexicographic over the job's slots, which are in ascending hypothesis index
+    c_pad, s_pad = cnt_x[d_pad], sd2_x[d_pad]
+    c_best = c_pad.max(dim=1).values
+    cand = c_pad == c_best[:, None]
+    s_best = torch.where(cand, s_pad, torch.full_like(s_pad, float('inf'))).min(dim=1).values
+    cand &= s_pad == s_best[:, None]
+    k_best = torch.where(cand, torch.arange(k_max, device=dev)[None, :], k_max).min(dim=1).values
+    found = c_best >= 3
+    best_slot = d_pad.gather(1, k_best.clamp(max=k_max - 1)[:, None]).reshape(-1).clamp(max=S - 1)
+    best_glob = hyp_of_slot[best_slot]
+    # 6.
+    m = M['models'][best_glob]
+    T = eye.repeat(n_jobs, 1, 1)
+    T[:, :3, :3], T[:, :3, 3] = m[:, :9].reshape(-1, 3, 3), m[:, 9:]
+    cf = c_best.to(torch.float64)
+    out['transform'] = torch.where(found[:, None, None], T, eye)
+    out['fitness'] = torch.where(found & (d_nq > 0), cf / d_nq.clamp(min=1.0), torch.zeros_like(cf))
+    out['inlier_rmse'] = torch.where(found, torch.sqrt(s_best / cf.clamp(min=1.0)), torch.zeros_like(cf))
+    out['best_hyp'] = torch.where(found, best_glob - d_hoff, torch.full_like(best_glob, -1)).to(torch.int32)
+    out['n_validated'] = (c_pad >= 0).sum(dim=1).to(torch.int32)
+    out['status'] = torch.where(found, 0, 1).to(torch.int32)
+    return out
