@@ -168,7 +168,8 @@ int sga_fusion_var_bwd(const float* const* embs, int M, const int32_t* widths, c
  * duplicate edges count with their multiplicity (as PyG's scatter does) up to 255 copies of one (source, target) pair -- the
  * multiplicity matrix is 8-bit and saturates there; when that happens bit 0 of *status (device int32, caller-zeroed, may be NULL)
  * is set, and the Python wrapper turns it into an exception (deferred by at most one step, like the edge range check).
- * A graph with more than 256 nodes is rejected with SGA_ERR_ARG.
+ * A graph with more than 256 nodes is rejected with SGA_ERR_ARG.  Both limits -- 256 nodes, 255 copies -- belong to THIS route, the dense
+ * multiplicity matrix in LDS; the sparse route below (sga_gat_sp_*) has neither.
  * complete [G] uint8 (may be NULL): 1 = graph g lists every ordered pair i != j exactly once and nothing else -- what
  * preprocessing/scan3r/preprocess.py:176-182 writes for every scene (annotated relations + the supplemented 'none' pairs); its
  * multiplicities are all 1 and the kernels do not read its edges at all (16 B per edge: 2.13 GB at configs[2], eight times per step).
@@ -195,6 +196,47 @@ int sga_gat_attn_bwd_hc(const float* H, const float* dO, int heads, int channels
                         const int64_t* edges, const int32_t* node_off, const int32_t* edge_off, int G, int nmax, float* dH,
                         float* d_att_src, float* d_att_dst, const uint8_t* complete, void* stream);
 int sga_gat_lds_nodes(int channels, int bwd);
+/* The SPARSE route: the same attention over a compressed edge list instead of a dense matrix in LDS -- graphs of ANY size, multiplicities of
+ * 32 bits (no saturation, no status word), no atomics: every sum's order is fixed by the structure alone, so the outputs are bitwise
+ * repeatable, a graph's out / dH rows are the same bits alone or inside a batch, and nothing depends on the order in which the edge list
+ * names the edges.  Limits: 1 <= heads <= 65536, 1 <= channels <= 256 per head, T * heads below 2^31, cap = sum E + T at most 2^31 - 65.  The entry points above (the dense
+ * route, at most 256 nodes per graph) are unchanged and remain the default of the Python layer; sga_gcn_aggregate is dense-only.
+ *
+ * Structure, built on the device once per batch from the inputs of the dense route (T = node_off[G] nodes, E = edge_off[G] listed edges;
+ * input self loops and endpoints outside [0, nodes of the graph) dropped, one self loop added per node, duplicates counted), over
+ * batch-global node ids:
+ *   row_ptr [T+1], src [cap], mult [cap]   target-major: the entries of target i are [row_ptr[i], row_ptr[i+1]), sources ascending
+ *   col_ptr [T+1], tgt [cap], perm [cap]   its transpose: the entries of source j, targets ascending; perm = index of the target-major entry
+ * U = row_ptr[T] = col_ptr[T] <= cap entries are used (U stays on the device); the slots behind them are zeroed.  The caller sorts:
+ *   sga_gat_sp_keys      keys [cap] int64: target << 32 | source per listed edge and per self loop, INT64_MAX for a dropped edge
+ *   (caller)             sorted_keys = sort(keys)
+ *   sga_gat_sp_heads     head [cap] int32: 1 where a run of equal sorted keys begins
+ *   (caller)             head_incl = inclusive prefix sum of head, int32
+ *   sga_gat_sp_rows      row_ptr, src, mult and keys_t [cap] int64 (source << 32 | target per entry, INT64_MAX behind U);
+ *                        workspace: sga_gat_sp_build_workspace_bytes(cap) bytes
+ *   (caller)             sorted_keys_t, order_t = sort(keys_t) with the int64 slot each key came from
+ *   sga_gat_sp_cols      col_ptr, tgt, perm
+ * sga_gat_sp_capacity(T, E) = T + E, or -1 (message set) where that exceeds 2^31 - 65 (the kernels walk a segment in steps of 64 entries
+ * with 32-bit positions); every call that takes cap refuses a larger one.
+ * sga_gat_sp_fwd / sga_gat_sp_bwd: H / dO / out / dH [T, heads*channels] head-major, att_src / att_dst / bias / d_att_src / d_att_dst
+ * [heads*channels], workspace of sga_gat_sp_workspace_bytes(T, cap, heads, channels, bwd) bytes (0: bad arguments, or nothing needed;
+ * a smaller one is SGA_ERR_WORKSPACE).  T == 0 is a no-op; the backward still zeroes d_att_src / d_att_dst. */
+int sga_gat_sp_capacity(int T, int E);
+size_t sga_gat_sp_build_workspace_bytes(int cap);
+size_t sga_gat_sp_workspace_bytes(int T, int cap, int heads, int channels, int bwd);
+int sga_gat_sp_keys(const int64_t* edges, const int32_t* node_off, const int32_t* edge_off, int G, int T, int E, int64_t* keys, void* stream);
+int sga_gat_sp_heads(const int64_t* sorted_keys, int cap, int32_t* head, void* stream);
+int sga_gat_sp_rows(const int64_t* sorted_keys, const int32_t* head_incl, int cap, int T, int32_t* row_ptr, int32_t* src, int32_t* mult,
+                    int64_t* keys_t, void* workspace, size_t ws_bytes, void* stream);
+int sga_gat_sp_cols(const int64_t* sorted_keys_t, const int64_t* order_t, int cap, int T, int32_t* col_ptr, int32_t* tgt, int32_t* perm,
+                    void* stream);
+int sga_gat_sp_fwd(const float* H, int heads, int channels, const float* att_src, const float* att_dst, const float* bias,
+                   const int32_t* row_ptr, const int32_t* src, const int32_t* mult, int T, float* out, void* workspace, size_t ws_bytes,
+                   void* stream);
+int sga_gat_sp_bwd(const float* H, const float* dO, int heads, int channels, const float* att_src, const float* att_dst,
+                   const int32_t* row_ptr, const int32_t* src, const int32_t* mult, const int32_t* col_ptr, const int32_t* tgt,
+                   const int32_t* perm, int T, int cap, float* dH, float* d_att_src, float* d_att_dst, void* workspace, size_t ws_bytes,
+                   void* stream);
 int sga_elu_fwd(const float* x, float* y, size_t n, void* stream);                    /* F.elu, gat.py:45-46 */
 int sga_elu_bwd(const float* x, const float* gy, float* gx, size_t n, void* stream);
 
@@ -202,7 +244,7 @@ int sga_elu_bwd(const float* x, const float* gy, float* gx, size_t n, void* stre
  * replaces torch_geometric.nn.GCNConv(in, out, cached=False) as src/aligner/networks/gat.py:6-25 (MultiGCN) stacks it, for all graphs of a
  * batch in one launch.  H [T,C] = x W^T (any C >= 1), bias [C] or NULL; edges / node_off / edge_off / nmax / status as for the GAT kernels
  * above (graph-local ids, endpoints out of range dropped, at most 256 nodes per graph -- more is SGA_ERR_ARG --, 8-bit multiplicities
- * with bit 0 of *status set beyond 255 copies of one pair).  Input self loops are removed, every node gets one self loop of weight 1,
+ * with bit 0 of *status set beyond 255 copies of one pair; there is no sparse route for the GCN yet).  Input self loops are removed, every node gets one self loop of weight 1,
  * deg_i = 1 + #{listed j -> i, j != i} (duplicates counted), dinv = deg^-1/2 correctly rounded to fp32, and
  *   transpose == 0:  out[i] = sum_{j -> i} dinv_i dinv_j H[j] + bias      (relu != 0: max(., 0) on top)
  *   transpose != 0:  out[j] = sum_{j -> i} dinv_i dinv_j H[i]             (the backward of the line above; bias NULL, relu 0)

@@ -44,6 +44,15 @@ SIGNATURES = {
     'sga_gat_attn_fwd_hc': (I, [P, I, I, P, P, P, P, P, P, I, I, P, P, P, P]),
     'sga_gat_attn_bwd_hc': (I, [P, P, I, I, P, P, P, P, P, I, I, P, P, P, P, P]),
     'sga_gat_lds_nodes': (I, [I, I]),
+    'sga_gat_sp_capacity': (I, [I, I]),
+    'sga_gat_sp_build_workspace_bytes': (c_size_t, [I]),
+    'sga_gat_sp_workspace_bytes': (c_size_t, [I, I, I, I, I]),
+    'sga_gat_sp_keys': (I, [P, P, P, I, I, I, P, P]),
+    'sga_gat_sp_heads': (I, [P, I, P, P]),
+    'sga_gat_sp_rows': (I, [P, P, I, I, P, P, P, P, P, c_size_t, P]),
+    'sga_gat_sp_cols': (I, [P, P, I, I, P, P, P, P]),
+    'sga_gat_sp_fwd': (I, [P, I, I, P, P, P, P, P, P, I, P, P, c_size_t, P]),
+    'sga_gat_sp_bwd': (I, [P, P, I, I, P, P, P, P, P, P, P, P, I, I, P, P, P, P, c_size_t, P]),
     'sga_elu_fwd': (I, [P, P, c_size_t, P]),
     'sga_elu_bwd': (I, [P, P, P, c_size_t, P]),
     'sga_simrank_workspace_bytes': (c_size_t, [I]),

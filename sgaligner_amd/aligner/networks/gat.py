@@ -34,13 +34,17 @@ class GATConv(nn.Module):
 class MultiGAT(nn.Module):
     """gat.py:27-48: GATConv layers of any depth, head count and width (at most MAX_CHANNELS channels per head), dropout on every layer's
     input, ELU between layers.  The reference's own model -- n_units=[F,128,128], n_heads=[2,2], no dropout -- runs on the kernels
-    specialised for it; every other stack on the general ones (ops.multi_gat_layers)."""
+    specialised for it; every other stack on the general ones (ops.multi_gat_layers).
+    route: 'dense' (default; a graph holds at most 256 nodes), 'sparse' (the CSR attention kernels: graphs of any size, no atomics -- every
+    model, the 2 x 128 one included) or 'auto' (per batch: sparse exactly when its largest graph has more than 256 nodes)."""
     MAX_CHANNELS = 256
 
-    def __init__(self, n_units=[17, 128, 100], n_heads=[2, 2], dropout=0.0):
+    def __init__(self, n_units=[17, 128, 100], n_heads=[2, 2], dropout=0.0, route='dense'):
         super().__init__()
         self.num_layers = len(n_units) - 1
         self.dropout = dropout
+        ops.resolve_route(route)
+        self.route = route
         if self.num_layers < 1 or len(n_heads) != self.num_layers:
             raise ValueError(f'sgaligner_amd MultiGAT: n_units {list(n_units)} needs at least two entries and one head count per layer, '
                              f'got n_heads {list(n_heads)}')
@@ -62,9 +66,11 @@ class MultiGAT(nn.Module):
         """All graphs of a batch in one launch per layer (x [T,F], graph_batch: ops.GraphBatch).  masks: one [T, in_width] tensor per layer,
         already scaled by 1 / (1 - p), used INSTEAD of drawing (parity with a recorded run); without them F.dropout draws in train mode."""
         drop = self.training and self.dropout > 0.0
-        if self._canonical and masks is None and not drop:
+        route = ops.resolve_route(self.route, graph_batch)
+        if route == 'dense' and self._canonical and masks is None and not drop:
             return ops.multi_gat(graph_batch, x, self.layer_stack[0].params(), self.layer_stack[1].params())
-        return ops.multi_gat_layers(graph_batch, x, [l.params() for l in self.layer_stack], p=self.dropout, training=self.training, masks=masks)
+        return ops.multi_gat_layers(graph_batch, x, [l.params() for l in self.layer_stack], p=self.dropout, training=self.training, masks=masks,
+                                    route=route)
 
     def forward(self, x, edges):
         """Reference signature (gat.py:40): one graph, x [N,F], edges [2,E] (row 0 source, row 1 target)."""

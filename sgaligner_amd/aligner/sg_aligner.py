@@ -58,9 +58,10 @@ class MultiModalEncoder(nn.Module):
     with the reference's name -- it shadows nn.Module.modules(), exactly as in the reference (:41)."""
 
     def __init__(self, modules, rel_dim, attr_dim, hidden_units=[3, 128, 128], heads=[2, 2], emb_dim=100,
-                 pt_out_dim=256, dropout=0.0, attn_dropout=0.0, instance_norm=False):
+                 pt_out_dim=256, dropout=0.0, attn_dropout=0.0, instance_norm=False, gat_route='dense'):
         super().__init__()
         self.modules = modules
+        self.gat_route = gat_route          # MultiGAT's route: 'dense' | 'sparse' | 'auto' (graphs of more than 256 nodes need the sparse one)
         self.pt_out_dim = pt_out_dim
         self.rel_dim = rel_dim
         self.emb_dim = emb_dim
@@ -82,7 +83,7 @@ class MultiModalEncoder(nn.Module):
         else:
             raise NotImplementedError                                   # sg_aligner.py:61-62
         self.object_embedding = _Linear(self.pt_out_dim, self.emb_dim)
-        self.structure_encoder = MultiGAT(n_units=self.hidden_units, n_heads=self.heads, dropout=self.dropout)
+        self.structure_encoder = MultiGAT(n_units=self.hidden_units, n_heads=self.heads, dropout=self.dropout, route=self.gat_route)
         self.structure_embedding = _Linear(256, self.emb_dim)
         self.fusion = MultiModalFusion(modal_num=self.inner_view_num, with_weight=1)
         self._on_table = None          # optional callable(module, table), see forward
