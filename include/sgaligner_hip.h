@@ -408,6 +408,15 @@ int sga_loss_scatter_tangent(const float* dZ, const float* Z, const float* nrm, 
  * product, fp32 accumulation; dZ [2A.., 104] receives the two-part form (columns 0..99 and 101) that sga_loss_scatter_tangent projects. */
 int sga_loss_stash_grad_symx_bf16x6(const float* M1, const float* M2, const void* Zb, int A, int J1, int J2, float* dZ,
                                     int a_lo, int a_hi, int j_lo, int j_hi, int mir, void* stream);
+/* How that entry point cuts a job into workgroups on a device of `cus` compute units; launches nothing and needs no device.
+ * plan[25] = {workgroups, then per product (up to four, unused ones zero) {owner rows, first 32-row tile, end tile, nsplit, first workgroup,
+ * transposed}}: workgroup blk0 + s * nob + ob of a product (nob = ceil(owner rows / 128)) takes owner rows 128 ob .. and the tiles
+ * [t0 + s per, min(t1, t0 + (s + 1) per)), per = ceil((t1 - t0) / nsplit).
+ * sga_loss_stash_unit_tiles: the length in tiles that a work unit aims at (0: the library's default; every product still gets ~4
+ * workgroups per CU); -n: units of exactly n tiles whatever the fill (small jobs in tests).  Returns the value before.  Process-wide;
+ * for tests and timing. */
+int sga_loss_stash_plan(int A, int a_lo, int a_hi, int j_lo, int j_hi, int mir, int cus, int32_t* plan);
+int sga_loss_stash_unit_tiles(int tiles);
 /* sga_loss_anchor_multi_bwd_symx with the similarities formed from the three-plane images Zb[m] of sga_loss_split3_tables (same A, J1, J2;
  * their anchor segments X1 | X2) on the bf16 matrix pipe: the sweeps' six partial products in one fp32 accumulator, then the fp32 kernel's
  * own epilogue.  M = 2 or 3.  Same outputs: stash layouts, gs / gamma / out_terms slots and their fold.  a_lo, j_lo, mir: multiples of 32

@@ -148,6 +148,8 @@ SIGNATURES = {
     'sga_loss_split3_tables': (I, [P, I, I, I, P, P, P]),
     'sga_loss_scatter_tangent': (I, [P, P, P, P, I, I, I, I, P, P, P]),
     'sga_loss_stash_grad_symx_bf16x6': (I, [P, P, P, I, I, I, P, I, I, I, I, I, P]),
+    'sga_loss_stash_plan': (I, [I, I, I, I, I, I, I, P]),
+    'sga_loss_stash_unit_tiles': (I, [I]),
     'sga_loss_anchor_multi_bwd_symx_bf16x6': (I, [P, I, P, I, I, I, P, F, F, F, P, P, P, P, P, I, I, I, I, I, P, P]),
     'sga_loss_anchor_plan': (I, [I, I, I, I, I, I, I, I, P]),
     'sga_loss_multi_sums_bf16x6': (I, [P, I, P, I, I, I, F, F, P, I, I, I, P]),

@@ -1103,6 +1103,21 @@ __global__ __launch_bounds__(WV * 64, WV == 8 ? 2 : 1) void sweep3_kernel(TArgs 
 struct SProd { const float* S; int ld, tn, own_seg, own0, nown, oth_seg, oth0, noth, blk0, nsplit; };
 struct SArgs { const unsigned char* Zb; float* dZ; const float* zero; int A, nbA, n; SProd p[4]; };   // zero: a readable word that holds 0.f
 
+// One LDS-DMA of stash3_kernel: 64 lanes x 16 B from base + 16 lane (base wave-uniform, off = 16 lane) to LDS [lds_addr + 16 lane] (lds_addr
+// wave-uniform, through M0: written in the statement that reads it, one wait state apart).  Inline asm on purpose: hipcc does not count these
+// loads, so it neither drains them nor orders an LDS read behind them -- stash3_wait_barrier does, by count.
+__device__ __forceinline__ void stash3_copy(const unsigned char* base, unsigned off, unsigned lds_addr) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(off), "s"(base) : "memory");
+}
+// The end of a step: at most N vector-memory requests of this wave stay in flight (the N newest: the coefficient loads issued behind the
+// copies), its LDS reads have returned, then the workgroup's barrier -- a raw s_barrier: __syncthreads() would drain every request.
+template <int N> __device__ __forceinline__ void stash3_wait_barrier() {
+    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit count");
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
+}
+// coefficient-load instructions per step and wave in the forms of stash3_kernel's load_c: 2 row sets x 2 dwordx4 (form 1) | 2 row sets x 8 dwords
+constexpr int s3_nc(int form) { return form == 1 ? 4 : 16; }
+
 __global__ __launch_bounds__(256, 2) void stash3_kernel(SArgs a) {
     // 4 waves x 32 owner rows: a wave applies every B operand it reads from LDS (the other rows' planes, transposed) to TWO 16-row coefficient
     // sets.  With 16 rows per wave and 16 waves per CU the transpose reads alone were 344 KB per CU and tile round -- 2 700 cycles of the LDS's
@@ -1137,25 +1152,35 @@ __global__ __launch_bounds__(256, 2) void stash3_kernel(SArgs a) {
     unsigned l16 = threadIdx.x;
     asm volatile("" : "+v"(l16));
     l16 = (l16 & 63u) * 16u;
-    auto issue = [&](int blk, unsigned char* buf) {
-        const unsigned long long tb = sreg64(reinterpret_cast<unsigned long long>(a.Zb) + (unsigned long long)blk * S3_BLOCK);
+    // The copy of a 32-row block into an LDS buffer: KMAX LDS-DMAs of 1 KiB per wave, by stash3_copy -- hipcc neither counts them nor orders
+    // an LDS read behind them; the loop below waits for them itself (its comment states the protocol).
+    const unsigned lds_base = (unsigned)(size_t)((__attribute__((address_space(3))) unsigned char*)lds3);
+    auto issue = [&](int blk, unsigned buf) __attribute__((always_inline)) {
+        const unsigned char* tb = a.Zb + (size_t)blk * S3_BLOCK;
 #pragma unroll
         for (int k = 0; k < KMAX; ++k) {
             int c = wave_u + k * WAVES;
             if ((k + 1) * WAVES > S3_NCH) c = c >= S3_NCH ? c - WAVES : c;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const unsigned char*>(tb + (unsigned)(c * 1024)) + l16),
-                                             (__attribute__((address_space(3))) void*)(buf + c * 1024), 16, 0, 0);
+            stash3_copy(tb + c * 1024, l16, lds_base + buf * (unsigned)S3_BLOCK + (unsigned)(c * 1024));
         }
     };
-    // this lane's 8 coefficients of tile jt for its row set rs: owner row orow0 + 16 rs, others 32 jt + 8 g4 + k (segment rows); zero outside the product's ranges
-    auto load_c = [&](int jt, int rs, float (&c)[8]) {
+    // this lane's 8 coefficients of tile jt for its row set rs: owner row orow0 + 16 rs, others 32 jt + 8 g4 + k (segment rows); zero outside the
+    // product's ranges.  The form is the WORKGROUP's, fixed for its whole run, so that a step issues a known number of load instructions
+    // (s3_nc: the loop's counted wait is built on it).  When all 128 owner rows lie inside the product and every tile is whole, nothing has
+    // to be masked: form 1, untransposed with 16-byte aligned rows -- two dwordx4 per row set; form 2, transposed -- eight dwords a stash
+    // row apart, the second row set 64 B further on.  Form 0: element by element, each one tested.
+    auto load_c = [&](auto form, int jt, int rs, float (&c)[8]) __attribute__((always_inline)) {
         const int orow = orow0 + 16 * rs;
         const bool ov = orow < Pnown;
         const int r0 = 32 * jt + 8 * g4 - Poth0;                     // stash index of k = 0
-        if (!Ptn && (Pld & 3) == 0 && (Poth0 & 3) == 0 && ov && r0 >= 0 && r0 + 8 <= Pnoth) {
+        if constexpr (decltype(form)::value == 1) {
             const f32x4* q = reinterpret_cast<const f32x4*>(PS + (size_t)orow * Pld + r0);
             const f32x4 u = q[0], v = q[1];
             c[0] = u[0]; c[1] = u[1]; c[2] = u[2]; c[3] = u[3]; c[4] = v[0]; c[5] = v[1]; c[6] = v[2]; c[7] = v[3];
+        } else if constexpr (decltype(form)::value == 2) {
+            const float* q = PS + (size_t)r0 * Pld + orow;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) c[k] = q[(size_t)k * Pld];
         } else {
             // (no exec-masked loads and no masks kept until the values arrive -- eight of them per call cost this kernel its scalar registers:
             //  an element outside the product's ranges is read from a word that holds zero, the tables' slack block)
@@ -1185,18 +1210,24 @@ __global__ __launch_bounds__(256, 2) void stash3_kernel(SArgs a) {
     // The coefficient tiles come straight from HBM (the stash is read once per product and never again): TWO tiles in flight per wave -- a tile's
     // values are split into their planes first thing in its step and the load of the tile after next goes into the same registers, while the
     // next tile's load (issued one step earlier) is still travelling.
+    //
+    // The wait protocol is written out (hipcc would put s_waitcnt vmcnt(0) in front of the first transpose read behind a copy it knows of,
+    // i.e. wait at the head of every step for the copy AND the coefficient loads it issued a moment earlier).  A step, in program order:
+    //   1. split this tile's coefficients (loaded two steps ago; hipcc's own counted wait for those registers stands in front of it, and
+    //      counts only hipcc's loads -- the copies it does not know of sit OLDER in the queue than what that count leaves in flight);
+    //   2. issue the next tile's copies into the other buffer (stash3_copy);
+    //   3. issue the coefficient loads of the tile after next, NC instructions, into the registers just consumed;
+    //   4. the 84 MFMAs on this tile's buffer;
+    //   5. stash3_wait_barrier<NC>: s_waitcnt vmcnt(NC) -- the requests retire in order, so the copies of 2. have landed and only the loads
+    //      of 3. stay in flight -- + lgkmcnt(0), then s_barrier (vmcnt(0) in a step that issued no loads).
+    // INVARIANT: no wave ever waits for a request it issued in the current step before the step's MFMAs are behind it, and a buffer is read
+    // only behind the barrier that follows the wait which retired its copy (every wave waits for its own copies, then the barrier); it is
+    // overwritten only behind the barrier that follows its last read (5.'s lgkmcnt(0)).  sched_barrier(0) pins 1. | 2. 3. | 4. | 5.
     float c0[RW][8], c1[RW][8];
-#pragma unroll
-    for (int rs = 0; rs < RW; ++rs) {
-        load_c(jt0, rs, c0[rs]);
-        if (jt0 + 1 < jt1) load_c(jt0 + 1, rs, c1[rs]);
-    }
-    issue(oblk0 + jt0, lds3);
     int it = 0;
-    auto step = [&](int jt, float (&cc)[RW][8]) {
-        unsigned char* buf = lds3 + (it & 1) * S3_BLOCK;
-        __syncthreads();                                   // tile `it` has landed, the other buffer is free
-        issue(oblk0 + (jt + 1 < jt1 ? jt + 1 : jt), lds3 + ((it + 1) & 1) * S3_BLOCK);
+    auto step = [&](auto form, int jt, float (&cc)[RW][8]) __attribute__((always_inline)) {
+        constexpr int NC = s3_nc(decltype(form)::value);
+        const unsigned char* buf = lds3 + (it & 1) * S3_BLOCK;
         u32x4 ch[RW], cm[RW], cl[RW];
 #pragma unroll
         for (int rs = 0; rs < RW; ++rs)
@@ -1206,10 +1237,16 @@ __global__ __launch_bounds__(256, 2) void stash3_kernel(SArgs a) {
                 split3_pair(cc[rs][2 * p], cc[rs][2 * p + 1], h_, m_, l_);
                 ch[rs][p] = h_; cm[rs][p] = m_; cl[rs][p] = l_;
             }
-        if (jt + 2 < jt1) {                                // into the registers just consumed
+        // (the planes exist HERE: a volatile statement keeps its place among the copies', and the split cannot sink below them to its first use)
 #pragma unroll
-            for (int rs = 0; rs < RW; ++rs) load_c(jt + 2, rs, cc[rs]);
-        }
+        for (int rs = 0; rs < RW; ++rs) asm volatile("" : "+v"(ch[rs]), "+v"(cm[rs]), "+v"(cl[rs]));
+        __builtin_amdgcn_sched_barrier(0);
+        if (jt + 1 < jt1) issue(oblk0 + jt + 1, (unsigned)((it + 1) & 1));
+        // into the registers just consumed.  Unconditionally (the run's last two steps reload its last tile, from L2, and drop it): NC is
+        // the same in every step, and hipcc's count in front of the split never has to cover a path on which nothing was loaded
+#pragma unroll
+        for (int rs = 0; rs < RW; ++rs) load_c(form, min(jt + 2, jt1 - 1), rs, cc[rs]);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) {
             u32x4 bp[3];
@@ -1234,13 +1271,36 @@ __global__ __launch_bounds__(256, 2) void stash3_kernel(SArgs a) {
 #pragma unroll
             for (int rs = 0; rs < RW; ++rs) gacc[rs][ct] = mfma_b(ch[rs], bp[0], gacc[rs][ct]);
         }
+        __builtin_amdgcn_sched_barrier(0);
+        stash3_wait_barrier<NC>();
+        __builtin_amdgcn_sched_barrier(0);
         ++it;
     };
+    auto run = [&](auto form) __attribute__((always_inline)) {
+        constexpr int NC = s3_nc(decltype(form)::value);
+        issue(oblk0 + jt0, 0u);
+#pragma unroll
+        for (int rs = 0; rs < RW; ++rs) load_c(form, jt0, rs, c0[rs]);
+#pragma unroll
+        for (int rs = 0; rs < RW; ++rs) load_c(form, min(jt0 + 1, jt1 - 1), rs, c1[rs]);
+        __builtin_amdgcn_sched_barrier(0);
+        stash3_wait_barrier<2 * NC>();                     // tile jt0 has landed; both coefficient tiles stay in flight
+        __builtin_amdgcn_sched_barrier(0);
+        // two steps per trip (the two register sets take turns without a move); an odd run's last step stands behind the loop, so that no
+        // path reaches a split without the loads hipcc counts for it
+        int jt = jt0;
 #pragma unroll 1
-    for (int jt = jt0; jt < jt1; jt += 2) {
-        step(jt, c0);
-        if (jt + 1 < jt1) step(jt + 1, c1);
-    }
+        for (; jt + 1 < jt1; jt += 2) {
+            step(form, jt, c0);
+            step(form, jt + 1, c1);
+        }
+        if (jt < jt1) step(form, jt, c0);
+    };
+    // the form of load_c: one for the whole workgroup (see there)
+    const bool whole = (Poth0 & 31) == 0 && (Pnoth & 31) == 0 && ob * OWN + OWN <= Pnown;
+    if (whole && Ptn) run(std::integral_constant<int, 2>{});
+    else if (whole && (Pld & 3) == 0 && (reinterpret_cast<size_t>(PS) & 15) == 0) run(std::integral_constant<int, 1>{});
+    else run(std::integral_constant<int, 0>{});
     // out rows: accumulator layout row = 4 g4 + r of the row set's 16, column 16 ct + l15
     float* dz = a.dZ + (size_t)(P.own_seg ? a.A : 0) * S3_DP;
 #pragma unroll
@@ -1521,18 +1581,13 @@ extern "C" int sga_loss_multi_grad_bf16x6(const void* const* Zb, int M, const fl
     return SGA_OK;
 }
 
-extern "C" int sga_loss_stash_grad_symx_bf16x6(const float* M1, const float* M2, const void* Zb, int A, int J1, int J2, float* dZ,
-                                               int a_lo, int a_hi, int j_lo, int j_hi, int mir, void* stream) {
-    SGA_CHECK_ARG(M1 && Zb && dZ && A >= 0 && a_lo >= 0 && a_hi <= A && a_lo <= a_hi && j_lo >= 0 && j_lo <= j_hi && j_hi <= A &&
-                  mir >= j_lo && (M2 || mir >= j_hi), "sga_loss_stash_grad_symx_bf16x6: bad argument");
+namespace {
+
+// The products of one stash job (the block arguments of sga_loss_stash_grad_symx), without their split:
+// d1[a_lo + i] += sum_j M1[j][i] X2[j_lo + j];  d2[j_lo + j] += sum_i M1[j][i] X1[a_lo + i];
+// d1[mir + j]  += sum_i M2[j][i] X2[a_lo + i];  d2[a_lo + i] += sum_j M2[j][i] X1[mir + j]      (segments: 0 = X1, 1 = X2)
+void stash_products(SArgs& a, const float* M1, const float* M2, int a_lo, int a_hi, int j_lo, int j_hi, int mir) {
     const int ns = a_hi - a_lo, c1 = j_hi - j_lo, c2 = mir < j_hi ? j_hi - mir : 0;
-    if (A == 0 || ns == 0 || c1 == 0) return SGA_OK;
-    const TLayout L = make_tlayout(A, J1, J2);
-    SArgs a{};
-    a.Zb = static_cast<const unsigned char*>(Zb); a.dZ = dZ; a.A = A; a.nbA = L.nbA;
-    a.zero = reinterpret_cast<const float*>(a.Zb + (size_t)(2 * L.nbA + L.nb1 + L.nb2) * S3_BLOCK);      // the slack block (zeroed by sga_loss_split3_tables)
-    // d1[a_lo + i] += sum_j M1[j][i] X2[j_lo + j];  d2[j_lo + j] += sum_i M1[j][i] X1[a_lo + i];
-    // d1[mir + j]  += sum_i M2[j][i] X2[a_lo + i];  d2[a_lo + i] += sum_j M2[j][i] X1[mir + j]      (segments: 0 = X1, 1 = X2)
     int n = 0;
     a.p[n++] = SProd{M1, ns, 1, 0, a_lo, ns, 1, j_lo, c1, 0, 1};
     a.p[n++] = SProd{M1, ns, 0, 1, j_lo, c1, 0, a_lo, ns, 0, 1};
@@ -1541,19 +1596,69 @@ extern "C" int sga_loss_stash_grad_symx_bf16x6(const float* M1, const float* M2,
         a.p[n++] = SProd{M2, ns, 1, 1, a_lo, ns, 0, mir, c2, 0, 1};
     }
     a.n = n;
-    // work units of ~128 owner rows x ~64 other tiles: enough workgroups to fill the chip several times over whatever the block's shape
+}
+
+// The split of a job's products into work units of 128 owner rows x a run of 32-row tiles, and their first workgroups; returns the grid.
+// A unit ends with 128 x 102 atomic additions, so it should be long -- `unit` tiles, S3_STASH_UNIT_TILES unless sga_loss_stash_unit_tiles
+// says otherwise -- but every product keeps at least ~4 workgroups per CU, whatever the block's shape.  The kernel cuts the tiles into
+// nsplit runs of ceil(tiles / nsplit) (the last ones may be short or empty).
+// (an override < 0 asks for units of exactly that many tiles and drops the fill rule: how a test reaches a multi-tile unit on a small job)
+constexpr int S3_STASH_UNIT_TILES = 128;
+int g_stash_unit_tiles = 0;
+int stash_plan(SArgs& a, int cus) {
+    const bool exact = g_stash_unit_tiles < 0;
+    const int unit = exact ? -g_stash_unit_tiles : g_stash_unit_tiles > 0 ? g_stash_unit_tiles : S3_STASH_UNIT_TILES;
     int nwg = 0;
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < a.n; ++i) {
         SProd& P = a.p[i];
         const int n_ob = (P.nown + 127) / 128, tiles = ((P.oth0 + P.noth + 31) >> 5) - (P.oth0 >> 5);
-        int nsp = (tiles + 63) / 64;
-        const int want = (4 * sga_num_cus() + n_ob - 1) / n_ob;        // at least ~4 workgroups per CU per product
+        int nsp = (tiles + unit - 1) / unit;
+        const int want = exact ? 1 : (4 * cus + n_ob - 1) / n_ob;
         if (nsp < want) nsp = want;
         if (nsp > tiles) nsp = tiles;
         if (nsp < 1) nsp = 1;
         P.nsplit = nsp; P.blk0 = nwg;
         nwg += n_ob * nsp;
     }
+    return nwg;
+}
+
+}  // namespace
+
+extern "C" int sga_loss_stash_unit_tiles(int tiles) {
+    const int before = g_stash_unit_tiles;
+    g_stash_unit_tiles = tiles;
+    return before;
+}
+
+extern "C" int sga_loss_stash_plan(int A, int a_lo, int a_hi, int j_lo, int j_hi, int mir, int cus, int32_t* plan) {
+    SGA_CHECK_ARG(plan && cus > 0 && A >= 0 && a_lo >= 0 && a_hi <= A && a_lo <= a_hi && j_lo >= 0 && j_lo <= j_hi && j_hi <= A && mir >= j_lo,
+                  "sga_loss_stash_plan: bad argument");
+    SArgs a{};
+    for (int i = 0; i < 1 + 4 * 6; ++i) plan[i] = 0;
+    if (A == 0 || a_hi == a_lo || j_hi == j_lo) return SGA_OK;
+    stash_products(a, nullptr, nullptr, a_lo, a_hi, j_lo, j_hi, mir);
+    plan[0] = stash_plan(a, cus);
+    for (int i = 0; i < a.n; ++i) {
+        const SProd& P = a.p[i];
+        int32_t* q = plan + 1 + 6 * i;
+        q[0] = P.nown; q[1] = P.oth0 >> 5; q[2] = (P.oth0 + P.noth + 31) >> 5; q[3] = P.nsplit; q[4] = P.blk0; q[5] = P.tn;
+    }
+    return SGA_OK;
+}
+
+extern "C" int sga_loss_stash_grad_symx_bf16x6(const float* M1, const float* M2, const void* Zb, int A, int J1, int J2, float* dZ,
+                                               int a_lo, int a_hi, int j_lo, int j_hi, int mir, void* stream) {
+    SGA_CHECK_ARG(M1 && Zb && dZ && A >= 0 && a_lo >= 0 && a_hi <= A && a_lo <= a_hi && j_lo >= 0 && j_lo <= j_hi && j_hi <= A &&
+                  mir >= j_lo && (M2 || mir >= j_hi), "sga_loss_stash_grad_symx_bf16x6: bad argument");
+    const int ns = a_hi - a_lo, c1 = j_hi - j_lo;
+    if (A == 0 || ns == 0 || c1 == 0) return SGA_OK;
+    const TLayout L = make_tlayout(A, J1, J2);
+    SArgs a{};
+    a.Zb = static_cast<const unsigned char*>(Zb); a.dZ = dZ; a.A = A; a.nbA = L.nbA;
+    a.zero = reinterpret_cast<const float*>(a.Zb + (size_t)(2 * L.nbA + L.nb1 + L.nb2) * S3_BLOCK);      // the slack block (zeroed by sga_loss_split3_tables)
+    stash_products(a, M1, M2, a_lo, a_hi, j_lo, j_hi, mir);
+    const int nwg = stash_plan(a, sga_num_cus());
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t lds = (size_t)2 * S3_BLOCK;
     hipFuncSetAttribute(reinterpret_cast<const void*>(stash3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
