@@ -4,7 +4,7 @@
 // LeakyReLU(0.2)), the head :311-315 (BN + ReLU on [T, C]).
 //
 // Four HBM-bound passes (a thread owns one channel of a row strip, lanes = consecutive channels -> coalesced):
-//   bn_stats      sum x, sum x^2 per channel               (fp32 partials -> fp64 atomics)
+//   bn_stats      sum x, sum x^2 per channel               (fp64 partials -> fp64 atomics)
 //   bn_apply      y = act(x * scale + shift) (+ resid)     scale = gamma * rstd, shift = beta - mean * scale (host, C values)
 //   bn_bwd_stats  g = dy * act'(x * scale + shift);  sum g, sum g * xhat per channel        (= dbeta, dgamma)
 //   bn_bwd_apply  dx = gamma * rstd * (g - mean(g) - xhat * mean(g * xhat))
@@ -20,21 +20,24 @@ __device__ __forceinline__ float act_grad(float pre, int act) { return act == 1 
 
 __global__ void bn_stats_kernel(const float* __restrict__ X, long ld, int R, int C, double* __restrict__ sums) {
     const int c = blockIdx.x * 64 + (threadIdx.x & 63), rw = threadIdx.x >> 6;
-    float s = 0.f, q = 0.f;
+    // fp64 from the first addition on: bn_finalize forms var = sum x^2 / R - mean^2, which cancels (mean / std)^2 of the sums' leading
+    // digits -- fp32 partial sums left the variance of a column at mean / std = 32 with four digits, at 1000 with none.  The pass is
+    // bound by the read of X; an fp64 product of two fp32 values is exact.
+    double s = 0.0, q = 0.0;
     if (c < C)
         for (int r = blockIdx.y * 4 + rw; r < R; r += gridDim.y * 4) {
-            const float v = X[(size_t)r * ld + c];
+            const double v = (double)X[(size_t)r * ld + c];
             s += v;
-            q = fmaf(v, v, q);
+            q = fma(v, v, q);
         }
-    __shared__ float red[2][4][64];
+    __shared__ double red[2][4][64];
     red[0][rw][threadIdx.x & 63] = s;
     red[1][rw][threadIdx.x & 63] = q;
     __syncthreads();
     if (rw == 0 && c < C) {
         const int k = threadIdx.x;
-        atomicAdd(sums + c, (double)red[0][0][k] + (double)red[0][1][k] + (double)red[0][2][k] + (double)red[0][3][k]);
-        atomicAdd(sums + C + c, (double)red[1][0][k] + (double)red[1][1][k] + (double)red[1][2][k] + (double)red[1][3][k]);
+        atomicAdd(sums + c, red[0][0][k] + red[0][1][k] + red[0][2][k] + red[0][3][k]);
+        atomicAdd(sums + C + c, red[1][0][k] + red[1][1][k] + red[1][2][k] + red[1][3][k]);
     }
 }
 

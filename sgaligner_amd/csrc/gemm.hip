@@ -165,8 +165,12 @@ __global__ __launch_bounds__(GM_THREADS) void gemm_small_kernel(const TA* __rest
 // offsets that are sums of a few multiples of ldc -- `C + (size_t)m * ldc + n` per element was two v_mul_lo_u32, a v_mad_u64_u32 and two more
 // 64-bit adds for every output (a K = 128 layer over 163 840 rows spent 38 of its 77 us there whatever its K: tools/bench_gemm.py with the
 // epilogue compiled out).  The optional C / residual loads of a tile are issued together; interior tiles carry no row masks.
+// STATS: the column sum and sum of squares of what is written, in fp64 from the first addition on -- BatchNorm forms
+// var = sum x^2 / R - mean^2 from them, which cancels (mean / std)^2 of their leading digits, and an fp32 partial sum over a lane's 64 rows
+// left a column at mean / std = 32 with four digits of its variance.  The product of two fp32 values is exact in fp64.
+template <bool STATS>
 __device__ __forceinline__ void store_tile32(const f32x16& a, float bv, float* __restrict__ C, long ldc, int m_base, int h, int M, int n, bool nv,
-                                             int accumulate, int act, const float* __restrict__ resid, long ldr, float& cs, float& cq) {
+                                             int accumulate, int act, const float* __restrict__ resid, long ldr, double& cs, double& cq) {
     if (!nv) return;
     const bool full = m_base + 32 <= M;                   // uniform
     float* cp = C + (size_t)(m_base + 4 * h) * ldc + n;
@@ -193,7 +197,7 @@ __device__ __forceinline__ void store_tile32(const f32x16& a, float bv, float* _
             v += rs[e];
             if (full || m_base + 4 * h + 8 * q + e < M) {
                 cp[(8 * q + e) * l1] = v;
-                cs += v; cq = fmaf(v, v, cq);
+                if (STATS) { const double vd = (double)v; cs += vd; cq = fma(vd, vd, cq); }
             }
         }
     }
@@ -248,14 +252,17 @@ __global__ __launch_bounds__(GM_THREADS) void gemm_nt_kernel(const float* __rest
     if (!nv && !colstats) return;
     const float bv = (bias && nv) ? bias[n] : 0.f;
     const int h = lane >> 5;
-    float cs = 0.f, cq = 0.f;                           // column sum / sum of squares of what is written (colstats != null)
+    double cs = 0.0, cq = 0.0;                          // column sum / sum of squares of what is written (colstats != null)
+    if (!colstats) {
 #pragma unroll
-    for (int t = 0; t < NTA; ++t) store_tile32(acc[t], bv, C, ldc, m0 + t * 32, h, M, n, nv, accumulate, act, resid, ldr, cs, cq);
-    if (colstats) {
+        for (int t = 0; t < NTA; ++t) store_tile32<false>(acc[t], bv, C, ldc, m0 + t * 32, h, M, n, nv, accumulate, act, resid, ldr, cs, cq);
+    } else {
+#pragma unroll
+        for (int t = 0; t < NTA; ++t) store_tile32<true>(acc[t], bv, C, ldc, m0 + t * 32, h, M, n, nv, accumulate, act, resid, ldr, cs, cq);
         // BatchNorm batch statistics of the output in the epilogue that produces it (pct.py: every conv is followed by a BatchNorm):
         // the two lane halves of a column fold, then one fp64 atomic pair per column and workgroup -- sums[0..N) = sum, [N..2N) = sum of squares
         cs += __shfl_xor(cs, 32, 64); cq += __shfl_xor(cq, 32, 64);
-        if (h == 0 && nv) { atomicAdd(colstats + n, (double)cs); atomicAdd(colstats + N + n, (double)cq); }
+        if (h == 0 && nv) { atomicAdd(colstats + n, cs); atomicAdd(colstats + N + n, cq); }
     }
 }
 
@@ -360,17 +367,18 @@ __global__ __launch_bounds__(GM_THREADS, 2) void gemm_nt3_kernel(const float* __
     const bool nv = n < N;
     if (!nv && !colstats) return;
     const float bv = (bias && nv) ? bias[n] : 0.f;
-    float cs = 0.f, cq = 0.f;                           // column sum / sum of squares of what is written (colstats != null)
+    double cs = 0.0, cq = 0.0;                          // column sum / sum of squares of what is written (colstats != null)
 #pragma unroll
     for (int t = 0; t < NTA; ++t) {
         f32x16 sum;
 #pragma unroll
         for (int r = 0; r < 16; ++r) sum[r] = acc[t][r] + accs[t][r];
-        store_tile32(sum, bv, C, ldc, m0 + t * 32, h, M, n, nv, accumulate, act, resid, ldr, cs, cq);
+        if (colstats) store_tile32<true>(sum, bv, C, ldc, m0 + t * 32, h, M, n, nv, accumulate, act, resid, ldr, cs, cq);
+        else store_tile32<false>(sum, bv, C, ldc, m0 + t * 32, h, M, n, nv, accumulate, act, resid, ldr, cs, cq);
     }
     if (colstats) {
         cs += __shfl_xor(cs, 32, 64); cq += __shfl_xor(cq, 32, 64);
-        if (h == 0 && nv) { atomicAdd(colstats + n, (double)cs); atomicAdd(colstats + N + n, (double)cq); }
+        if (h == 0 && nv) { atomicAdd(colstats + n, cs); atomicAdd(colstats + N + n, cq); }
     }
 }
 

@@ -63,10 +63,13 @@ __global__ __launch_bounds__(PA_THREADS) void attn_stats_kernel(const float* __r
             tmax = fmaxf(tmax, acc[r]);
         }
         const float mn = fmaxf(m, tmax);
+        // a half with no valid row yet (N <= 4: the upper half owns tile rows 4..7, 12..15, ...) keeps (m, l) = (-inf, 0): the differences are
+        // taken against 0 there, -inf - (-inf) would be NaN
+        const float ms = mn == -INFINITY ? 0.f : mn;
         float sum = 0.f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) sum += __builtin_amdgcn_exp2f((acc[r] - mn) * c);      // exp2(-inf) = 0
-        l = l * __builtin_amdgcn_exp2f((m - mn) * c) + sum;
+        for (int r = 0; r < 16; ++r) sum += __builtin_amdgcn_exp2f((acc[r] - ms) * c);      // exp2(-inf) = 0
+        l = l * __builtin_amdgcn_exp2f((m - ms) * c) + sum;
         m = mn;
     }
     // the two halves of the wave hold disjoint j subsets of the same row
@@ -122,8 +125,10 @@ __global__ __launch_bounds__(PA_THREADS) void attn_apply_kernel(const float* __r
         }
         if (tid < 32) {
             const bool ok = i0 + tid < N;
-            buf[32 * QS + 32 * VS + tid] = ok ? mt[i0 + tid] : 0.f;
-            buf[32 * QS + 32 * VS + 32 + tid] = ok ? (OWN ? 1.f : 1.f / lt[i0 + tid]) : 0.f;   // rows past N contribute nothing
+            // rows past N contribute nothing: 1/l = 0, and m = +inf so that the exponential is 0 too (with m = 0 a large energy of the
+            // clamped row overflows to inf, and inf * 0 is NaN)
+            buf[32 * QS + 32 * VS + tid] = ok ? mt[i0 + tid] : INFINITY;
+            buf[32 * QS + 32 * VS + 32 + tid] = ok ? (OWN ? 1.f : 1.f / lt[i0 + tid]) : 0.f;
         }
     };
 
@@ -239,7 +244,7 @@ __global__ __launch_bounds__(PA_THREADS) void attn_bwd_dq_kernel(const float* __
         if (tid < 32) {
             const bool ok = j0 + tid < N;
             float* st = buf + 32 * QS + 2 * 32 * VS;
-            st[tid] = ok ? mstat[base + j0 + tid] : 0.f;
+            st[tid] = ok ? mstat[base + j0 + tid] : INFINITY;           // exp2(-inf) = 0: no inf * 0 for a row past N
             st[32 + tid] = ok ? 1.f / lstat[base + j0 + tid] : 0.f;
             st[64 + tid] = ok ? delta[base + j0 + tid] : 0.f;
             st[96 + tid] = ok ? 1.f : 0.f;
