@@ -25,10 +25,8 @@
 //
 // normals_kernel / fpfh_kernel: one lane per point (per point and bin group); sums run in list order, so they are sequential by contract.
 // spfh_kernel: one wave per point, lane k takes list entry 1 + k; the 33 bins are integer LDS atomics (integer sums do not depend on order).
-#include <limits.h>
-#include <math.h>
-
 #include "pair_jobs.h"
+#include "wave_search.h"
 
 namespace {
 
@@ -42,86 +40,14 @@ constexpr int FP_BINS = 33;
 constexpr int NR_SWEEPS = 8;                       // cyclic Jacobi sweeps on the 3x3 covariance: always this many (it converges in 4-5)
 constexpr double FP_PI = 3.14159265358979323846;
 
-struct FCloud { int o0, n, c; bool ok; };
-
-// Cloud c of the packed array, range-checked.
-__device__ __forceinline__ FCloud fp_cloud(const int* __restrict__ off, int total_points, int c) {
-    const SgaSegment s = sga_segment(off, total_points, c);
-    return FCloud{s.o0, s.n, c, s.ok};
-}
-
-// The cloud that holds packed point i: the LAST c with offsets[c] <= i (empty clouds repeat an offset), re-checked.
-__device__ __forceinline__ FCloud fp_cloud_of_point(const int* __restrict__ off, int n_clouds, int total_points, int i) {
-    int lo = 0, hi = n_clouds - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    const FCloud C = fp_cloud(off, total_points, lo);
-    if (!C.ok || i < C.o0 || i - C.o0 >= C.n) return FCloud{0, 0, lo, false};
-    return C;
-}
-
-__device__ __forceinline__ void kl_wave_sync() {     // the wave's own LDS writes before its next LDS reads: lanes exchange entries
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ bool kl_less(double da, int ja, double db, int jb) { return da < db || (da == db && ja < jb); }
-
-// Merge the wave's S staged entries [L, L + S) into its sorted list [0, L) in place and keep the first max_nn: a rank sort in which only the
-// staged entries are walked.  An entry's rank is the number of entries below it by (d2, j): for a list entry its own position plus the
-// staged entries below it; for a staged entry the staged entries below it plus its lower bound in the sorted list (a binary search).
-// E = L + S <= 64 * K; every lane holds at most K entries in named registers.
-template <int K>
-__device__ __forceinline__ void kl_rank_sort(double* __restrict__ wd, int* __restrict__ wi, int lane, int L, int E, int max_nn) {
-    double d[K];
-    int j[K], r[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int e = lane + 64 * k;
-        const bool ok = e < E;
-        d[k] = ok ? wd[e] : INFINITY;
-        j[k] = ok ? wi[e] : INT_MAX;
-        r[k] = e < L ? e : 0;
-    }
-#pragma unroll 2                                     // 4 keeps too many compare masks alive: the scalar registers spill
-    for (int m = L; m < E; ++m) {
-        const double dm = wd[m];                     // one address for the whole wave: broadcast
-        const int jm = wi[m];
-#pragma unroll
-        for (int k = 0; k < K; ++k) r[k] += kl_less(dm, jm, d[k], j[k]) ? 1 : 0;
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        if (L >= 64 * (k + 1) || E <= 64 * k || L == 0) continue;                  // wave-uniform: no staged entry among these 64, or no list
-        const int e = lane + 64 * k;
-        int lo = 0, hi = (e >= L && e < E) ? L : 0;                                 // staged entries only; L <= 128: 8 halvings
-#pragma unroll 1
-        for (int step = 0; step < 8; ++step) {                                      // branch-free: every lane walks all steps
-            const int mid = (lo + hi) >> 1;                                         // < L whenever lo < hi; else lo == hi <= L
-            const int at = min(mid, L - 1);
-            const bool go = lo < hi, up = kl_less(wd[at], wi[at], d[k], j[k]);
-            lo = (go && up) ? mid + 1 : lo;
-            hi = (go && !up) ? mid : hi;
-        }
-        r[k] += lo;
-    }
-    kl_wave_sync();                                  // every lane has read before any lane writes
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-        if (lane + 64 * k < E && r[k] < max_nn) { wd[r[k]] = d[k]; wi[r[k]] = j[k]; }      // (d2, j) pairs are distinct: the ranks are a permutation
-    kl_wave_sync();
-}
-
+// knn_kernel's list state around kl_rank_sort (wave_search.h), its staged-entry loop unrolled by 2; refreshes tau once the list is full.
 __device__ __forceinline__ void kl_merge(double* __restrict__ wd, int* __restrict__ wi, int lane, int max_nn, int& L, int& S, double& tau,
                                          bool& full) {
     const int E = L + S;
-    kl_wave_sync();
-    if (E <= 64) kl_rank_sort<1>(wd, wi, lane, L, E, max_nn);
-    else if (E <= 128) kl_rank_sort<2>(wd, wi, lane, L, E, max_nn);
-    else kl_rank_sort<3>(wd, wi, lane, L, E, max_nn);
+    sga_wave_sync();
+    if (E <= 64) kl_rank_sort<1, 2>(wd, wi, lane, L, E, max_nn);
+    else if (E <= 128) kl_rank_sort<2, 2>(wd, wi, lane, L, E, max_nn);
+    else kl_rank_sort<3, 2>(wd, wi, lane, L, E, max_nn);
     L = min(E, max_nn);
     S = 0;
     if (E >= max_nn) { full = true; tau = wd[max_nn - 1]; }
@@ -141,7 +67,7 @@ __global__ __launch_bounds__(KL_THREADS) void knn_kernel(const double* __restric
         const int mid = (lo + hi + 1) >> 1;
         if ((off[mid] >> 2) + mid <= b) lo = mid; else hi = mid - 1;
     }
-    const FCloud C = fp_cloud(off, total_points, lo);
+    const SgaCloud C = sga_cloud(off, total_points, lo);
     if (!C.ok) return;
     const long long t = (long long)b - ((C.o0 >> 2) + lo);
     if (t < 0 || t * KL_WAVES >= C.n) return;                   // before the first cloud's tiles, or the spare id between two clouds
@@ -191,7 +117,7 @@ __global__ __launch_bounds__(KL_THREADS) void knn_kernel(const double* __restric
     }
     if (!active) return;
     if (S > 0) kl_merge(wd, wi, lane, max_nn, L, S, tau, full);
-    kl_wave_sync();
+    sga_wave_sync();
     const size_t row = ((size_t)C.o0 + q) * max_nn;
     for (int e = lane; e < max_nn; e += 64) {
         out_idx[row + e] = e < L ? wi[e] : -1;
@@ -208,7 +134,7 @@ __global__ __launch_bounds__(256) void normals_kernel(const double* __restrict__
     const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
     if (gi >= total_points) return;
     const int i = (int)gi;
-    const FCloud C = fp_cloud_of_point(off, n_clouds, total_points, i);
+    const SgaCloud C = sga_cloud_of_point(off, n_clouds, total_points, i);
     if (!C.ok) return;
     const double* P = pts + (size_t)C.o0 * 3;
     const int* row = idx + (size_t)i * max_nn;
@@ -311,10 +237,10 @@ __global__ __launch_bounds__(256) void spfh_kernel(const double* __restrict__ pt
     const long long gi = (long long)blockIdx.x * 4 + wave;
     if (gi >= total_points) return;                              // no workgroup-wide barrier below: a wave may leave on its own
     const int i = (int)gi;
-    const FCloud C = fp_cloud_of_point(off, n_clouds, total_points, i);
+    const SgaCloud C = sga_cloud_of_point(off, n_clouds, total_points, i);
     if (!C.ok) return;
     if (lane < FP_BINS) bins[wave][lane] = 0;
-    kl_wave_sync();
+    sga_wave_sync();
     const int mc = count[i];
     const int m = mc < 0 ? 0 : (mc > max_nn ? max_nn : mc);
     const double* P = pts + (size_t)C.o0 * 3;
@@ -355,7 +281,7 @@ __global__ __launch_bounds__(256) void spfh_kernel(const double* __restrict__ pt
         atomicAdd(&bins[wave][11 + fp_bin(11.0 * (f1 + 1.0) / 2.0)], 1);
         atomicAdd(&bins[wave][22 + fp_bin(11.0 * (f2 + 1.0) / 2.0)], 1);
     }
-    kl_wave_sync();
+    sga_wave_sync();
     if (lane < FP_BINS) counts[(size_t)i * FP_BINS + lane] = bins[wave][lane];
 }
 
@@ -369,7 +295,7 @@ __global__ __launch_bounds__(256) void fpfh_kernel(const int* __restrict__ count
     const long long gt = (long long)blockIdx.x * 256 + threadIdx.x;
     if (gt >= 3ll * total_points) return;
     const int i = (int)(gt / 3), g = (int)(gt % 3);
-    const FCloud C = fp_cloud_of_point(off, n_clouds, total_points, i);
+    const SgaCloud C = sga_cloud_of_point(off, n_clouds, total_points, i);
     if (!C.ok) return;
     const int mc = count[i];
     const int m = mc < 0 ? 0 : (mc > max_nn ? max_nn : mc);

@@ -18,7 +18,7 @@
 // The moved query: without transforms q' = q; with m = transforms[job] (row-major [R | t], m[0..8] = R, m[9..11] = t)
 // x' = ((m0 x + m1 y) + m2 z) + m9, y' = ((m3 x + m4 y) + m5 z) + m10, z' = ((m6 x + m7 y) + m8 z) + m11, no fma.
 //
-// The walk is vg_knn_kernel's (copied: voxel.hip is left byte for byte as it was).  The query is NOT a point of the support cloud: its
+// The walk is vg_knn_kernel's, written out here with a list of one; its helpers and the grid constants are wave_search.h's.  The query is NOT a point of the support cloud: its
 // cell coordinate t_a = floor((q'_a - o_a) / h) may be negative, beyond dims_a, huge or infinite, so it is clamped IN FP64 to
 // [0, dims_a - 1] before the conversion, and the block |k - c|inf <= R is centred at the clamped cell c.  Every (kx, ky) row of the block
 // is one contiguous range of sorted positions: lane r finds row r's range by a lower and an upper bound on sorted_keys, the wave
@@ -44,62 +44,15 @@
 // at most the real g^2 (1 + 2^-52).  Hence g g (1 - 2^-40) > bound, bound = min(r2, best d2 or +inf without one), implies computed
 // d2 > bound for every such point: it fails d2 <= r2 or loses against `best` even on a tie.  Points INSIDE the block were scanned
 // whatever cell the rounding put them in: membership is by the key, not by position.
-#include <limits.h>
-#include <math.h>
-
 #include "pair_jobs.h"
+#include "rigid_solver.h"
+#include "wave_search.h"
 
 namespace {
 
 constexpr int IG_THREADS = 256;
 constexpr int IG_WAVES = 4;                        // queries per workgroup: one wave each
-constexpr int IG_MAX_R = 16;                       // block radii 1, 2, 4, 8, 16; then the whole support
-constexpr int IG_DROPPED = 65535;                  // voxel.hip's VX_DROPPED: a valid cell coordinate is below it
-constexpr int IG_MAX_CLOUDS = 32767;               // voxel.hip's VX_MAX_CLOUDS
-constexpr double IG_EPS = 0x1p-40;
 constexpr int IC_STATE_INTS = 8;                   // sga_icp's per-job state in int32 units: done, pad, then prev fitness / rmse as fp64
-
-__device__ __forceinline__ void ig_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ bool ig_less(double da, int ja, double db, int jb) { return da < db || (da == db && ja < jb); }
-
-__device__ __forceinline__ double ig_d2(double qx, double qy, double qz, const double* __restrict__ p) {
-    const double dx = __dsub_rn(qx, p[0]), dy = __dsub_rn(qy, p[1]), dz = __dsub_rn(qz, p[2]);
-    return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-}
-
-// The lane's candidate against the lane's best: within r2, below +inf (nn_kernel's strict < against its +inf start), a NaN fails both.
-__device__ __forceinline__ void ig_offer(double r2, double d2, int j, bool live, double& bd, int& bj) {
-    if (live && d2 <= r2 && d2 < INFINITY && ig_less(d2, j, bd, bj)) { bd = d2; bj = j; }
-}
-
-// The wave's best (d2, j), to every lane.
-__device__ __forceinline__ void ig_wave_best(double& bd, int& bj) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double od = __shfl_xor(bd, o, 64);
-        const int oj = __shfl_xor(bj, o, 64);
-        if (ig_less(od, oj, bd, bj)) { bd = od; bj = oj; }
-    }
-}
-
-// first position of sk[0, n) whose key is >= key
-__device__ __forceinline__ int ig_lower_bound(const long long* __restrict__ sk, int n, long long key) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (sk[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ double ig_move(const double* __restrict__ m, int row, double x, double y, double z) {
-    return __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(m[3 * row], x), __dmul_rn(m[3 * row + 1], y)), __dmul_rn(m[3 * row + 2], z)), m[9 + row]);
-}
 
 __global__ __launch_bounds__(IG_THREADS) void icp_nn_grid_kernel(const double* __restrict__ pts, const int* __restrict__ off, int n_clouds,
                                                                  int total_points, const int* __restrict__ pairs, int n_pairs,
@@ -126,9 +79,9 @@ __global__ __launch_bounds__(IG_THREADS) void icp_nn_grid_kernel(const double* _
     if (transforms) {
         const double* m = transforms + (size_t)job * 12;
         const double x = qx, y = qy, z = qz;
-        qx = ig_move(m, 0, x, y, z);
-        qy = ig_move(m, 1, x, y, z);
-        qz = ig_move(m, 2, x, y, z);
+        qx = sga_move_point(m, 0, x, y, z);
+        qy = sga_move_point(m, 1, x, y, z);
+        qz = sga_move_point(m, 2, x, y, z);
     }
     const double* P = pts + (size_t)J.s0 * 3;
     const int* ord = order + J.s0;
@@ -138,11 +91,11 @@ __global__ __launch_bounds__(IG_THREADS) void icp_nn_grid_kernel(const double* _
 
     const double h = cell[sc];
     int kc[3], dm[3];
-    bool use_grid = status[sc] == 0 && n_clouds <= IG_MAX_CLOUDS && h > 0.0 && isfinite(h) && isfinite(qx) && isfinite(qy) && isfinite(qz);
+    bool use_grid = status[sc] == 0 && n_clouds <= GRID_MAX_CLOUDS && h > 0.0 && isfinite(h) && isfinite(qx) && isfinite(qy) && isfinite(qz);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const int d = dims[(size_t)sc * 3 + a];
-        dm[a] = d < 0 ? 0 : (d > IG_DROPPED ? IG_DROPPED : d);
+        dm[a] = d < 0 ? 0 : (d > GRID_DROPPED ? GRID_DROPPED : d);
         const double qa = a == 0 ? qx : (a == 1 ? qy : qz);
         double t = floor(__ddiv_rn(__dsub_rn(qa, origin[(size_t)sc * 3 + a]), h));
         use_grid = use_grid && dm[a] > 0 && t == t;                      // no kept point, or a NaN: the whole walk
@@ -156,7 +109,7 @@ __global__ __launch_bounds__(IG_THREADS) void icp_nn_grid_kernel(const double* _
     bool decided = false;
     if (use_grid) {
 #pragma unroll 1
-        for (int R = 1; R <= IG_MAX_R && !decided; R *= 2) {
+        for (int R = 1; R <= GRID_MAX_R && !decided; R *= 2) {
             const int x0 = max(kc[0] - R, 0), y0 = max(kc[1] - R, 0), z0 = max(kc[2] - R, 0);
             const int x1 = min(kc[0] + R, dm[0] - 1), y1 = min(kc[1] + R, dm[1] - 1), z1 = min(kc[2] + R, dm[2] - 1);
             const int ny = y1 - y0 + 1, rows = (x1 - x0 + 1) * ny;       // at most 33 x 33
@@ -166,16 +119,16 @@ __global__ __launch_bounds__(IG_THREADS) void icp_nn_grid_kernel(const double* _
                 int start = 0, len = 0;
                 if (r < rows) {
                     const long long rowkey = cloud_bits | ((long long)(x0 + r / ny) << 32) | ((long long)(y0 + r % ny) << 16);
-                    start = ig_lower_bound(sk, J.ns, rowkey | (long long)z0);
-                    len = ig_lower_bound(sk, J.ns, (rowkey | (long long)z1) + 1) - start;
+                    start = sga_lower_bound(sk, J.ns, rowkey | (long long)z0);
+                    len = sga_lower_bound(sk, J.ns, (rowkey | (long long)z1) + 1) - start;
                     if (len < 0) len = 0;
                 }
                 const int incl = wave_incl_scan(len, lane);
                 const int total_len = __shfl(incl, 63, 64);
-                ig_wave_sync();                                          // the previous batch's table has been read by every lane
+                sga_wave_sync();                                          // the previous batch's table has been read by every lane
                 rs[lane] = start;
                 rx[lane] = incl - len;
-                ig_wave_sync();
+                sga_wave_sync();
 #pragma unroll 1
                 for (int u0 = 0; u0 < total_len; u0 += 64) {
                     const bool inb = u0 + lane < total_len;
@@ -189,11 +142,11 @@ __global__ __launch_bounds__(IG_THREADS) void icp_nn_grid_kernel(const double* _
                     const int i = tin ? ord[t] : J.s0;
                     const bool jin = tin && i >= J.s0 && i - J.s0 < J.ns;
                     const int j = jin ? i - J.s0 : 0;
-                    const double d2 = ig_d2(qx, qy, qz, P + (size_t)j * 3);          // total_len > 0: the support has a row 0
-                    ig_offer(r2, d2, j, inb && jin, bd, bj);
+                    const double d2 = sga_point_d2(qx, qy, qz, P + (size_t)j * 3);          // total_len > 0: the support has a row 0
+                    sga_nn_offer(r2, d2, j, inb && jin, bd, bj);
                 }
             }
-            ig_wave_best(bd, bj);
+            sga_wave_best(bd, bj);
             if (x0 == 0 && y0 == 0 && z0 == 0 && x1 == dm[0] - 1 && y1 == dm[1] - 1 && z1 == dm[2] - 1) { decided = true; break; }   // the whole box
             // the stop rule: see the head of this file
             const double bound = fmin(r2, bd);
@@ -210,18 +163,18 @@ __global__ __launch_bounds__(IG_THREADS) void icp_nn_grid_kernel(const double* _
                     ok = ok && up == up && gap == gap;
                     gap = fmin(gap, up);
                 }
-                const double ga = __dsub_rn(gap, __dmul_rn(IG_EPS, scale));
+                const double ga = __dsub_rn(gap, __dmul_rn(GRID_EPS, scale));
                 ok = ok && ga > 0.0;                                     // a NaN is not > 0
                 g = fmin(g, ga);
             }
-            if (ok && g > 0.0 && __dmul_rn(__dmul_rn(g, g), 1.0 - IG_EPS) > bound) decided = true;
+            if (ok && g > 0.0 && __dmul_rn(__dmul_rn(g, g), 1.0 - GRID_EPS) > bound) decided = true;
         }
     }
     if (!decided) {                                                      // the whole support in original order, as nn_kernel looks at it
         bd = INFINITY;
         bj = INT_MAX;
-        for (int j = lane; j < J.ns; j += 64) ig_offer(r2, ig_d2(qx, qy, qz, P + (size_t)j * 3), j, true, bd, bj);
-        ig_wave_best(bd, bj);
+        for (int j = lane; j < J.ns; j += 64) sga_nn_offer(r2, sga_point_d2(qx, qy, qz, P + (size_t)j * 3), j, true, bd, bj);
+        sga_wave_best(bd, bj);
     }
     if (lane == 0) {
         out_d[(size_t)J.oo + qi] = squared ? bd : __dsqrt_rn(bd);
@@ -237,7 +190,7 @@ __global__ __launch_bounds__(IG_THREADS) void icp_nn_grid_kernel(const double* _
 //
 // icp_accum_kernel: a slice is IC_SLICE query rows counted from the job's first row; one workgroup per (job, slice).  Over the rows with a
 // partner (out_idx >= 0, re-checked against the support's length): slot 0 the count, slot 1 sum d2, then with a = x' - pivot (x' recomputed by
-// the search's own expression) and b = s - pivot, method 0: sum a (3), sum b (3), sum a b^T (9) -- ic_rigid_from_moments' layout --; method 1,
+// the search's own expression) and b = s - pivot, method 0: sum a (3), sum b (3), sum a b^T (9) -- rigid_from_moments' layout --; method 1,
 // with n the partner's normal, r = (a - b) . n and J = [a x n, n]: the 21 upper entries of sum J J^T (row by row), the 6 of sum J r, sum r r.
 // The fold is fixed: every lane its IC_RPL rows in ascending order, a wave butterfly, the four waves in order; icp_step_kernel adds the
 // slices in ascending order.  No atomics: two calls give the same bits, and a job in a batch gives the bits of the same job alone.
@@ -245,8 +198,6 @@ constexpr int IC_THREADS = 256;
 constexpr int IC_RPL = 4;                          // query rows per lane
 constexpr int IC_SLICE = IC_THREADS * IC_RPL;      // query rows per slice
 constexpr int IC_ACC = 32;                         // slots of a partial: 17 used by method 0, 30 by method 1
-constexpr int IC_SWEEPS = 10;                      // ransac.hip's RS_SWEEPS and RS_CONVERGED
-constexpr double IC_CONVERGED = 1e-32;
 
 struct ICState { int done, pad; double prev_fitness, prev_rmse, pad1; };
 static_assert(sizeof(ICState) == IC_STATE_INTS * 4, "icp_nn_grid_kernel reads the done flag by this stride");
@@ -285,7 +236,7 @@ __global__ __launch_bounds__(IC_THREADS) void icp_accum_kernel(const double* __r
         double a[3], b[3];
 #pragma unroll
         for (int e = 0; e < 3; ++e) {
-            a[e] = ig_move(m, e, x, y, z) - piv[e];
+            a[e] = sga_move_point(m, e, x, y, z) - piv[e];
             b[e] = S[e] - piv[e];
         }
         acc[0] += 1.0;
@@ -324,104 +275,6 @@ __global__ __launch_bounds__(IC_THREADS) void icp_accum_kernel(const double* __r
         for (int w = 1; w < IC_THREADS / 64; ++w) s += red[w][tid];
         partials[((size_t)job * slices + c) * IC_ACC + tid] = s;
     }
-}
-
-// ransac.hip's rigid_from_moments, copied (ransac.hip is left byte for byte as it was): the least-squares proper rotation + translation
-// from moments about the pivots (ps, pr), S = [sum s' (3) | sum r' (3) | sum s' r'^T (9)] over n pairs; Horn's unit quaternion by cyclic
-// Jacobi sweeps.  Returns false (out untouched) when a result is not finite.
-__device__ inline bool ic_rigid_from_moments(double n, const double* S, const double* ps, const double* pr, double* out) {
-    const double inv = 1.0 / n;
-    double ms[3], mr[3], H[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { ms[a] = S[a] * inv; mr[a] = S[3 + a] * inv; }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) H[a][b] = S[6 + 3 * a + b] - S[a] * mr[b];
-    double A[4][4], V[4][4];
-    A[0][0] = H[0][0] + H[1][1] + H[2][2];
-    A[1][1] = H[0][0] - H[1][1] - H[2][2];
-    A[2][2] = -H[0][0] + H[1][1] - H[2][2];
-    A[3][3] = -H[0][0] - H[1][1] + H[2][2];
-    A[0][1] = A[1][0] = H[1][2] - H[2][1];
-    A[0][2] = A[2][0] = H[2][0] - H[0][2];
-    A[0][3] = A[3][0] = H[0][1] - H[1][0];
-    A[1][2] = A[2][1] = H[0][1] + H[1][0];
-    A[1][3] = A[3][1] = H[2][0] + H[0][2];
-    A[2][3] = A[3][2] = H[1][2] + H[2][1];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-#pragma unroll 1
-    for (int sweep = 0; sweep < IC_SWEEPS; ++sweep) {
-        double offd = 0.0, diag = 0.0;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            diag = fma(A[p][p], A[p][p], diag);
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) offd = fma(A[p][q], A[p][q], offd);
-        }
-        if (offd <= IC_CONVERGED * diag) break;               // off-diagonal norm at rounding level of the diagonal's: nothing left to rotate
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) {
-                const double apq = A[p][q];
-                const bool rot = apq != 0.0;
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * (rot ? apq : 1.0));
-                const double tt = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(fma(theta, theta, 1.0)));     // |theta| huge: 1 / inf = 0
-                const double t = rot ? tt : 0.0;
-                const double c = 1.0 / sqrt(fma(t, t, 1.0)), s = t * c;
-                A[p][p] -= t * apq;
-                A[q][q] += t * apq;
-                A[p][q] = A[q][p] = 0.0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    if (k != p && k != q) {
-                        const double akp = A[k][p], akq = A[k][q];
-                        A[k][p] = A[p][k] = c * akp - s * akq;
-                        A[k][q] = A[q][k] = s * akp + c * akq;
-                    }
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - s * vkq;
-                    V[k][q] = s * vkp + c * vkq;
-                }
-            }
-        }
-    }
-    double lam = A[0][0], w = V[0][0], x = V[1][0], y = V[2][0], z = V[3][0];
-#pragma unroll
-    for (int i = 1; i < 4; ++i)
-        if (A[i][i] > lam) { lam = A[i][i]; w = V[0][i]; x = V[1][i]; y = V[2][i]; z = V[3][i]; }
-    const double qn = 1.0 / sqrt(w * w + x * x + y * y + z * z);
-    w *= qn; x *= qn; y *= qn; z *= qn;
-    double R[9];
-    R[0] = w * w + x * x - y * y - z * z;
-    R[1] = 2.0 * (x * y - w * z);
-    R[2] = 2.0 * (x * z + w * y);
-    R[3] = 2.0 * (x * y + w * z);
-    R[4] = w * w - x * x + y * y - z * z;
-    R[5] = 2.0 * (y * z - w * x);
-    R[6] = 2.0 * (x * z - w * y);
-    R[7] = 2.0 * (y * z + w * x);
-    R[8] = w * w - x * x - y * y + z * z;
-    double t[3];
-    bool fin = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double cx = ps[0] + ms[0], cy = ps[1] + ms[1], cz = ps[2] + ms[2];
-        t[a] = (pr[a] + mr[a]) - (R[3 * a] * cx + R[3 * a + 1] * cy + R[3 * a + 2] * cz);
-        fin = fin && isfinite(t[a]);
-    }
-#pragma unroll
-    for (int a = 0; a < 9; ++a) fin = fin && isfinite(R[a]);
-    if (!fin) return false;
-#pragma unroll
-    for (int a = 0; a < 9; ++a) out[a] = R[a];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) out[9 + a] = t[a];
-    return true;
 }
 
 // Method 1's update from the folded sums S (slots 2 .. 28): (sum J J^T) x = -sum J r by Cholesky without pivoting, every index a
@@ -529,7 +382,7 @@ __global__ __launch_bounds__(64) void icp_step_kernel(const int* __restrict__ of
             ok = false;
             stt = 1;
         } else {
-            ok = method == 0 ? ic_rigid_from_moments(cnt, S + 2, piv, piv, U) : ic_plane_update(S, piv, U);
+            ok = method == 0 ? rigid_from_moments(cnt, S + 2, piv, piv, U) : ic_plane_update(S, piv, U);
             if (!ok) stt = 2;
         }
         if (ok) {

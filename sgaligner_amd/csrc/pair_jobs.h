@@ -2,12 +2,16 @@
 // (query set, support set) pair of ids into one packed array, job p writes its nq results at out_off[p], and a support longer than `chunk`
 // is split over workgroups whose partials are folded in ascending chunk order with a strict <.  The device half re-derives every range
 // from the device arrays and does nothing on a bad one; the host half refuses a bad job list before anything is launched.  sga_segment is
-// the lookup under it: fpfh.hip calls it; sga_pair_job and ransac.hip's rs_job write it out (the call changes their kernels' code objects).
+// the lookup under it: sga_cloud calls it; sga_pair_job, sga_cloud_pair and sga_hyp_job write it out (the call changes their kernels' code
+// objects).  The hypothesis-job lookup of ransac.hip / ransac_geo.hip and the cloud lookups of fpfh.hip / voxel.hip stand here too, once.
 #pragma once
 #include "packed.h"
 
 struct SgaSegment { int o0, n; bool ok; };
 struct SgaPairJob { int q0, nq, s0, ns, oo; bool ok; };
+struct SgaCloudPair { int q0, nq, s0, ns, sc; bool ok; };
+struct SgaHypJob { int o0, n, h0, nh; bool ok; };
+struct SgaCloud { int o0, n, c; bool ok; };
 
 // Segment i of a packed array, [off[i], off[i + 1]), range-checked against `total`: a bad offset gives {0, 0, false}.
 __device__ __forceinline__ SgaSegment sga_segment(const int* __restrict__ off, int total, int i) {
@@ -28,6 +32,43 @@ __device__ __forceinline__ SgaPairJob sga_pair_job(const int* __restrict__ off, 
     if (q0 < 0 || q1 < q0 || q1 > total_rows || s0 < 0 || s1 < s0 || s1 > total_rows) return none;
     if (oo < 0 || oo > total_queries || q1 - q0 > total_queries - oo) return none;
     return SgaPairJob{q0, q1 - q0, s0, s1 - s0, oo, true};
+}
+
+// sga_pair_job without the output range: the job id, the two cloud ids and both segments, read from the device arrays and range-checked.
+__device__ __forceinline__ SgaCloudPair sga_cloud_pair(const int* __restrict__ off, int n_clouds, int total_points, const int* __restrict__ pairs,
+                                                       int n_pairs, int job) {
+    const SgaCloudPair none{0, 0, 0, 0, 0, false};
+    if (job < 0 || job >= n_pairs) return none;
+    const int qc = pairs[2 * job], sc = pairs[2 * job + 1];
+    if (qc < 0 || qc >= n_clouds || sc < 0 || sc >= n_clouds) return none;
+    const int q0 = off[qc], q1 = off[qc + 1], s0 = off[sc], s1 = off[sc + 1];
+    if (q0 < 0 || q1 < q0 || q1 > total_points || s0 < 0 || s1 < s0 || s1 > total_points) return none;
+    return SgaCloudPair{q0, q1 - q0, s0, s1 - s0, sc, true};
+}
+
+// Rows and hypotheses of RANSAC job `job`, range-checked (two sga_segment lookups, written out): a bad offset makes the caller do nothing.
+__device__ __forceinline__ SgaHypJob sga_hyp_job(const int* __restrict__ off, int total_rows, const int* __restrict__ hoff, int total_hyp, int job) {
+    const int o0 = off[job], o1 = off[job + 1], h0 = hoff[job], h1 = hoff[job + 1];
+    if (o0 < 0 || o1 < o0 || o1 > total_rows || h0 < 0 || h1 < h0 || h1 > total_hyp) return SgaHypJob{0, 0, 0, 0, false};
+    return SgaHypJob{o0, o1 - o0, h0, h1 - h0, true};
+}
+
+// Cloud c of the packed array, range-checked.
+__device__ __forceinline__ SgaCloud sga_cloud(const int* __restrict__ off, int total_points, int c) {
+    const SgaSegment s = sga_segment(off, total_points, c);
+    return SgaCloud{s.o0, s.n, c, s.ok};
+}
+
+// The cloud that holds packed row i: the LAST c with offsets[c] <= i (empty clouds repeat an offset), re-checked.
+__device__ __forceinline__ SgaCloud sga_cloud_of_point(const int* __restrict__ off, int n_clouds, int total_points, int i) {
+    int lo = 0, hi = n_clouds - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    const SgaCloud C = sga_cloud(off, total_points, lo);
+    if (!C.ok || i < C.o0 || i - C.o0 >= C.n) return SgaCloud{0, 0, lo, false};
+    return C;
 }
 
 // Passes over a support of ns rows in chunks of `chunk` (>= 1).  An empty support still takes one pass: the one that writes "no neighbour".

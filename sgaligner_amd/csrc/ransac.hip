@@ -25,6 +25,7 @@
 #include <math.h>
 
 #include "pair_jobs.h"
+#include "rigid_solver.h"
 
 namespace {
 
@@ -34,8 +35,6 @@ constexpr int RS_HTILE = RS_THREADS * RS_HPL;      // hypotheses per workgroup
 constexpr int RS_STILE = 256;                      // rows per LDS tile (6 x 256 x 8 B = 12 KiB)
 constexpr int RS_RPL = 4;                          // rows per lane in the refit / mask kernels
 constexpr int RS_RCHUNK = RS_THREADS * RS_RPL;     // rows per workgroup there
-constexpr int RS_SWEEPS = 10;                      // at most this many cyclic Jacobi sweeps on the 4x4 quaternion matrix (it converges in 5-6)
-constexpr double RS_CONVERGED = 1e-32;             // ... stopping once |off-diagonal|^2 <= this x |diagonal|^2: a function of the matrix alone
 constexpr int RS_MAX_ROUNDS = 64;
 
 struct RSState {            // per job, in the workspace
@@ -43,15 +42,6 @@ struct RSState {            // per job, in the workspace
     double cand[12];        // the model the next accum pass measures
     int cur_count, stopped, pad0, pad1;
 };
-
-struct RSJob { int o0, n, h0, nh; bool ok; };
-
-// Rows and hypotheses of job `job`, range-checked (two sga_segment lookups of pair_jobs.h, written out): a bad offset makes the caller do nothing.
-__device__ __forceinline__ RSJob rs_job(const int* __restrict__ off, int total_rows, const int* __restrict__ hoff, int total_hyp, int job) {
-    const int o0 = off[job], o1 = off[job + 1], h0 = hoff[job], h1 = hoff[job + 1];
-    if (o0 < 0 || o1 < o0 || o1 > total_rows || h0 < 0 || h1 < h0 || h1 > total_hyp) return RSJob{0, 0, 0, 0, false};
-    return RSJob{o0, o1 - o0, h0, h1 - h0, true};
-}
 
 // |R s + t - r|^2 <= thr2, every operation explicit.  A NaN model fails the test.
 __host__ __device__ __forceinline__ bool ransac_inlier(const double* m, double sx, double sy, double sz, double rx, double ry, double rz,
@@ -62,111 +52,12 @@ __host__ __device__ __forceinline__ bool ransac_inlier(const double* m, double s
     return fma(dz, dz, fma(dy, dy, dx * dx)) <= thr2;
 }
 
-// Least-squares rigid transform (proper rotation) from moments taken about a pivot (ps, pr): S = [sum s' (3) | sum r' (3) | sum s' r'^T (9)],
-// s' = s - ps, r' = r - pr, over n pairs.  Horn's unit quaternion: the eigenvector of the largest eigenvalue of the symmetric 4x4 matrix
-// built from the centred cross-covariance, by cyclic Jacobi sweeps.  All array indices are compile-time constants
-// after unrolling, so everything stays in registers.  Returns false (out untouched) when a result is not finite.
-__host__ __device__ inline bool rigid_from_moments(double n, const double* S, const double* ps, const double* pr, double* out) {
-    const double inv = 1.0 / n;
-    double ms[3], mr[3], H[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { ms[a] = S[a] * inv; mr[a] = S[3 + a] * inv; }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) H[a][b] = S[6 + 3 * a + b] - S[a] * mr[b];
-    double A[4][4], V[4][4];
-    A[0][0] = H[0][0] + H[1][1] + H[2][2];
-    A[1][1] = H[0][0] - H[1][1] - H[2][2];
-    A[2][2] = -H[0][0] + H[1][1] - H[2][2];
-    A[3][3] = -H[0][0] - H[1][1] + H[2][2];
-    A[0][1] = A[1][0] = H[1][2] - H[2][1];
-    A[0][2] = A[2][0] = H[2][0] - H[0][2];
-    A[0][3] = A[3][0] = H[0][1] - H[1][0];
-    A[1][2] = A[2][1] = H[0][1] + H[1][0];
-    A[1][3] = A[3][1] = H[2][0] + H[0][2];
-    A[2][3] = A[3][2] = H[1][2] + H[2][1];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-#pragma unroll 1
-    for (int sweep = 0; sweep < RS_SWEEPS; ++sweep) {
-        double offd = 0.0, diag = 0.0;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            diag = fma(A[p][p], A[p][p], diag);
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) offd = fma(A[p][q], A[p][q], offd);
-        }
-        if (offd <= RS_CONVERGED * diag) break;               // off-diagonal norm at rounding level of the diagonal's: nothing left to rotate
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) {
-                const double apq = A[p][q];
-                const bool rot = apq != 0.0;
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * (rot ? apq : 1.0));
-                const double tt = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(fma(theta, theta, 1.0)));     // |theta| huge: 1 / inf = 0
-                const double t = rot ? tt : 0.0;
-                const double c = 1.0 / sqrt(fma(t, t, 1.0)), s = t * c;
-                A[p][p] -= t * apq;
-                A[q][q] += t * apq;
-                A[p][q] = A[q][p] = 0.0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    if (k != p && k != q) {
-                        const double akp = A[k][p], akq = A[k][q];
-                        A[k][p] = A[p][k] = c * akp - s * akq;
-                        A[k][q] = A[q][k] = s * akp + c * akq;
-                    }
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - s * vkq;
-                    V[k][q] = s * vkp + c * vkq;
-                }
-            }
-        }
-    }
-    double lam = A[0][0], w = V[0][0], x = V[1][0], y = V[2][0], z = V[3][0];
-#pragma unroll
-    for (int i = 1; i < 4; ++i)
-        if (A[i][i] > lam) { lam = A[i][i]; w = V[0][i]; x = V[1][i]; y = V[2][i]; z = V[3][i]; }
-    const double qn = 1.0 / sqrt(w * w + x * x + y * y + z * z);
-    w *= qn; x *= qn; y *= qn; z *= qn;
-    double R[9];
-    R[0] = w * w + x * x - y * y - z * z;
-    R[1] = 2.0 * (x * y - w * z);
-    R[2] = 2.0 * (x * z + w * y);
-    R[3] = 2.0 * (x * y + w * z);
-    R[4] = w * w - x * x + y * y - z * z;
-    R[5] = 2.0 * (y * z - w * x);
-    R[6] = 2.0 * (x * z - w * y);
-    R[7] = 2.0 * (y * z + w * x);
-    R[8] = w * w - x * x - y * y + z * z;
-    double t[3];
-    bool fin = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double cx = ps[0] + ms[0], cy = ps[1] + ms[1], cz = ps[2] + ms[2];
-        t[a] = (pr[a] + mr[a]) - (R[3 * a] * cx + R[3 * a + 1] * cy + R[3 * a + 2] * cz);
-        fin = fin && isfinite(t[a]);
-    }
-#pragma unroll
-    for (int a = 0; a < 9; ++a) fin = fin && isfinite(R[a]);
-    if (!fin) return false;
-#pragma unroll
-    for (int a = 0; a < 9; ++a) out[a] = R[a];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) out[9 + a] = t[a];
-    return true;
-}
-
 __global__ __launch_bounds__(RS_THREADS) void ransac_hyp_kernel(const double* __restrict__ corr, const int* __restrict__ off, int total_rows,
                                                                 const int* __restrict__ samples, const int* __restrict__ hoff, int total_hyp,
                                                                 int g_tiles, double* __restrict__ model) {
     const int job = blockIdx.x / g_tiles;
     const int h = (blockIdx.x % g_tiles) * RS_THREADS + threadIdx.x;
-    const RSJob J = rs_job(off, total_rows, hoff, total_hyp, job);
+    const SgaHypJob J = sga_hyp_job(off, total_rows, hoff, total_hyp, job);
     if (!J.ok || h >= J.nh) return;
     const size_t g = (size_t)J.h0 + h;
     const int ia = samples[3 * g], ib = samples[3 * g + 1], ic = samples[3 * g + 2];
@@ -210,7 +101,7 @@ __global__ __launch_bounds__(RS_THREADS) void ransac_score_kernel(const double* 
     const int ht = b % h_tiles;
     b /= h_tiles;
     const int c = b % n_chunks, job = b / n_chunks;
-    const RSJob J = rs_job(off, total_rows, hoff, total_hyp, job);
+    const SgaHypJob J = sga_hyp_job(off, total_rows, hoff, total_hyp, job);
     if (!J.ok) return;
     const int hb = ht * RS_HTILE;
     if (hb >= J.nh) return;
@@ -253,7 +144,7 @@ __global__ __launch_bounds__(RS_THREADS) void ransac_fold_kernel(const int* __re
                                                                  const int* __restrict__ ws_cnt, int* __restrict__ hyp_count) {
     const int job = blockIdx.x / g_tiles;
     const int h = (blockIdx.x % g_tiles) * RS_THREADS + threadIdx.x;
-    const RSJob J = rs_job(off, total_rows, hoff, total_hyp, job);
+    const SgaHypJob J = sga_hyp_job(off, total_rows, hoff, total_hyp, job);
     if (!J.ok || h >= J.nh) return;
     const int my_chunks = J.n <= chunk ? 1 : (int)min((long long)n_chunks, ((long long)J.n + chunk - 1) / chunk);   // never past what was written
     int s = 0;
@@ -268,7 +159,7 @@ __global__ __launch_bounds__(RS_THREADS) void ransac_select_kernel(const int* __
                                                                    int* __restrict__ best_hyp, int* __restrict__ status) {
     __shared__ int s_cnt[RS_THREADS], s_idx[RS_THREADS];
     const int tid = threadIdx.x, job = blockIdx.x;
-    const RSJob J = rs_job(off, total_rows, hoff, total_hyp, job);
+    const SgaHypJob J = sga_hyp_job(off, total_rows, hoff, total_hyp, job);
     int bc = -1, bi = 0x7fffffff;
     if (J.ok)
         for (int h = tid; h < J.nh; h += RS_THREADS) {
@@ -306,7 +197,7 @@ __global__ __launch_bounds__(RS_THREADS) void ransac_accum_kernel(const double* 
                                                                   double* __restrict__ partials) {
     __shared__ double red[RS_THREADS / 64][16];
     const int tid = threadIdx.x, job = blockIdx.x / r_chunks, c = blockIdx.x % r_chunks;
-    const RSJob J = rs_job(off, total_rows, hoff, total_hyp, job);
+    const SgaHypJob J = sga_hyp_job(off, total_rows, hoff, total_hyp, job);
     if (!J.ok || state[job].stopped) return;
     const int c0 = c * RS_RCHUNK;                              // c < r_chunks <= ceil(max_rows / RS_RCHUNK): no overflow
     if (c0 >= J.n) return;
@@ -356,7 +247,7 @@ __global__ __launch_bounds__(64) void ransac_step_kernel(const double* __restric
                                                          int* __restrict__ inlier_count) {
     __shared__ double S[16];
     const int tid = threadIdx.x, job = blockIdx.x;
-    const RSJob J = rs_job(off, total_rows, hoff, total_hyp, job);
+    const SgaHypJob J = sga_hyp_job(off, total_rows, hoff, total_hyp, job);
     RSState* st = state + job;
     const bool live = J.ok && !st->stopped;                    // uniform over the workgroup
     if (live && tid < 16) {
@@ -405,7 +296,7 @@ __global__ __launch_bounds__(RS_THREADS) void ransac_mask_kernel(const double* _
                                                                  const RSState* __restrict__ state, const int* __restrict__ status,
                                                                  double thr2, int r_chunks, unsigned char* __restrict__ mask) {
     const int tid = threadIdx.x, job = blockIdx.x / r_chunks, c = blockIdx.x % r_chunks;
-    const RSJob J = rs_job(off, total_rows, hoff, total_hyp, job);
+    const SgaHypJob J = sga_hyp_job(off, total_rows, hoff, total_hyp, job);
     if (!J.ok) return;
     const int c0 = c * RS_RCHUNK;
     if (c0 >= J.n) return;

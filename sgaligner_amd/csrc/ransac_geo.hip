@@ -3,7 +3,7 @@
 // correspondences it was drawn from.  The contract written in include/sgaligner_hip.h IS the definition; tests/ransac_geo_ref.py restates
 // it in numpy.  Two entries:
 //
-//   sga_ransac_models          one lane per hypothesis: ransac.hip's three-point model (the same solver, sweeps and validity rules) as an
+//   sga_ransac_models          one lane per hypothesis: ransac.hip's three-point model (rigid_solver.h's solver, the same validity rules) as an
 //                              output of its own, [total_hyp, 12] row-major [R | t], with a valid flag and the largest residual of the three
 //                              sampled rows (Open3D's distance checker reads it).  The residual is taken with the search's arithmetic below,
 //                              so numpy recomputes it bit for bit from the downloaded model.
@@ -12,11 +12,11 @@
 //                              geo_score_kernel searches and folds a slice; geo_fold_kernel adds the slices.
 //
 // Every fp64 operation is rounded on its own (explicit __d*_rn forms in the search, -ffp-contract=off for this file); the solver's explicit
-// fma() calls are ransac.hip's.  No atomics: both entries are pure functions of their inputs.  Every id, offset and index read from a device
+// fma() calls are rigid_solver.h's.  No atomics: both entries are pure functions of their inputs.  Every id, offset and index read from a device
 // array is re-checked: a bad one makes the workgroup do nothing (or skip that candidate), never read or write out of bounds.
 //
-// THE SEARCH is icp_nn_grid_kernel's, copied (icp.hip is left byte for byte as it was): one wave per query, the clamp of the cell
-// coordinate in fp64, the blocks |k - c|inf <= R for R = 1, 2, 4, 8, 16 around the clamped cell, every (kx, ky) row one range of sorted
+// THE SEARCH is icp_nn_grid_kernel's walk, written out again (gs_search; its helpers are wave_search.h's): one wave per query, the clamp of
+// the cell coordinate in fp64, the blocks |k - c|inf <= R for R = 1, 2, 4, 8, 16 around the clamped cell, every (kx, ky) row one range of sorted
 // positions found by two binary searches, the stop rule with its 2^-40 margins, and the walk of the whole support for a query that stays
 // undecided, has a non-finite moved coordinate or meets a support without a grid.  The proof that the stop rule is exact, also for a centre
 // outside the box, stands at the head of icp.hip and is not repeated; nothing in it depends on what is done with the result.
@@ -28,129 +28,14 @@
 //     fold over slices c ascending ( fold over waves w = 0..3 ( fold over the wave's rows ascending ) )
 // with every fold starting at +0.0: the same bits in two calls, for a job alone or in a batch, and for every cell size -- the grid decides
 // how much of the support is looked at, never what comes out.
-#include <limits.h>
-#include <math.h>
-
 #include "pair_jobs.h"
+#include "rigid_solver.h"
+#include "wave_search.h"
 
 namespace {
 
 // ---- models ----------------------------------------------------------------------------------------------------------------------------------
 constexpr int GM_THREADS = 256;
-constexpr int GM_SWEEPS = 10;                      // ransac.hip's RS_SWEEPS and RS_CONVERGED
-constexpr double GM_CONVERGED = 1e-32;
-
-struct GMJob { int o0, n, h0, nh; bool ok; };
-
-// ransac.hip's rs_job: rows and hypotheses of job `job`, range-checked; a bad offset makes the caller do nothing.
-__device__ __forceinline__ GMJob gm_job(const int* __restrict__ off, int total_rows, const int* __restrict__ hoff, int total_hyp, int job) {
-    const int o0 = off[job], o1 = off[job + 1], h0 = hoff[job], h1 = hoff[job + 1];
-    if (o0 < 0 || o1 < o0 || o1 > total_rows || h0 < 0 || h1 < h0 || h1 > total_hyp) return GMJob{0, 0, 0, 0, false};
-    return GMJob{o0, o1 - o0, h0, h1 - h0, true};
-}
-
-// ransac.hip's rigid_from_moments, copied (ransac.hip is left byte for byte as it was): the least-squares proper rotation + translation
-// from moments about the pivots (ps, pr), S = [sum s' (3) | sum r' (3) | sum s' r'^T (9)] over n pairs; Horn's unit quaternion by cyclic
-// Jacobi sweeps.  Returns false (out untouched) when a result is not finite.
-__device__ inline bool gm_rigid_from_moments(double n, const double* S, const double* ps, const double* pr, double* out) {
-    const double inv = 1.0 / n;
-    double ms[3], mr[3], H[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { ms[a] = S[a] * inv; mr[a] = S[3 + a] * inv; }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) H[a][b] = S[6 + 3 * a + b] - S[a] * mr[b];
-    double A[4][4], V[4][4];
-    A[0][0] = H[0][0] + H[1][1] + H[2][2];
-    A[1][1] = H[0][0] - H[1][1] - H[2][2];
-    A[2][2] = -H[0][0] + H[1][1] - H[2][2];
-    A[3][3] = -H[0][0] - H[1][1] + H[2][2];
-    A[0][1] = A[1][0] = H[1][2] - H[2][1];
-    A[0][2] = A[2][0] = H[2][0] - H[0][2];
-    A[0][3] = A[3][0] = H[0][1] - H[1][0];
-    A[1][2] = A[2][1] = H[0][1] + H[1][0];
-    A[1][3] = A[3][1] = H[2][0] + H[0][2];
-    A[2][3] = A[3][2] = H[1][2] + H[2][1];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-#pragma unroll 1
-    for (int sweep = 0; sweep < GM_SWEEPS; ++sweep) {
-        double offd = 0.0, diag = 0.0;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            diag = fma(A[p][p], A[p][p], diag);
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) offd = fma(A[p][q], A[p][q], offd);
-        }
-        if (offd <= GM_CONVERGED * diag) break;               // off-diagonal norm at rounding level of the diagonal's: nothing left to rotate
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-#pragma unroll
-            for (int q = p + 1; q < 4; ++q) {
-                const double apq = A[p][q];
-                const bool rot = apq != 0.0;
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * (rot ? apq : 1.0));
-                const double tt = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(fma(theta, theta, 1.0)));     // |theta| huge: 1 / inf = 0
-                const double t = rot ? tt : 0.0;
-                const double c = 1.0 / sqrt(fma(t, t, 1.0)), s = t * c;
-                A[p][p] -= t * apq;
-                A[q][q] += t * apq;
-                A[p][q] = A[q][p] = 0.0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    if (k != p && k != q) {
-                        const double akp = A[k][p], akq = A[k][q];
-                        A[k][p] = A[p][k] = c * akp - s * akq;
-                        A[k][q] = A[q][k] = s * akp + c * akq;
-                    }
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - s * vkq;
-                    V[k][q] = s * vkp + c * vkq;
-                }
-            }
-        }
-    }
-    double lam = A[0][0], w = V[0][0], x = V[1][0], y = V[2][0], z = V[3][0];
-#pragma unroll
-    for (int i = 1; i < 4; ++i)
-        if (A[i][i] > lam) { lam = A[i][i]; w = V[0][i]; x = V[1][i]; y = V[2][i]; z = V[3][i]; }
-    const double qn = 1.0 / sqrt(w * w + x * x + y * y + z * z);
-    w *= qn; x *= qn; y *= qn; z *= qn;
-    double R[9];
-    R[0] = w * w + x * x - y * y - z * z;
-    R[1] = 2.0 * (x * y - w * z);
-    R[2] = 2.0 * (x * z + w * y);
-    R[3] = 2.0 * (x * y + w * z);
-    R[4] = w * w - x * x + y * y - z * z;
-    R[5] = 2.0 * (y * z - w * x);
-    R[6] = 2.0 * (x * z - w * y);
-    R[7] = 2.0 * (y * z + w * x);
-    R[8] = w * w - x * x - y * y + z * z;
-    double t[3];
-    bool fin = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double cx = ps[0] + ms[0], cy = ps[1] + ms[1], cz = ps[2] + ms[2];
-        t[a] = (pr[a] + mr[a]) - (R[3 * a] * cx + R[3 * a + 1] * cy + R[3 * a + 2] * cz);
-        fin = fin && isfinite(t[a]);
-    }
-#pragma unroll
-    for (int a = 0; a < 9; ++a) fin = fin && isfinite(R[a]);
-    if (!fin) return false;
-#pragma unroll
-    for (int a = 0; a < 9; ++a) out[a] = R[a];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) out[9 + a] = t[a];
-    return true;
-}
-
-// The search's move of a point, one coordinate: ((m[3 row] x + m[3 row + 1] y) + m[3 row + 2] z) + m[9 + row], no fma.
-__device__ __forceinline__ double gs_move(const double* __restrict__ m, int row, double x, double y, double z) {
-    return __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(m[3 * row], x), __dmul_rn(m[3 * row + 1], y)), __dmul_rn(m[3 * row + 2], z)), m[9 + row]);
-}
 
 // A value that every lane of the wave holds alike, as a scalar: the compiler then keeps it and what is derived from it in SGPRs.
 __device__ __forceinline__ double gs_uniform(double v) {
@@ -159,11 +44,11 @@ __device__ __forceinline__ double gs_uniform(double v) {
     return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
 }
 
-// |R s + t - r|^2 of one corr row under model m, in the search's arithmetic: the move above, then (dx dx + dy dy) + dz dz.
+// |R s + t - r|^2 of one corr row under model m, in the search's arithmetic: sga_move_point, then (dx dx + dy dy) + dz dz.
 __device__ __forceinline__ double gm_resid2(const double* m, const double* row) {
-    const double dx = __dsub_rn(gs_move(m, 0, row[0], row[1], row[2]), row[3]);
-    const double dy = __dsub_rn(gs_move(m, 1, row[0], row[1], row[2]), row[4]);
-    const double dz = __dsub_rn(gs_move(m, 2, row[0], row[1], row[2]), row[5]);
+    const double dx = __dsub_rn(sga_move_point(m, 0, row[0], row[1], row[2]), row[3]);
+    const double dy = __dsub_rn(sga_move_point(m, 1, row[0], row[1], row[2]), row[4]);
+    const double dz = __dsub_rn(sga_move_point(m, 2, row[0], row[1], row[2]), row[5]);
     return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
 }
 
@@ -173,7 +58,7 @@ __global__ __launch_bounds__(GM_THREADS) void geo_models_kernel(const double* __
                                                                 double* __restrict__ resid2) {
     const int job = blockIdx.x / g_tiles;
     const int h = (blockIdx.x % g_tiles) * GM_THREADS + threadIdx.x;
-    const GMJob J = gm_job(off, total_rows, hoff, total_hyp, job);
+    const SgaHypJob J = sga_hyp_job(off, total_rows, hoff, total_hyp, job);
     if (!J.ok || h >= J.nh) return;
     const size_t g = (size_t)J.h0 + h;
     const int ia = samples[3 * g], ib = samples[3 * g + 1], ic = samples[3 * g + 2];
@@ -205,7 +90,7 @@ __global__ __launch_bounds__(GM_THREADS) void geo_models_kernel(const double* __
 #pragma unroll
                 for (int b = 0; b < 3; ++b) S[6 + 3 * a + b] = fma(d[a], d[3 + b], S[6 + 3 * a + b]);
         }
-        ok = gm_rigid_from_moments(3.0, S, pa, pa + 3, out);
+        ok = rigid_from_moments(3.0, S, pa, pa + 3, out);
         if (ok) {
             const double ra = gm_resid2(out, pa), rb = gm_resid2(out, pb), rc = gm_resid2(out, pc);
             ok = ra == ra && rb == rb && rc == rc;          // a NaN residual (an overflow on the way): no model
@@ -227,63 +112,8 @@ __global__ __launch_bounds__(GM_THREADS) void geo_models_kernel(const double* __
 constexpr int GS_THREADS = 256;
 constexpr int GS_WAVES = 4;
 constexpr int GS_SLICE = 1024;                     // query rows per workgroup, counted from the job's first row (icp.hip's IC_SLICE)
-constexpr int GS_MAX_R = 16;                       // block radii 1, 2, 4, 8, 16; then the whole support
-constexpr int GS_DROPPED = 65535;                  // voxel.hip's VX_DROPPED: a valid cell coordinate is below it
-constexpr int GS_MAX_CLOUDS = 32767;               // voxel.hip's VX_MAX_CLOUDS
-constexpr double GS_EPS = 0x1p-40;
 
 struct GSPartial { double sum; long long count; };
-struct GSJob { int q0, nq, s0, ns, sc; bool ok; };
-
-// sga_pair_job without the output range: the job id, the two cloud ids and both segments, read from the device arrays and range-checked.
-__device__ __forceinline__ GSJob gs_job(const int* __restrict__ off, int n_clouds, int total_points, const int* __restrict__ pairs, int n_pairs,
-                                        int job) {
-    const GSJob none{0, 0, 0, 0, 0, false};
-    if (job < 0 || job >= n_pairs) return none;
-    const int qc = pairs[2 * job], sc = pairs[2 * job + 1];
-    if (qc < 0 || qc >= n_clouds || sc < 0 || sc >= n_clouds) return none;
-    const int q0 = off[qc], q1 = off[qc + 1], s0 = off[sc], s1 = off[sc + 1];
-    if (q0 < 0 || q1 < q0 || q1 > total_points || s0 < 0 || s1 < s0 || s1 > total_points) return none;
-    return GSJob{q0, q1 - q0, s0, s1 - s0, sc, true};
-}
-
-__device__ __forceinline__ void gs_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ bool gs_less(double da, int ja, double db, int jb) { return da < db || (da == db && ja < jb); }
-
-__device__ __forceinline__ double gs_d2(double qx, double qy, double qz, const double* __restrict__ p) {
-    const double dx = __dsub_rn(qx, p[0]), dy = __dsub_rn(qy, p[1]), dz = __dsub_rn(qz, p[2]);
-    return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-}
-
-// The lane's candidate against the lane's best: within r2, below +inf, a NaN fails both.
-__device__ __forceinline__ void gs_offer(double r2, double d2, int j, bool live, double& bd, int& bj) {
-    if (live && d2 <= r2 && d2 < INFINITY && gs_less(d2, j, bd, bj)) { bd = d2; bj = j; }
-}
-
-// The wave's best (d2, j), to every lane.
-__device__ __forceinline__ void gs_wave_best(double& bd, int& bj) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double od = __shfl_xor(bd, o, 64);
-        const int oj = __shfl_xor(bj, o, 64);
-        if (gs_less(od, oj, bd, bj)) { bd = od; bj = oj; }
-    }
-}
-
-// first position of sk[0, n) whose key is >= key
-__device__ __forceinline__ int gs_lower_bound(const long long* __restrict__ sk, int n, long long key) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (sk[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 // What the wave needs to know about the job's support, read once.
 struct GSSupport {
@@ -322,7 +152,7 @@ __device__ __forceinline__ void gs_search(const GSSupport& U, double qx, double 
     bool decided = false;
     if (use_grid) {
 #pragma unroll 1
-        for (int R = 1; R <= GS_MAX_R && !decided; R *= 2) {
+        for (int R = 1; R <= GRID_MAX_R && !decided; R *= 2) {
             const int x0 = max(kc[0] - R, 0), y0 = max(kc[1] - R, 0), z0 = max(kc[2] - R, 0);
             const int x1 = min(kc[0] + R, U.dm[0] - 1), y1 = min(kc[1] + R, U.dm[1] - 1), z1 = min(kc[2] + R, U.dm[2] - 1);
             const int ny = y1 - y0 + 1, rows = (x1 - x0 + 1) * ny;       // at most 33 x 33
@@ -332,16 +162,16 @@ __device__ __forceinline__ void gs_search(const GSSupport& U, double qx, double 
                 int start = 0, len = 0;
                 if (r < rows) {
                     const long long rowkey = cloud_bits | ((long long)(x0 + r / ny) << 32) | ((long long)(y0 + r % ny) << 16);
-                    start = gs_lower_bound(U.sk, U.ns, rowkey | (long long)z0);
-                    len = gs_lower_bound(U.sk, U.ns, (rowkey | (long long)z1) + 1) - start;
+                    start = sga_lower_bound(U.sk, U.ns, rowkey | (long long)z0);
+                    len = sga_lower_bound(U.sk, U.ns, (rowkey | (long long)z1) + 1) - start;
                     if (len < 0) len = 0;
                 }
                 const int incl = wave_incl_scan(len, lane);
                 const int total_len = __shfl(incl, 63, 64);
-                gs_wave_sync();                                          // the previous batch's table has been read by every lane
+                sga_wave_sync();                                          // the previous batch's table has been read by every lane
                 rs[lane] = start;
                 rx[lane] = incl - len;
-                gs_wave_sync();
+                sga_wave_sync();
 #pragma unroll 1
                 for (int u0 = 0; u0 < total_len; u0 += 64) {
                     const bool inb = u0 + lane < total_len;
@@ -355,11 +185,11 @@ __device__ __forceinline__ void gs_search(const GSSupport& U, double qx, double 
                     const int i = tin ? U.ord[t] : U.s0;
                     const bool jin = tin && i >= U.s0 && i - U.s0 < U.ns;
                     const int j = jin ? i - U.s0 : 0;
-                    const double d2 = gs_d2(qx, qy, qz, U.P + (size_t)j * 3);        // total_len > 0: the support has a row 0
-                    gs_offer(r2, d2, j, inb && jin, bd, bj);
+                    const double d2 = sga_point_d2(qx, qy, qz, U.P + (size_t)j * 3);        // total_len > 0: the support has a row 0
+                    sga_nn_offer(r2, d2, j, inb && jin, bd, bj);
                 }
             }
-            gs_wave_best(bd, bj);
+            sga_wave_best(bd, bj);
             if (x0 == 0 && y0 == 0 && z0 == 0 && x1 == U.dm[0] - 1 && y1 == U.dm[1] - 1 && z1 == U.dm[2] - 1) { decided = true; break; }   // the whole box
             // the stop rule: see the head of icp.hip
             const double bound = fmin(r2, bd), h = U.geo[3];
@@ -376,18 +206,18 @@ __device__ __forceinline__ void gs_search(const GSSupport& U, double qx, double 
                     ok = ok && up == up && gap == gap;
                     gap = fmin(gap, up);
                 }
-                const double ga = __dsub_rn(gap, __dmul_rn(GS_EPS, scale));
+                const double ga = __dsub_rn(gap, __dmul_rn(GRID_EPS, scale));
                 ok = ok && ga > 0.0;                                     // a NaN is not > 0
                 g = fmin(g, ga);
             }
-            if (gs_uniform(ok && g > 0.0 && __dmul_rn(__dmul_rn(g, g), 1.0 - GS_EPS) > bound)) decided = true;
+            if (gs_uniform(ok && g > 0.0 && __dmul_rn(__dmul_rn(g, g), 1.0 - GRID_EPS) > bound)) decided = true;
         }
     }
     if (!decided) {                                                      // the whole support in original order, as nn_kernel looks at it
         bd = INFINITY;
         bj = INT_MAX;
-        for (int j = lane; j < U.ns; j += 64) gs_offer(r2, gs_d2(qx, qy, qz, U.P + (size_t)j * 3), j, true, bd, bj);
-        gs_wave_best(bd, bj);
+        for (int j = lane; j < U.ns; j += 64) sga_nn_offer(r2, sga_point_d2(qx, qy, qz, U.P + (size_t)j * 3), j, true, bd, bj);
+        sga_wave_best(bd, bj);
     }
 }
 
@@ -403,7 +233,7 @@ __global__ __launch_bounds__(GS_THREADS) void geo_score_kernel(const double* __r
     __shared__ int red_cnt[GS_WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int job = blockIdx.x / slices, c = blockIdx.x % slices;
-    const GSJob J = gs_job(off, n_clouds, total_points, pairs, n_pairs, job);
+    const SgaCloudPair J = sga_cloud_pair(off, n_clouds, total_points, pairs, n_pairs, job);
     if (!J.ok) return;                                                   // every exit before the barrier is uniform over the workgroup
     if (live && live[job] == 0) return;
     const int c0 = c * GS_SLICE;                                         // c < slices <= ceil(max_queries / GS_SLICE): no overflow
@@ -426,11 +256,11 @@ __global__ __launch_bounds__(GS_THREADS) void geo_score_kernel(const double* __r
     U.geo = s_geo;
     U.sc = J.sc;
     const double h = cell[J.sc];
-    U.grid = status[J.sc] == 0 && n_clouds <= GS_MAX_CLOUDS && h > 0.0 && isfinite(h);
+    U.grid = status[J.sc] == 0 && n_clouds <= GRID_MAX_CLOUDS && h > 0.0 && isfinite(h);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const int d = dims[(size_t)J.sc * 3 + a];
-        U.dm[a] = d < 0 ? 0 : (d > GS_DROPPED ? GS_DROPPED : d);
+        U.dm[a] = d < 0 ? 0 : (d > GRID_DROPPED ? GRID_DROPPED : d);
     }
 
     double sum = 0.0;
@@ -442,7 +272,7 @@ __global__ __launch_bounds__(GS_THREADS) void geo_score_kernel(const double* __r
         const double x = Q[0], y = Q[1], z = Q[2];
         double bd;
         int bj;
-        gs_search(U, gs_uniform(gs_move(m, 0, x, y, z)), gs_uniform(gs_move(m, 1, x, y, z)), gs_uniform(gs_move(m, 2, x, y, z)), lane,
+        gs_search(U, gs_uniform(sga_move_point(m, 0, x, y, z)), gs_uniform(sga_move_point(m, 1, x, y, z)), gs_uniform(sga_move_point(m, 2, x, y, z)), lane,
                   row_start[wave], row_excl[wave], bd, bj);
         if (bj != INT_MAX) {                                             // uniform over the wave: the butterfly left the same pair in every lane
             sum = __dadd_rn(sum, bd);
@@ -474,7 +304,7 @@ __global__ __launch_bounds__(GS_THREADS) void geo_fold_kernel(const int* __restr
                                                               int* __restrict__ count, double* __restrict__ sum_d2) {
     const long long job = (long long)blockIdx.x * GS_THREADS + threadIdx.x;
     if (job >= n_pairs) return;
-    const GSJob J = gs_job(off, n_clouds, total_points, pairs, n_pairs, (int)job);
+    const SgaCloudPair J = sga_cloud_pair(off, n_clouds, total_points, pairs, n_pairs, (int)job);
     double s = 0.0;
     long long n = 0;
     if (J.ok && !(live && live[job] == 0)) {

@@ -18,8 +18,8 @@
 // the original row.  For the block of cells |k - c|inf <= R around the query's cell c, every (kx, ky) row of the block is one contiguous
 // range of sorted positions (kz is the lowest key field): lane r finds row r's range with a lower and an upper bound on sorted_keys, the
 // wave prefix-sums the lengths and walks the concatenated ranges 64 candidates at a time (a lane finds its candidate's row by a binary
-// search over the 64 prefix entries in LDS), with the d2 expression of knn_kernel and its ballot / stage / rank-sort merge (copied here:
-// fpfh.hip is left byte for byte as it was).  Candidates do not arrive in ascending j, so admission against a full list is
+// search over the 64 prefix entries in LDS), with the d2 expression of knn_kernel and its ballot / stage / rank-sort merge (kl_rank_sort of
+// wave_search.h; vg_merge / vg_offer are this file's list state around it).  Candidates do not arrive in ascending j, so admission against a full list is
 // lexicographic: d2 < tau || (d2 == tau && j < tau_j).  R = 1, 2, 4, 8, 16, each from an empty list; a query that is still undecided, one whose
 // block would cover the cloud's whole cell box, a dropped query and every query of a cloud without a grid (status != 0) streams its whole
 // cloud in original order instead, as knn_kernel does.  Either way the list is the first max_nn of {j : d2 <= r2} by (d2, j): the grid
@@ -39,18 +39,14 @@
 // Hence g g (1 - 2^-40) > bound implies computed d2 > bound for every point outside the block, where bound = min(r2, tau if the list is
 // full else +inf): such a point fails d2 <= r2 or loses against the full list even on a tie (d2 > tau strictly), so scanning it would not
 // change the list.  Points INSIDE the block were scanned whatever cell the rounding put them in: membership is by the key, not by position.
-#include <limits.h>
-#include <math.h>
-
 #include "pair_jobs.h"
+#include "wave_search.h"
 
 namespace {
 
 constexpr int VX_THREADS = 256;
 constexpr int VX_ITEMS = 4;                        // sorted positions per lane in the scan kernels
 constexpr int VX_BLOCK = VX_THREADS * VX_ITEMS;    // sorted positions per workgroup in the scan kernels
-constexpr int VX_DROPPED = 65535;                  // the cell coordinate of a dropped point; a valid one is below it
-constexpr int VX_MAX_CLOUDS = 32767;               // the cloud id is the key's top field: 15 bits keep the key non-negative
 constexpr long long VX_CELL_MASK = 0xFFFFFFFFFFFFll;
 
 constexpr int KL_THREADS = 256;
@@ -58,28 +54,6 @@ constexpr int KL_WAVES = 4;                        // queries per workgroup: one
 constexpr int KL_MAX_NN = 128;                     // longest list
 constexpr int KL_STAGE = 64;                       // staged candidates per wave: one full ballot
 constexpr int KL_SLOTS = KL_MAX_NN + KL_STAGE;     // entries a merge sorts, three per lane at most
-constexpr int VG_MAX_R = 16;                       // block radii 1, 2, 4, 8, 16; then the whole cloud
-constexpr double VG_EPS = 0x1p-40;
-
-struct VCloud { int o0, n, c; bool ok; };
-
-__device__ __forceinline__ VCloud vx_cloud(const int* __restrict__ off, int total_points, int c) {
-    const SgaSegment s = sga_segment(off, total_points, c);
-    return VCloud{s.o0, s.n, c, s.ok};
-}
-
-// The cloud that holds packed row i: the LAST c with offsets[c] <= i (empty clouds repeat an offset), re-checked.
-__device__ __forceinline__ VCloud vx_cloud_of_point(const int* __restrict__ off, int n_clouds, int total_points, int i) {
-    int lo = 0, hi = n_clouds - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    const VCloud C = vx_cloud(off, total_points, lo);
-    if (!C.ok || i < C.o0 || i - C.o0 >= C.n) return VCloud{0, 0, lo, false};
-    return C;
-}
-
 __device__ __forceinline__ long long vx_dropped_key(int c) { return ((long long)c << 48) | VX_CELL_MASK; }
 __device__ __forceinline__ bool vx_is_dropped(long long key) { return (key & VX_CELL_MASK) == VX_CELL_MASK; }
 
@@ -94,7 +68,7 @@ __global__ __launch_bounds__(VX_THREADS) void vx_bounds_kernel(const double* __r
     __shared__ double smn[3][VX_THREADS / 64], smx[3][VX_THREADS / 64];
     const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (c >= n_clouds) return;
-    const VCloud C = vx_cloud(off, total_points, c);
+    const SgaCloud C = sga_cloud(off, total_points, c);
     double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int j = tid; j < C.n; j += VX_THREADS) {                       // C.n == 0 on a bad offset
         const double* p = pts + ((size_t)C.o0 + j) * 3;
@@ -138,7 +112,7 @@ __global__ __launch_bounds__(VX_THREADS) void vx_bounds_kernel(const double* __r
     }
     const double h = cell[c];
     const bool h_ok = C.ok && h > 0.0 && isfinite(h);
-    int st = (h_ok && n_clouds <= VX_MAX_CLOUDS) ? 0 : 2;
+    int st = (h_ok && n_clouds <= GRID_MAX_CLOUDS) ? 0 : 2;
     double o[3] = {0.0, 0.0, 0.0};
     int d[3] = {0, 0, 0};
 #pragma unroll
@@ -149,7 +123,7 @@ __global__ __launch_bounds__(VX_THREADS) void vx_bounds_kernel(const double* __r
         if (h_ok && lo <= hi) {                                         // the cloud has a kept point
             o[a] = __dsub_rn(lo, __dmul_rn(0.5, h));
             const double kd = floor(__ddiv_rn(__dsub_rn(hi, o[a]), h));
-            if (kd >= 0.0 && kd < (double)VX_DROPPED) d[a] = (int)kd + 1; else st = 2;
+            if (kd >= 0.0 && kd < (double)GRID_DROPPED) d[a] = (int)kd + 1; else st = 2;
         }
     }
 #pragma unroll
@@ -167,8 +141,8 @@ __global__ __launch_bounds__(VX_THREADS) void vx_keys_kernel(const double* __res
     const long long gi = (long long)blockIdx.x * VX_THREADS + threadIdx.x;
     if (gi >= total_points) return;
     const int i = (int)gi;
-    const VCloud C = vx_cloud_of_point(off, n_clouds, total_points, i);
-    const int cf = n_clouds <= VX_MAX_CLOUDS ? C.c : 0;
+    const SgaCloud C = sga_cloud_of_point(off, n_clouds, total_points, i);
+    const int cf = n_clouds <= GRID_MAX_CLOUDS ? C.c : 0;
     long long key = vx_dropped_key(cf);
     if (C.ok && status[C.c] == 0) {
         const double h = cell[C.c];
@@ -178,8 +152,8 @@ __global__ __launch_bounds__(VX_THREADS) void vx_keys_kernel(const double* __res
         for (int a = 0; a < 3; ++a) {
             const double p = pts[(size_t)i * 3 + a];
             const double kd = floor(__ddiv_rn(__dsub_rn(p, origin[(size_t)C.c * 3 + a]), h));
-            kept = kept && isfinite(p) && kd >= 0.0 && kd < (double)VX_DROPPED;
-            k[a] = kept ? (int)kd : VX_DROPPED;
+            kept = kept && isfinite(p) && kd >= 0.0 && kd < (double)GRID_DROPPED;
+            k[a] = kept ? (int)kd : GRID_DROPPED;
         }
         if (kept) key = ((long long)cf << 48) | ((long long)k[0] << 32) | ((long long)k[1] << 16) | (long long)k[2];
     }
@@ -196,7 +170,7 @@ __global__ __launch_bounds__(VX_THREADS) void vx_verify_kernel(const int* __rest
     const long long gt = (long long)blockIdx.x * VX_THREADS + threadIdx.x;
     if (gt >= total_points) return;
     const int t = (int)gt;
-    const VCloud C = vx_cloud_of_point(off, n_clouds, total_points, t);
+    const SgaCloud C = sga_cloud_of_point(off, n_clouds, total_points, t);
     if (!C.ok) { sorted_keys[t] = vx_dropped_key(0); return; }
     const int i = order[t];
     if (i < C.o0 || i - C.o0 >= C.n) {
@@ -255,7 +229,7 @@ __global__ __launch_bounds__(VX_THREADS) void vx_heads_kernel(const int* __restr
         const long long gt = base + e;
         if (gt >= total_points) break;
         const int t = (int)gt;
-        const VCloud C = vx_cloud_of_point(off, n_clouds, total_points, t);
+        const SgaCloud C = sga_cloud_of_point(off, n_clouds, total_points, t);
         int head = 0;
         if (C.ok && status[C.c] == 0 && bad[C.c] == 0) {
             const long long k = sorted_keys[t];
@@ -313,7 +287,7 @@ __global__ __launch_bounds__(VX_THREADS) void vx_finish_kernel(const int* __rest
     const long long gt = (long long)blockIdx.x * VX_THREADS + threadIdx.x;
     if (gt < total_points) {
         const int t = (int)gt;
-        const VCloud C = vx_cloud_of_point(off, n_clouds, total_points, t);
+        const SgaCloud C = sga_cloud_of_point(off, n_clouds, total_points, t);
         const bool valid = C.ok && status[C.c] == 0 && bad[C.c] == 0;      // status[c] may already read 3 here: bad[c] says the same
         if (!valid) {
             voxel_of_point[t] = -1;                                        // by position: the order of such a cloud is not trusted
@@ -361,7 +335,7 @@ __global__ __launch_bounds__(VX_THREADS) void vx_means_kernel(const double* __re
         const int mid = (lo + hi + 1) >> 1;
         if (voxel_offsets[mid] <= g) lo = mid; else hi = mid - 1;
     }
-    const VCloud C = vx_cloud(off, total_points, lo);
+    const SgaCloud C = sga_cloud(off, total_points, lo);
     if (!C.ok || status[lo] != 0 || voxel_offsets[lo] > g || voxel_offsets[lo + 1] <= g) return;
     const int s = voxel_first[g];
     if (s < C.o0 || s - C.o0 >= C.n) return;
@@ -394,56 +368,6 @@ __global__ __launch_bounds__(VX_THREADS) void vx_means_kernel(const double* __re
 }
 
 // ---- grid neighbour lists ----------------------------------------------------------------------------------------------------------------
-// The list machinery of fpfh.hip's knn_kernel, copied: see there.
-__device__ __forceinline__ void kl_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ bool kl_less(double da, int ja, double db, int jb) { return da < db || (da == db && ja < jb); }
-
-template <int K>
-__device__ __forceinline__ void kl_rank_sort(double* __restrict__ wd, int* __restrict__ wi, int lane, int L, int E, int max_nn) {
-    double d[K];
-    int j[K], r[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int e = lane + 64 * k;
-        const bool ok = e < E;
-        d[k] = ok ? wd[e] : INFINITY;
-        j[k] = ok ? wi[e] : INT_MAX;
-        r[k] = e < L ? e : 0;
-    }
-#pragma unroll 1
-    for (int m = L; m < E; ++m) {
-        const double dm = wd[m];
-        const int jm = wi[m];
-#pragma unroll
-        for (int k = 0; k < K; ++k) r[k] += kl_less(dm, jm, d[k], j[k]) ? 1 : 0;
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        if (L >= 64 * (k + 1) || E <= 64 * k || L == 0) continue;
-        const int e = lane + 64 * k;
-        int lo = 0, hi = (e >= L && e < E) ? L : 0;
-#pragma unroll 1
-        for (int step = 0; step < 8; ++step) {
-            const int mid = (lo + hi) >> 1;
-            const int at = min(mid, L - 1);
-            const bool go = lo < hi, up = kl_less(wd[at], wi[at], d[k], j[k]);
-            lo = (go && up) ? mid + 1 : lo;
-            hi = (go && !up) ? mid : hi;
-        }
-        r[k] += lo;
-    }
-    kl_wave_sync();
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-        if (lane + 64 * k < E && r[k] < max_nn) { wd[r[k]] = d[k]; wi[r[k]] = j[k]; }
-    kl_wave_sync();
-}
-
 // The wave's list: L sorted entries, S staged behind them; full: tau / tau_j are the max_nn-th best (d2, j).
 struct VgList { int L, S; double tau; int tau_j; bool full; };
 
@@ -451,10 +375,10 @@ __device__ __forceinline__ void vg_reset(VgList& q) { q.L = 0; q.S = 0; q.tau = 
 
 __device__ __forceinline__ void vg_merge(double* __restrict__ wd, int* __restrict__ wi, int lane, int max_nn, VgList& q) {
     const int E = q.L + q.S;
-    kl_wave_sync();
-    if (E <= 64) kl_rank_sort<1>(wd, wi, lane, q.L, E, max_nn);
-    else if (E <= 128) kl_rank_sort<2>(wd, wi, lane, q.L, E, max_nn);
-    else kl_rank_sort<3>(wd, wi, lane, q.L, E, max_nn);
+    sga_wave_sync();
+    if (E <= 64) kl_rank_sort<1, 1>(wd, wi, lane, q.L, E, max_nn);
+    else if (E <= 128) kl_rank_sort<2, 1>(wd, wi, lane, q.L, E, max_nn);
+    else kl_rank_sort<3, 1>(wd, wi, lane, q.L, E, max_nn);
     q.L = min(E, max_nn);
     q.S = 0;
     if (E >= max_nn) { q.full = true; q.tau = wd[max_nn - 1]; q.tau_j = wi[max_nn - 1]; }
@@ -464,13 +388,13 @@ __device__ __forceinline__ void vg_merge(double* __restrict__ wd, int* __restric
 // admits too much; the merge drops it again.
 __device__ __forceinline__ void vg_offer(double* __restrict__ wd, int* __restrict__ wi, int lane, int max_nn, double r2, double d2, int j,
                                          bool inb, VgList& q) {
-    bool adm = inb && d2 <= r2 && (!q.full || kl_less(d2, j, q.tau, q.tau_j));      // a NaN fails d2 <= r2
+    bool adm = inb && d2 <= r2 && (!q.full || sga_d2j_less(d2, j, q.tau, q.tau_j));      // a NaN fails d2 <= r2
     unsigned long long bal = __ballot(adm);
     if (bal == 0ull) return;
     int c = __popcll(bal);
     if (q.S + c > KL_STAGE) {
         vg_merge(wd, wi, lane, max_nn, q);
-        adm = adm && (!q.full || kl_less(d2, j, q.tau, q.tau_j));
+        adm = adm && (!q.full || sga_d2j_less(d2, j, q.tau, q.tau_j));
         bal = __ballot(adm);
         c = __popcll(bal);
     }
@@ -480,21 +404,6 @@ __device__ __forceinline__ void vg_offer(double* __restrict__ wd, int* __restric
         wi[slot] = j;
     }
     q.S += c;
-}
-
-__device__ __forceinline__ double vg_d2(double qx, double qy, double qz, const double* __restrict__ p) {
-    const double dx = __dsub_rn(qx, p[0]), dy = __dsub_rn(qy, p[1]), dz = __dsub_rn(qz, p[2]);
-    return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-}
-
-// first position of sk[0, n) whose key is >= key
-__device__ __forceinline__ int vg_lower_bound(const long long* __restrict__ sk, int n, long long key) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (sk[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 // Five waves per SIMD = five workgroups per CU (95 VGPRs; knn_kernel holds 7 by its LDS): a sixth costs 11 spilled registers.
@@ -511,7 +420,7 @@ __global__ __launch_bounds__(KL_THREADS) __attribute__((amdgpu_waves_per_eu(5)))
     const long long gp = (long long)blockIdx.x * KL_WAVES + wave;
     if (gp >= total_points) return;                                      // no workgroup-wide barrier below: a wave may leave on its own
     const int pos = (int)gp;
-    const VCloud C = vx_cloud_of_point(off, n_clouds, total_points, pos);
+    const SgaCloud C = sga_cloud_of_point(off, n_clouds, total_points, pos);
     if (!C.ok) return;
     const bool has_grid = status[C.c] == 0;
     int qi = pos;                                                        // without a grid: the query at its own row
@@ -536,7 +445,7 @@ __global__ __launch_bounds__(KL_THREADS) __attribute__((amdgpu_waves_per_eu(5)))
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const int d = dims[(size_t)C.c * 3 + a];
-        dm[a] = d < 0 ? 0 : (d > VX_DROPPED ? VX_DROPPED : d);
+        dm[a] = d < 0 ? 0 : (d > GRID_DROPPED ? GRID_DROPPED : d);
     }
     const bool use_grid = has_grid && !vx_is_dropped(key) && kc[0] < dm[0] && kc[1] < dm[1] && kc[2] < dm[2] && cell[C.c] > 0.0;
     const long long cloud_bits = key & ~VX_CELL_MASK;
@@ -544,7 +453,7 @@ __global__ __launch_bounds__(KL_THREADS) __attribute__((amdgpu_waves_per_eu(5)))
     // knn_kernel walks it, dropped points included): a single "row" [0, n) read without `order`.  It is the last pass whenever it runs.
 #pragma unroll 1
     for (int R = use_grid ? 1 : 0;; R *= 2) {
-        if (R > VG_MAX_R) R = 0;
+        if (R > GRID_MAX_R) R = 0;
         int x0 = 0, y0 = 0, z0 = 0, z1 = 0, ny = 1, rows = 1;
         if (R > 0) {
             const int x1 = min(kc[0] + R, dm[0] - 1), y1 = min(kc[1] + R, dm[1] - 1);
@@ -565,16 +474,16 @@ __global__ __launch_bounds__(KL_THREADS) __attribute__((amdgpu_waves_per_eu(5)))
                 len = lane == 0 ? C.n : 0;
             } else if (r < rows) {
                 const long long rowkey = cloud_bits | ((long long)(x0 + r / ny) << 32) | ((long long)(y0 + r % ny) << 16);
-                start = vg_lower_bound(sk, C.n, rowkey | (long long)z0);
-                len = vg_lower_bound(sk, C.n, (rowkey | (long long)z1) + 1) - start;
+                start = sga_lower_bound(sk, C.n, rowkey | (long long)z0);
+                len = sga_lower_bound(sk, C.n, (rowkey | (long long)z1) + 1) - start;
                 if (len < 0) len = 0;
             }
             const int incl = wave_incl_scan(len, lane);
             const int total_len = __shfl(incl, 63, 64);
-            kl_wave_sync();                                              // the previous batch's table has been read by every lane
+            sga_wave_sync();                                              // the previous batch's table has been read by every lane
             rs[lane] = start;
             rx[lane] = incl - len;
-            kl_wave_sync();
+            sga_wave_sync();
 #pragma unroll 1
             for (int u0 = 0; u0 < total_len; u0 += 64) {
                 const bool inb = u0 + lane < total_len;
@@ -588,7 +497,7 @@ __global__ __launch_bounds__(KL_THREADS) __attribute__((amdgpu_waves_per_eu(5)))
                 const int i = !tin ? C.o0 : (whole ? C.o0 + t : ord[t]);
                 const bool jin = tin && i >= C.o0 && i - C.o0 < C.n;
                 const int j = jin ? i - C.o0 : 0;
-                const double d2 = vg_d2(qx, qy, qz, P + (size_t)j * 3);
+                const double d2 = sga_point_d2(qx, qy, qz, P + (size_t)j * 3);
                 vg_offer(wd, wi, lane, max_nn, r2, d2, j, inb && jin, q);
             }
         }
@@ -605,11 +514,11 @@ __global__ __launch_bounds__(KL_THREADS) __attribute__((amdgpu_waves_per_eu(5)))
             double gap = INFINITY;
             if (kc[a] - R > 0) gap = __dsub_rn(qa, __dadd_rn(o, __dmul_rn((double)(kc[a] - R), h)));
             if (kc[a] + R < dm[a] - 1) gap = fmin(gap, __dsub_rn(__dadd_rn(o, __dmul_rn((double)(kc[a] + R + 1), h)), qa));
-            g = fmin(g, __dsub_rn(gap, __dmul_rn(VG_EPS, scale)));
+            g = fmin(g, __dsub_rn(gap, __dmul_rn(GRID_EPS, scale)));
         }
-        if (g > 0.0 && __dmul_rn(__dmul_rn(g, g), 1.0 - VG_EPS) > bound) break;
+        if (g > 0.0 && __dmul_rn(__dmul_rn(g, g), 1.0 - GRID_EPS) > bound) break;
     }
-    kl_wave_sync();
+    sga_wave_sync();
     const size_t row = (size_t)qi * max_nn;
     for (int e = lane; e < max_nn; e += 64) {
         out_idx[row + e] = e < q.L ? wi[e] : -1;

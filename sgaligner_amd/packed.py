@@ -1,7 +1,7 @@
 """The packed-segment contract of the batched geometry ops, host side: segments (objects, clouds, jobs, scans) packed back to back, an
 [n + 1] prefix array that is validated here before the C ABI validates its host copy again (csrc/packed.h), tensors that must already live
 on the device, and small host arrays that travel in ONE upload; on top of it the job list of the nearest-neighbour searches (PairJobs,
-csrc/pair_jobs.h) and the one chunk rule (split_chunk).  Used by utils/point_cloud, registration, features and preprocessing/subscans, scene_graphs."""
+csrc/pair_jobs.h), the hypothesis list of the RANSAC entries (HypJobs) and the one chunk rule (split_chunk).  Used by utils/point_cloud, registration, features and preprocessing/subscans, scene_graphs."""
 from __future__ import annotations
 
 import numpy as np
@@ -76,6 +76,14 @@ def resolve_chunk(arg, module_default, rule) -> int:
     return chunk
 
 
+def pair_ids(pairs, n_sets=None, unit='cloud') -> np.ndarray:
+    """`pairs` (tensor or sequence) -> contiguous int64 [n_pairs, 2]; with n_sets, ValueError unless every id names one of the `unit`s."""
+    pr = np.ascontiguousarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
+    if n_sets is not None and pr.size and (pr.min() < 0 or pr.max() >= n_sets):
+        raise ValueError(f'pairs must name {unit}s in [0, {n_sets})')
+    return pr
+
+
 class PairJobs:
     """(query set, support set) jobs over sets packed back to back, what csrc/pair_jobs.h checks again behind the C ABI: off (int64
     [n_sets + 1] over `total` rows), pr (int64 [n_pairs, 2]), per job nq / ns, out_off (int64 [n_pairs + 1]: job p's results start at
@@ -84,9 +92,7 @@ class PairJobs:
     def __init__(self, offsets, total, pairs, what: str, unit: str):
         self.off = prefix_offsets(offsets, 'offsets', total)
         self.n_sets = len(self.off) - 1
-        self.pr = np.ascontiguousarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
-        if self.pr.size and (self.pr.min() < 0 or self.pr.max() >= self.n_sets):
-            raise ValueError(f'pairs must name {unit}s in [0, {self.n_sets})')
+        self.pr = pair_ids(pairs, self.n_sets, unit)
         self.nq, self.ns = (np.diff(self.off)[self.pr[:, k]] for k in (0, 1))
         self.out_off = np.concatenate([[0], np.cumsum(self.nq)]).astype(np.int64)
         self.n_pairs, self.total_q = len(self.pr), int(self.out_off[-1])
@@ -97,6 +103,39 @@ class PairJobs:
 
     def host_parts(self):                                   # what the kernels read, for the caller's ONE upload (it may append its own)
         return [self.h_off, self.h_pr, self.h_oo]
+
+
+class HypJobs:
+    """A packed hypothesis list as the RANSAC entries take it (csrc/ransac.hip, csrc/ransac_geo.hip), checked in the order dtype, device,
+    shape: corr [N, 6] float64 and samples [H, 3] int32 HIP tensors (job-local row indices), offsets / hyp_offsets the two [n_jobs + 1]
+    prefix arrays over them.  Holds corr, samples, off / hoff (int64), their int32 host copies h_off / h_hoff, n_jobs, total / total_h,
+    the per-job sizes_n / sizes_h and max_n / max_h.  corr_shape=False leaves corr's shape to the caller; convert_samples=True takes
+    samples from numpy or any integer tensor and converts it instead of refusing."""
+
+    def __init__(self, corr, offsets, samples, hyp_offsets, corr_shape=True, convert_samples=False):
+        self.corr = device_tensor(corr, 'corr', torch.float64)
+        if corr_shape and (self.corr.dim() != 2 or self.corr.shape[1] != 6):
+            raise ValueError(f'corr must be [N,6], got {tuple(self.corr.shape)}')
+        if convert_samples:
+            sm = samples if isinstance(samples, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(samples, dtype=np.int32))
+            sm = sm.to(device=self.corr.device, dtype=torch.int32).contiguous()
+        else:
+            sm = device_tensor(samples, 'samples', torch.int32)
+        self.samples = sm.reshape(-1, 3)
+        self.total, self.total_h = int(self.corr.shape[0]), int(self.samples.shape[0])
+        self.off = prefix_offsets(offsets, 'offsets', self.total)
+        self.hoff = prefix_offsets(hyp_offsets, 'hyp_offsets', self.total_h)
+        self.n_jobs = len(self.off) - 1
+        if len(self.hoff) != self.n_jobs + 1:
+            raise ValueError(f'offsets names {self.n_jobs} jobs, hyp_offsets {len(self.hoff) - 1}')
+        self.h_off, self.h_hoff = self.off.astype(np.int32), self.hoff.astype(np.int32)
+        self.sizes_n, self.sizes_h = np.diff(self.off), np.diff(self.hoff)
+        self.max_n, self.max_h = (int(self.sizes_n.max()), int(self.sizes_h.max())) if self.n_jobs else (0, 0)
+
+    def check_int32(self, what: str, per_hyp: int):
+        """ValueError unless corr's 6 columns and `per_hyp` values per hypothesis can be indexed with int32."""
+        if self.total >= 2 ** 31 // 6 or self.total_h >= 2 ** 31 // per_hyp:
+            raise ValueError(f'{what} indexes with int32: fewer than 2^31 / 6 rows and 2^31 / {per_hyp} hypotheses per call')
 
 
 class PackedLayout:

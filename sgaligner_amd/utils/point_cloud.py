@@ -234,11 +234,18 @@ def nn_grid_cell(clouds, radius=None):
     return edge
 
 
+def _search_grid(pts, off, radius, cell):
+    """What every cross-cloud grid search starts from: the clouds of the call and their grid (utils/voxel.build_grid) at `cell`, or at
+    nn_grid_cell's edge when none is given.  -> (clouds, grid)"""
+    from . import voxel
+    from .features import _Clouds
+    C = _Clouds(pts, off)
+    return C, voxel.build_grid(C, None, nn_grid_cell(C, radius) if cell is None else cell)
+
+
 def _nn_grid(pts, J, radius, transforms, cell, squared, dist, idx):
     """The grid route of nearest_neighbor_batch (csrc/icp.hip): the grid of every cloud of the call (utils/voxel.build_grid), then one
     launch for all jobs.  The cell edge is a speed choice only (nn_grid_cell)."""
-    from . import voxel
-    from .features import _Clouds
     r2 = float('inf') if radius is None else float(radius) * float(radius)
     if not r2 >= 0.0:
         raise ValueError(f'radius must be >= 0 or None, got {radius}')
@@ -247,13 +254,11 @@ def _nn_grid(pts, J, radius, transforms, cell, squared, dist, idx):
         tr = device_tensor(transforms, 'transforms', torch.float64)
         if tuple(tr.shape) != (J.n_pairs, 12):
             raise ValueError(f'transforms must be [{J.n_pairs}, 12] (row-major R | t per job), got {tuple(tr.shape)}')
-    C = _Clouds(pts, J.off)
-    G = voxel.build_grid(C, None, nn_grid_cell(C, radius) if cell is None else cell)
+    C, G = _search_grid(pts, J.off, radius, cell)
     _, d_pr, d_oo = upload(J.host_parts(), pts.device)
     rc = _lib.lib().sga_nn_search_grid(_p(pts), _p(C.d_off), J.n_sets, int(pts.shape[0]), _p(d_pr), J.n_pairs, _p(d_oo), J.total_q, J.max_q,
-                                       J.h_off.ctypes.data, J.h_pr.ctypes.data, _p(G.cell), _p(G.origin), _p(G.dims), _p(G.status), _p(G.order),
-                                       _p(G.sorted_keys), _p(tr) if tr is not None else None, r2, 1 if squared else 0, _p(dist), _p(idx),
-                                       _stream())
+                                       J.h_off.ctypes.data, J.h_pr.ctypes.data, *G.search_args(), _p(tr) if tr is not None else None, r2,
+                                       1 if squared else 0, _p(dist), _p(idx), _stream())
     _lib.check(rc, 'sga_nn_search_grid')
 
 

@@ -15,8 +15,8 @@ import torch
 
 from .. import _lib
 from ..ops import _p, _stream
-from ..packed import PairJobs, check_finite, device_tensor, prefix_offsets, resolve_chunk, split_chunk, upload, workspace
-from .point_cloud import _cloud64, _need_device, _nn_numpy, apply_transform, get_nearest_neighbor, nn_grid_cell
+from ..packed import HypJobs, PairJobs, check_finite, device_tensor, pair_ids, prefix_offsets, resolve_chunk, split_chunk, upload, workspace
+from .point_cloud import _cloud64, _need_device, _nn_numpy, _search_grid, apply_transform, get_nearest_neighbor
 
 
 def compute_modified_chamfer_distance(src_points, ref_points, raw_points, est_transform, gt_transform):
@@ -114,27 +114,15 @@ def find_rigid_transform_batch(corr, offsets, samples, hyp_offsets, threshold, r
     (column-vector convention: apply_transform(src, T) ~ ref), inlier_count / best_hyp / status [n_jobs] int32 (status 1 = no model: identity,
     count 0, best_hyp -1), inlier_mask [sum n] uint8, hyp_count [sum H] int32 (the inlier count of every hypothesis).  refine_rounds = -1
     stops after the scoring: only hyp_count is meaningful then (score_hypotheses_batch)."""
-    cr = device_tensor(corr, 'corr', torch.float64)
-    if cr.dim() != 2 or cr.shape[1] != 6:
-        raise ValueError(f'corr must be [N,6], got {tuple(cr.shape)}')
-    dev = cr.device
-    sm = samples if isinstance(samples, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(samples, dtype=np.int32))
-    sm = sm.to(device=dev, dtype=torch.int32).contiguous().reshape(-1, 3)
-    off = prefix_offsets(offsets, 'offsets', int(cr.shape[0]))
-    hoff = prefix_offsets(hyp_offsets, 'hyp_offsets', int(sm.shape[0]))
-    n_jobs = len(off) - 1
-    if len(hoff) != n_jobs + 1:
-        raise ValueError(f'offsets names {n_jobs} jobs, hyp_offsets {len(hoff) - 1}')
-    if cr.shape[0] >= 2 ** 31 // 6 or sm.shape[0] >= 2 ** 31 // 3:
-        raise ValueError('find_rigid_transform_batch indexes with int32: fewer than 2^31 / 6 rows and 2^31 / 3 hypotheses per call')
+    J = HypJobs(corr, offsets, samples, hyp_offsets, convert_samples=True)
+    J.check_int32('find_rigid_transform_batch', 3)
+    cr, sm, dev, n_jobs, total, total_h = J.corr, J.samples, J.corr.device, J.n_jobs, J.total, J.total_h
     threshold, refine_rounds = float(threshold), int(refine_rounds)
     if refine_rounds < -1:
         raise ValueError(f'refine_rounds must be >= 0 (or -1: scoring only), got {refine_rounds}')
     if not (np.isfinite(threshold) and threshold >= 0):
         raise ValueError(f'threshold must be finite and >= 0, got {threshold}')
     check_finite(cr, 'corr', 'coordinates')
-    sizes_n, sizes_h = np.diff(off), np.diff(hoff)
-    total, total_h = int(cr.shape[0]), int(sm.shape[0])
     out = {'transform': torch.empty((n_jobs, 4, 4), device=dev, dtype=torch.float64),
            'inlier_count': torch.empty((n_jobs,), device=dev, dtype=torch.int32),
            'best_hyp': torch.empty((n_jobs,), device=dev, dtype=torch.int32),
@@ -143,15 +131,13 @@ def find_rigid_transform_batch(corr, offsets, samples, hyp_offsets, threshold, r
            'hyp_count': torch.empty((total_h,), device=dev, dtype=torch.int32)}
     if n_jobs == 0:
         return out
-    chunk = resolve_chunk(chunk, RANSAC_CHUNK, lambda: _ransac_chunk(sizes_n, sizes_h))
+    chunk = resolve_chunk(chunk, RANSAC_CHUNK, lambda: _ransac_chunk(J.sizes_n, J.sizes_h))
     L = _lib.lib()
-    h_off, h_hoff = off.astype(np.int32), hoff.astype(np.int32)
-    d_off, d_hoff = upload([h_off, h_hoff], dev)                              # one small upload
-    max_n, max_h = int(sizes_n.max()), int(sizes_h.max())
-    ws_bytes = int(L.sga_ransac_workspace_bytes(n_jobs, total_h, max_n, chunk))
+    d_off, d_hoff = upload([J.h_off, J.h_hoff], dev)                          # one small upload
+    ws_bytes = int(L.sga_ransac_workspace_bytes(n_jobs, total_h, J.max_n, chunk))
     ws = workspace(ws_bytes, dev)
-    rc = L.sga_ransac_rigid(_p(cr) if total else None, _p(d_off), n_jobs, total, _p(sm) if total_h else None, _p(d_hoff), total_h, max_n, max_h,
-                            chunk, h_off.ctypes.data, h_hoff.ctypes.data, threshold, int(refine_rounds), _p(out['transform']),
+    rc = L.sga_ransac_rigid(_p(cr) if total else None, _p(d_off), n_jobs, total, _p(sm) if total_h else None, _p(d_hoff), total_h, J.max_n, J.max_h,
+                            chunk, J.h_off.ctypes.data, J.h_hoff.ctypes.data, threshold, int(refine_rounds), _p(out['transform']),
                             _p(out['inlier_count']), _p(out['best_hyp']), _p(out['status']), _p(out['inlier_mask']) if total else None,
                             _p(out['hyp_count']) if total_h else None, _p(ws), ws_bytes, _stream())
     _lib.check(rc, 'sga_ransac_rigid')
@@ -371,16 +357,12 @@ def edge_length_filter(corr, offsets, samples, hyp_offsets, similarity=0.9):
     fp64 distance sqrt((dx*dx + dy*dy) + dz*dz) between the two rows on that side.  A failing triple is overwritten with an invalid one
     (its first index three times), which sga_ransac_rigid scores 0 and never selects: hypothesis indices keep their meaning.  -> samples
     [sum H, 3] int32 HIP tensor (a new one)."""
-    cr = device_tensor(corr, 'corr', torch.float64)
-    sm = device_tensor(samples, 'samples', torch.int32).reshape(-1, 3)
-    off = prefix_offsets(offsets, 'offsets', int(cr.shape[0]))
-    hoff = prefix_offsets(hyp_offsets, 'hyp_offsets', int(sm.shape[0]))
-    if len(off) != len(hoff):
-        raise ValueError(f'offsets names {len(off) - 1} jobs, hyp_offsets {len(hoff) - 1}')
+    J = HypJobs(corr, offsets, samples, hyp_offsets, corr_shape=False)
+    cr, sm = J.corr, J.samples
     if sm.shape[0] == 0:
         return sm.clone()
-    sizes = torch.from_numpy(np.repeat(np.diff(off), np.diff(hoff))).to(cr.device)
-    base = torch.from_numpy(np.repeat(off[:-1], np.diff(hoff))).to(cr.device)
+    sizes = torch.from_numpy(np.repeat(J.sizes_n, J.sizes_h)).to(cr.device)
+    base = torch.from_numpy(np.repeat(J.off[:-1], J.sizes_h)).to(cr.device)
     local = sm.long()
     ok = ((local >= 0) & (local < sizes[:, None])).all(dim=1)
     rows = cr[(local.clamp(min=0) + base[:, None]).clamp(max=max(int(cr.shape[0]) - 1, 0))]      # [H, 3, 6]
@@ -496,8 +478,6 @@ def icp_batch(points, offsets, pairs, transforms, max_distance, method='point', 
     (max_iters + 1) launches on torch's current stream and no synchronisation.  -> dict of HIP tensors: transform [n_pairs, 12], fitness,
     inlier_rmse [n_pairs] float64, iterations, status [n_pairs] int32, trace [n_pairs, max_iters + 1, 2], idx [sum nq] int32, d2 [sum nq]
     float64 (the correspondences of the FINAL transform, reference-cloud-local, -1 / +inf without one), and out_offsets (host)."""
-    from . import voxel
-    from .features import _Clouds
     if method not in ICP_METHODS:
         raise ValueError(f'method must be one of {tuple(ICP_METHODS)}, got {method!r}')
     max_iters, max_distance = int(max_iters), float(max_distance)
@@ -530,8 +510,7 @@ def icp_batch(points, offsets, pairs, transforms, max_distance, method='point', 
     if n == 0:
         return out
     L = _lib.lib()
-    C = _Clouds(pts, J.off)
-    G = voxel.build_grid(C, None, nn_grid_cell(C, max_distance) if cell is None else cell)
+    C, G = _search_grid(pts, J.off, max_distance, cell)
     _, d_pr, d_oo = upload(J.host_parts(), dev)
     box = torch.empty((J.n_sets, 6), device=dev, dtype=torch.float64)
     _lib.check(L.sga_cloud_bounds(_p(pts), *C.args(), _p(box), 1.0, None, _stream()), 'sga_cloud_bounds')
@@ -540,10 +519,9 @@ def icp_batch(points, offsets, pairs, transforms, max_distance, method='point', 
     ws_bytes = int(L.sga_icp_workspace_bytes(n, J.max_q))
     ws = workspace(ws_bytes, dev)
     rc = L.sga_icp(_p(pts), _p(C.d_off), J.n_sets, int(pts.shape[0]), _p(d_pr), n, _p(d_oo), J.total_q, J.max_q, J.h_off.ctypes.data,
-                   J.h_pr.ctypes.data, _p(G.cell), _p(G.origin), _p(G.dims), _p(G.status), _p(G.order), _p(G.sorted_keys),
-                   max_distance * max_distance, ICP_METHODS[method], _p(nr), _p(pivot), max_iters, float(relative_fitness), float(relative_rmse),
-                   _p(T), _p(out['fitness']), _p(out['inlier_rmse']), _p(out['iterations']), _p(out['status']), _p(out['trace']), _p(out['idx']),
-                   _p(out['d2']), _p(ws), ws_bytes, _stream())
+                   J.h_pr.ctypes.data, *G.search_args(), max_distance * max_distance, ICP_METHODS[method], _p(nr), _p(pivot), max_iters,
+                   float(relative_fitness), float(relative_rmse), _p(T), _p(out['fitness']), _p(out['inlier_rmse']), _p(out['iterations']),
+                   _p(out['status']), _p(out['trace']), _p(out['idx']), _p(out['d2']), _p(ws), ws_bytes, _stream())
     _lib.check(rc, 'sga_icp')
     return out
 
@@ -637,29 +615,22 @@ def hypothesis_models_batch(corr, offsets, samples, hyp_offsets):
     sga_ransac_models).  -> dict of HIP tensors: models [sum H, 12] float64 (row-major R | t; NaN where invalid), valid [sum H] int32,
     resid2 [sum H] float64 -- the largest |R s + t - r|^2 of the three sampled rows in the grid search's arithmetic (no fma), +inf where
     invalid: what Open3D's distance checker compares with the threshold."""
-    cr = device_tensor(corr, 'corr', torch.float64)
-    if cr.dim() != 2 or cr.shape[1] != 6:
-        raise ValueError(f'corr must be [N,6], got {tuple(cr.shape)}')
-    dev = cr.device
-    sm = device_tensor(samples, 'samples', torch.int32).reshape(-1, 3)
-    off = prefix_offsets(offsets, 'offsets', int(cr.shape[0]))
-    hoff = prefix_offsets(hyp_offsets, 'hyp_offsets', int(sm.shape[0]))
-    n_jobs = len(off) - 1
-    if len(hoff) != n_jobs + 1:
-        raise ValueError(f'offsets names {n_jobs} jobs, hyp_offsets {len(hoff) - 1}')
-    if cr.shape[0] >= 2 ** 31 // 6 or sm.shape[0] >= 2 ** 31 // 12:
-        raise ValueError('hypothesis_models_batch indexes with int32: fewer than 2^31 / 6 rows and 2^31 / 12 hypotheses per call')
+    return _hypothesis_models(HypJobs(corr, offsets, samples, hyp_offsets))
+
+
+def _hypothesis_models(J):
+    """hypothesis_models_batch of a checked hypothesis list."""
+    J.check_int32('hypothesis_models_batch', 12)
+    cr, dev, n_jobs, total, total_h = J.corr, J.corr.device, J.n_jobs, J.total, J.total_h
     check_finite(cr, 'corr', 'coordinates')
-    total, total_h = int(cr.shape[0]), int(sm.shape[0])
     out = {'models': torch.full((total_h, 12), float('nan'), device=dev, dtype=torch.float64),
            'valid': torch.zeros((total_h,), device=dev, dtype=torch.int32),
            'resid2': torch.full((total_h,), float('inf'), device=dev, dtype=torch.float64)}
     if n_jobs == 0 or total_h == 0:
         return out
-    h_off, h_hoff = off.astype(np.int32), hoff.astype(np.int32)
-    d_off, d_hoff = upload([h_off, h_hoff], dev)                              # one small upload
-    rc = _lib.lib().sga_ransac_models(_p(cr) if total else None, _p(d_off), n_jobs, total, _p(sm), _p(d_hoff), total_h, int(np.diff(hoff).max()),
-                                      h_off.ctypes.data, h_hoff.ctypes.data, _p(out['models']), _p(out['valid']), _p(out['resid2']), _stream())
+    d_off, d_hoff = upload([J.h_off, J.h_hoff], dev)                          # one small upload
+    rc = _lib.lib().sga_ransac_models(_p(cr) if total else None, _p(d_off), n_jobs, total, _p(J.samples), _p(d_hoff), total_h, J.max_h,
+                                      J.h_off.ctypes.data, J.h_hoff.ctypes.data, _p(out['models']), _p(out['valid']), _p(out['resid2']), _stream())
     _lib.check(rc, 'sga_ransac_models')
     return out
 
@@ -672,8 +643,6 @@ def score_transforms_batch(points, offsets, pairs, transforms, max_distance, liv
     a speed choice only).  -> (count [n_jobs] int32, sum_d2 [n_jobs] float64) HIP tensors: the number of moved source points with a
     reference point within max_distance (inf: no limit) and the sum of their squared distances to the nearest, in a fixed order -- the same
     bits in two calls, for a job alone or in a batch, and for every cell.  No synchronisation."""
-    from . import voxel
-    from .features import _Clouds
     max_distance = float(max_distance)
     if not max_distance > 0.0:
         raise ValueError(f'max_distance must be > 0 (inf: no limit), got {max_distance}')
@@ -683,9 +652,7 @@ def score_transforms_batch(points, offsets, pairs, transforms, max_distance, liv
     dev = pts.device
     off = prefix_offsets(offsets, 'offsets', int(pts.shape[0]))
     n_sets = len(off) - 1
-    pr = np.ascontiguousarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
-    if pr.size and (pr.min() < 0 or pr.max() >= n_sets):
-        raise ValueError(f'pairs must name clouds in [0, {n_sets})')
+    pr = pair_ids(pairs, n_sets, 'cloud')
     n = len(pr)
     T = device_tensor(transforms, 'transforms', torch.float64)
     if tuple(T.shape) != (n, 12):
@@ -705,16 +672,14 @@ def score_transforms_batch(points, offsets, pairs, transforms, max_distance, liv
     if -(-max_q // 1024) * n >= 2 ** 24:
         raise ValueError(f'score_transforms_batch: {n} jobs of up to {max_q} queries exceed the grid limit; split the job list')
     L = _lib.lib()
-    C = _Clouds(pts, off)
-    G = voxel.build_grid(C, None, nn_grid_cell(C, max_distance) if cell is None else cell)
+    C, G = _search_grid(pts, off, max_distance, cell)
     h_off, h_pr = off.astype(np.int32), pr.astype(np.int32)
     d_pr, = upload([h_pr], dev)
     ws_bytes = int(L.sga_score_transforms_workspace_bytes(n, max_q))
     ws = workspace(ws_bytes, dev)
     rc = L.sga_score_transforms_grid(_p(pts), _p(C.d_off), n_sets, int(pts.shape[0]), _p(d_pr), n, max_q, h_off.ctypes.data, h_pr.ctypes.data,
-                                     _p(G.cell), _p(G.origin), _p(G.dims), _p(G.status), _p(G.order), _p(G.sorted_keys), _p(T),
-                                     _p(lv) if lv is not None else None, max_distance * max_distance, _p(count), _p(sum_d2), _p(ws), ws_bytes,
-                                     _stream())
+                                     *G.search_args(), _p(T), _p(lv) if lv is not None else None, max_distance * max_distance, _p(count),
+                                     _p(sum_d2), _p(ws), ws_bytes, _stream())
     _lib.check(rc, 'sga_score_transforms_grid')
     return count, sum_d2
 
@@ -743,16 +708,14 @@ def ransac_geometric_batch(points, offsets, pairs, corr, corr_offsets, samples, 
     pts = device_tensor(points, 'points', torch.float64)
     dev = pts.device
     check_finite(pts, 'points', 'coordinates')                                             # the only download, before the first stage
-    M = hypothesis_models_batch(corr, corr_offsets, samples, hyp_offsets)
-    hoff = prefix_offsets(hyp_offsets, 'hyp_offsets', int(M['valid'].shape[0]))
+    HJ = HypJobs(corr, corr_offsets, samples, hyp_offsets)
+    M = _hypothesis_models(HJ)
+    hoff, H, n_jobs, total_h = HJ.hoff, HJ.sizes_h, HJ.n_jobs, HJ.total_h
     off = prefix_offsets(offsets, 'offsets', int(pts.shape[0]))
-    pr = np.ascontiguousarray(pairs.cpu() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
-    n_jobs, total_h = len(hoff) - 1, int(hoff[-1])
+    pr = pair_ids(pairs)
     if len(pr) != n_jobs:
         raise ValueError(f'pairs names {len(pr)} jobs, hyp_offsets {n_jobs}')
-    if pr.size and (pr.min() < 0 or pr.max() >= len(off) - 1):
-        raise ValueError(f'pairs must name clouds in [0, {len(off) - 1})')
-    H = np.diff(hoff)
+    pair_ids(pr, len(off) - 1, 'cloud')
     K = np.minimum(H, max_validation)                                                      # evaluation slots per job: a host-side bound
     slot_off = np.concatenate([[0], np.cumsum(K)]).astype(np.int64)
     S, k_max = int(slot_off[-1]), int(K.max()) if n_jobs else 0

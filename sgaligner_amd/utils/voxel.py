@@ -37,6 +37,10 @@ class VoxelGrid:
             raise ValueError(f'voxel grid: cloud {int(bad[0])}: {STATUS_TEXT.get(int(status[bad[0]]), f"status {int(status[bad[0]])}")}')
         return voff
 
+    def search_args(self):
+        """The six pointers every grid search takes, in the order of the C ABI: cell, origin, dims, status, order, sorted_keys."""
+        return [_p(t) for t in (self.cell, self.origin, self.dims, self.status, self.order, self.sorted_keys)]
+
 
 def _cell_tensor(cell, n_clouds, dev):
     """cell: one edge for every cloud, or one per cloud (sequence, numpy array or tensor) -> ([C] float64 device tensor, host copy or None)."""
@@ -123,8 +127,7 @@ def grid_lists(points, offsets, r2, max_nn, cell=None, radius=None):
     idx = torch.empty((C.total_points, max_nn), device=C.dev, dtype=torch.int32)
     d2 = torch.empty((C.total_points, max_nn), device=C.dev, dtype=torch.float64)
     if C.total_points:
-        rc = _lib.lib().sga_knn_lists_grid(_p(C.pts), *C.args(), _p(G.cell), _p(G.origin), _p(G.dims), _p(G.status), _p(G.order),
-                                           _p(G.sorted_keys), r2, max_nn, _p(count), _p(idx), _p(d2), _stream())
+        rc = _lib.lib().sga_knn_lists_grid(_p(C.pts), *C.args(), *G.search_args(), r2, max_nn, _p(count), _p(idx), _p(d2), _stream())
         _lib.check(rc, 'sga_knn_lists_grid')
     return count, idx, d2
 

@@ -117,6 +117,53 @@ def test_pair_jobs_on_a_hand_written_case():
         PairJobs([0, 2 ** 20], 2 ** 20, np.zeros((2 ** 11, 2), dtype=np.int64), 'caller', 'set')
 
 
+def test_hyp_jobs_on_a_hand_written_case_and_its_refusals(monkeypatch):
+    """HypJobs with the device check waved through (dtype still checked first, as device_tensor does): the fields, and the refusals in the
+    words find_rigid_transform_batch, edge_length_filter and hypothesis_models_batch gave before they shared it."""
+    import torch
+    from sgaligner_amd import packed
+    from sgaligner_amd.packed import HypJobs
+    corr, samples = torch.zeros((10, 6), dtype=torch.float64), torch.zeros((7, 3), dtype=torch.int32)
+    with pytest.raises(RuntimeError, match=r'^sgaligner_amd: `corr` must be torch.float64 \(got torch.float32\)$'):       # dtype before device
+        HypJobs(corr.float(), [0, 10], samples, [0, 7])
+    with pytest.raises(RuntimeError, match=r'^sgaligner_amd: `corr` must be a HIP device tensor .*no CPU path'):
+        HypJobs(corr, [0, 10], samples, [0, 7])
+    monkeypatch.setattr(packed, 'device_tensor', lambda t, name, dtype: (packed.check_dtype(t, name, dtype), t.contiguous())[1])
+    J = HypJobs(corr, [0, 4, 4, 10], samples, [0, 5, 5, 7])
+    assert (J.n_jobs, J.total, J.total_h, J.max_n, J.max_h) == (3, 10, 7, 6, 5)
+    assert J.sizes_n.tolist() == [4, 0, 6] and J.sizes_h.tolist() == [5, 0, 2]
+    assert J.off.dtype == J.hoff.dtype == np.int64 and J.h_off.dtype == J.h_hoff.dtype == np.int32
+    assert J.h_off.tolist() == [0, 4, 4, 10] and J.h_hoff.tolist() == [0, 5, 5, 7] and tuple(J.samples.shape) == (7, 3)
+    E = HypJobs(corr[:0], [0], samples[:0], [0])                                           # no job: nothing to take a maximum of
+    assert (E.n_jobs, E.total, E.total_h, E.max_n, E.max_h) == (0, 0, 0, 0, 0)
+    with pytest.raises(RuntimeError, match=r'^sgaligner_amd: `samples` must be torch.int32 \(got torch.int64\)$'):
+        HypJobs(corr, [0, 10], samples.long(), [0, 7])
+    assert HypJobs(corr, [0, 10], samples.long().numpy(), [0, 7], convert_samples=True).samples.dtype == torch.int32
+    with pytest.raises(ValueError, match=r'^corr must be \[N,6\], got \(12, 5\)$'):
+        HypJobs(torch.zeros((12, 5), dtype=torch.float64), [0, 12], samples, [0, 7])
+    assert HypJobs(torch.zeros((12, 5), dtype=torch.float64), [0, 12], samples, [0, 7], corr_shape=False).total == 12
+    with pytest.raises(ValueError, match=r'^offsets must be a monotone prefix array starting at 0 and covering all 10 entries$'):
+        HypJobs(corr, [0, 6, 4, 10], samples, [0, 5, 5, 7])                                # a non-prefix offsets
+    with pytest.raises(ValueError, match=r'^hyp_offsets must be a monotone prefix array starting at 0 and covering all 7 entries$'):
+        HypJobs(corr, [0, 4, 4, 10], samples, [0, 5, 5, 8])                                # a total that does not match
+    with pytest.raises(ValueError, match=r'^offsets names 3 jobs, hyp_offsets 2$'):
+        HypJobs(corr, [0, 4, 4, 10], samples, [0, 5, 7])                                   # unequal job counts
+    J.check_int32('caller', 3)
+    J.total_h = 2 ** 31 // 12
+    J.check_int32('caller', 3)
+    with pytest.raises(ValueError, match=r'^caller indexes with int32: fewer than 2\^31 / 6 rows and 2\^31 / 12 hypotheses per call$'):
+        J.check_int32('caller', 12)
+
+
+def test_pair_ids_is_the_pair_check_of_pair_jobs():
+    from sgaligner_amd.packed import pair_ids
+    pr = pair_ids([(0, 2), (1, 0)], 3, 'cloud')
+    assert pr.dtype == np.int64 and pr.tolist() == [[0, 2], [1, 0]] and pair_ids(pr) is not None and pair_ids([]).shape == (0, 2)
+    assert pair_ids([(0, 9)]).tolist() == [[0, 9]]                                         # without n_sets: the conversion alone
+    with pytest.raises(ValueError, match=r'^pairs must name clouds in \[0, 2\)$'):
+        pair_ids(pr, 2, 'cloud')
+
+
 def test_resolve_chunk_and_workspace():
     import torch
     from sgaligner_amd.packed import resolve_chunk, workspace

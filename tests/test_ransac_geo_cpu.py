@@ -115,6 +115,23 @@ def test_kernels_use_no_scratch_and_do_not_spill():
     assert len(seen) == 3, seen
 
 
+def test_the_shared_device_code_is_defined_once_in_a_header():
+    """The solver, the wave helpers, the rank sort and the lookups of rigid_solver.h / wave_search.h / pair_jobs.h: a definition (a line
+    that opens with a function qualifier; calls are indented) of any name that ends in theirs exists once, in that header."""
+    import glob
+    import re
+    from sgaligner_amd import _build
+    text = {os.path.basename(f): open(f).read() for f in glob.glob(os.path.join(_build.CSRC, '*.hip')) + glob.glob(os.path.join(_build.CSRC, '*.h'))}
+    shared = {'rigid_solver.h': ['rigid_from_moments'],
+              'wave_search.h': ['wave_sync', 'd2j_less', 'point_d2', 'nn_offer', 'wave_best', 'lower_bound', 'move_point', 'rank_sort'],
+              'pair_jobs.h': ['sga_hyp_job', 'sga_cloud', 'sga_cloud_of_point', 'sga_cloud_pair', 'sga_pair_job']}
+    for header, names in shared.items():
+        for name in names:
+            found = [f for f, s in sorted(text.items()) for _ in re.finditer(rf'^__(?:host|device)__ [^\n;]*\b\w*{name}\(', s, re.M)]
+            assert found == [header], (name, found)
+    assert [f for f, s in sorted(text.items()) if 'offd <=' in s] == ['rigid_solver.h']       # the solver's convergence test, whatever its name
+
+
 def test_the_yardsticks_own_rules():
     assert GR.select_ref([5, 9, 9, -1, 9], [0.1, 0.3, 0.2, np.inf, 0.2]) == 2          # count, then sum d2, then the lowest index
     assert GR.select_ref([2, 2, -1], [0.0, 0.0, np.inf]) == -1 and GR.select_ref([-1, -1], [np.inf, np.inf]) == -1 and GR.select_ref([], []) == -1
