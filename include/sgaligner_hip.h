@@ -200,7 +200,8 @@ int sga_gat_lds_nodes(int channels, int bwd);
  * 32 bits (no saturation, no status word), no atomics: every sum's order is fixed by the structure alone, so the outputs are bitwise
  * repeatable, a graph's out / dH rows are the same bits alone or inside a batch, and nothing depends on the order in which the edge list
  * names the edges.  Limits: 1 <= heads <= 65536, 1 <= channels <= 256 per head, T * heads below 2^31, cap = sum E + T at most 2^31 - 65.  The entry points above (the dense
- * route, at most 256 nodes per graph) are unchanged and remain the default of the Python layer; sga_gcn_aggregate is dense-only.
+ * route, at most 256 nodes per graph) are unchanged and remain the default of the Python layer.  The GCN runs over the same structure
+ * through sga_gcn_sp_dinv / sga_gcn_sp_aggregate (below, with sga_gcn_aggregate).
  *
  * Structure, built on the device once per batch from the inputs of the dense route (T = node_off[G] nodes, E = edge_off[G] listed edges;
  * input self loops and endpoints outside [0, nodes of the graph) dropped, one self loop added per node, duplicates counted), over
@@ -244,7 +245,7 @@ int sga_elu_bwd(const float* x, const float* gy, float* gx, size_t n, void* stre
  * replaces torch_geometric.nn.GCNConv(in, out, cached=False) as src/aligner/networks/gat.py:6-25 (MultiGCN) stacks it, for all graphs of a
  * batch in one launch.  H [T,C] = x W^T (any C >= 1), bias [C] or NULL; edges / node_off / edge_off / nmax / status as for the GAT kernels
  * above (graph-local ids, endpoints out of range dropped, at most 256 nodes per graph -- more is SGA_ERR_ARG --, 8-bit multiplicities
- * with bit 0 of *status set beyond 255 copies of one pair; there is no sparse route for the GCN yet).  Input self loops are removed, every node gets one self loop of weight 1,
+ * with bit 0 of *status set beyond 255 copies of one pair; both limits belong to this dense route, sga_gcn_sp_* below has neither).  Input self loops are removed, every node gets one self loop of weight 1,
  * deg_i = 1 + #{listed j -> i, j != i} (duplicates counted), dinv = deg^-1/2 correctly rounded to fp32, and
  *   transpose == 0:  out[i] = sum_{j -> i} dinv_i dinv_j H[j] + bias      (relu != 0: max(., 0) on top)
  *   transpose != 0:  out[j] = sum_{j -> i} dinv_i dinv_j H[i]             (the backward of the line above; bias NULL, relu 0)
@@ -253,6 +254,23 @@ int sga_elu_bwd(const float* x, const float* gy, float* gx, size_t n, void* stre
 int sga_gcn_aggregate(const float* H, int C, const float* bias, const int64_t* edges, const int32_t* node_off, const int32_t* edge_off,
                       int G, int nmax, int transpose, int relu, float* out, int32_t* status, void* stream);
 int sga_relu_bwd(const float* y, const float* gy, float* gx, size_t n, void* stream);
+/* The SPARSE route of the GCN: the same arithmetic over the structure of sga_gat_sp_rows / sga_gat_sp_cols (batch-global node ids, ascending
+ * neighbours, 32-bit multiplicities, one self loop per node) -- graphs of ANY size, any number of copies of a pair, no status word.
+ *   sga_gcn_sp_dinv       dinv [T]: deg_i = the integer sum of mult over the target-major row of i (the self loop counts 1),
+ *                         dinv_i = (float)(1.0 / sqrt((double)deg_i)), correctly rounded -- once per batch
+ *   sga_gcn_sp_aggregate  one entry point for both directions, by the choice of arrays (ptr [T+1], nbr [cap], mult [cap], perm [cap] or NULL):
+ *     forward    ptr = row_ptr, nbr = src, perm = NULL:   out[i] = sum_{entries e of row i} coef_e H[src_e] + bias   (relu != 0: max(., 0) on top)
+ *     transpose  ptr = col_ptr, nbr = tgt, perm = perm:   out[j] = sum_{entries e of column j} coef_e H[tgt_e], the multiplicity read as
+ *                mult[perm[e]]; bias must be NULL and relu 0 (anything else is SGA_ERR_ARG)
+ *   coef_e = (float)mult_e * (dinv_out * dinv_nbr), two separately rounded multiplies.  Every output element is ONE fmaf chain from 0 in
+ *   ascending neighbour order, the bias added after the chain, then the ReLU: the chain of sga_gcn_aggregate.  For a batch that route can
+ *   take (at most 256 nodes per graph, no pair listed more than 255 times) both routes therefore return THE SAME BITS, in both directions.
+ *   No floating-point atomics; a graph's rows are the same bits alone or inside a batch, whatever the order of the edge list.
+ * H / out [T, C], any C >= 1 (C < 1: SGA_ERR_ARG "width %d < 1"); T < 0, cap < T or cap above 2^31 - 65 is SGA_ERR_ARG; a null pointer or out
+ * aliasing H is refused before any device call; T == 0 is a no-op. */
+int sga_gcn_sp_dinv(const int32_t* row_ptr, const int32_t* mult, int T, int cap, float* dinv, void* stream);
+int sga_gcn_sp_aggregate(const float* H, int C, const float* bias, const int32_t* ptr, const int32_t* nbr, const int32_t* mult,
+                         const int32_t* perm, const float* dinv, int T, int cap, int relu, float* out, void* stream);
 
 /* ---- NCA loss (EVA baseline) --------------------------------------------------------------------------
  * replaces NCALoss.forward, src/aligner/losses.py:161-173, and its autograd, over row blocks of the score matrix s = Z1 Z2^T of the A

@@ -163,6 +163,8 @@ SIGNATURES = {
     'sga_fusion_var_bwd': (I, [P, I, P, P, P, P, P, I, P, c_size_t, P]),
     'sga_gcn_aggregate': (I, [P, I, P, P, P, P, I, I, I, I, P, P, P]),
     'sga_relu_bwd': (I, [P, P, P, c_size_t, P]),
+    'sga_gcn_sp_dinv': (I, [P, P, I, I, P, P]),
+    'sga_gcn_sp_aggregate': (I, [P, I, P, P, P, P, P, P, I, I, I, P, P]),
     'sga_nca_row_group': (I, []),
     'sga_nca_block_sums': (I, [P, c_long, I, I, I, F, F, P, P, P, P]),
     'sga_nca_loss': (I, [P, P, I, P, I, F, F, P, P, P, P, P]),

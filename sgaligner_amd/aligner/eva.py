@@ -13,10 +13,12 @@ from .sg_aligner import MultiModalFusion, _Linear
 class EVA(nn.Module):
     """eva.py:9-96.  `modules` (list of 'gcn' | 'point' | 'rel' | 'attr') is kept as an attribute with the reference's name -- it
     shadows nn.Module.modules(), exactly as in the reference (:12).  The tables keep their own widths (gcn n_units[-1] = 400, point 200,
-    rel / attr emb_dim = 100): the reference has no projection to emb_dim for the first two (:72,:75)."""
+    rel / attr emb_dim = 100): the reference has no projection to emb_dim for the first two (:72,:75).
+    gcn_route (last, so the reference's positional order stands): MultiGCN's route -- 'dense' (default; scenes of at most 256 objects), 'sparse'
+    or 'auto' (scenes of any size)."""
 
     def __init__(self, modules, rel_dim, attr_dim, n_units=[3, 200, 400], emb_dim=100, pt_out_dim=256, dropout=0.0, attn_dropout=0.0,
-                 instance_norm=False):
+                 instance_norm=False, gcn_route='dense'):
         super().__init__()
         self.modules = modules
         self.pt_out_dim = pt_out_dim
@@ -33,7 +35,8 @@ class EVA(nn.Module):
         self.meta_embedding_attr = _Linear(self.attr_dim, self.emb_dim)
         self.object_encoder = PointNetfeat(global_feat=True, batch_norm=True, point_size=3, input_transform=False,
                                            feature_transform=False, out_size=200)                     # eva.py:27
-        self.structure_encoder = MultiGCN(n_units=self.n_units, dropout=self.dropout)
+        self.gcn_route = gcn_route
+        self.structure_encoder = MultiGCN(n_units=self.n_units, dropout=self.dropout, route=gcn_route)
         self.fusion = MultiModalFusion(modal_num=self.inner_view_num, with_weight=1)
 
     def forward(self, data_dict):

@@ -95,21 +95,33 @@ class GCNConv(nn.Module):
 
 
 class MultiGCN(nn.Module):
-    """gat.py:6-25: GCNConv, ReLU, GCNConv (dropout 0)."""
+    """gat.py:6-25: GCNConv layers of any depth (len(n_units) - 1 of them) and width, ReLU between layers and none after the last.  Dropout is
+    out of scope: the reference's default is 0 (eva.py:10), anything else raises NotImplementedError.  The two-layer model on the dense route
+    runs on ops.multi_gcn; every other stack on ops.multi_gcn_layers.
+    route: 'dense' (default; a graph holds at most 256 nodes, a pair at most 255 copies), 'sparse' (the CSR aggregation kernels: graphs of any
+    size -- the same bits as 'dense' wherever that route can run) or 'auto' (per batch: sparse exactly when its largest graph has more than
+    256 nodes)."""
 
-    def __init__(self, n_units=[17, 128, 100], dropout=0.0):
+    def __init__(self, n_units=[17, 128, 100], dropout=0.0, route='dense'):
         super().__init__()
         self.num_layers = len(n_units) - 1
         self.dropout = dropout
+        ops.resolve_route(route)
+        self.route = route
+        if self.num_layers < 1:
+            raise ValueError(f'sgaligner_amd MultiGCN: n_units {list(n_units)} needs at least two entries')
+        if any(int(c) < 1 for c in n_units):
+            raise ValueError(f'sgaligner_amd MultiGCN: widths must be positive, got {list(n_units)}')
         if dropout != 0.0:
             raise NotImplementedError('sgaligner_amd MultiGCN: dropout must be 0.0 (reference default, eva.py:10)')
-        if self.num_layers != 2:
-            raise NotImplementedError('sgaligner_amd MultiGCN: the HIP path implements two layers, n_units=[F, C0, C1] (eva.py:10)')
         self.layer_stack = nn.ModuleList([GCNConv(n_units[i], n_units[i + 1]) for i in range(self.num_layers)])     # gat.py:13-15
 
     def forward_batched(self, x, graph_batch):
         """All graphs of a batch in one launch per layer and direction (x [T,F], graph_batch: ops.GraphBatch)."""
-        return ops.multi_gcn(graph_batch, x, self.layer_stack[0].params(), self.layer_stack[1].params())
+        route = ops.resolve_route(self.route, graph_batch)
+        if route == 'dense' and self.num_layers == 2:
+            return ops.multi_gcn(graph_batch, x, self.layer_stack[0].params(), self.layer_stack[1].params())
+        return ops.multi_gcn_layers(graph_batch, x, [l.params() for l in self.layer_stack], route=route)
 
     def forward(self, x, edges):
         """Reference signature (gat.py:17): one graph, x [N,F], edges [2,E] (row 0 source, row 1 target)."""

@@ -13,5 +13,5 @@ void sga_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* sga_last_error(void) { return g_err; }
-extern "C" int sga_version(void) { return 104; }  // 0.1.4: + the PointNet launch plan (sga_pointnet_plan, sga_pointnet_fwd_lg_ws_bytes)
+extern "C" int sga_version(void) { return 105; }  // 0.1.5: + the sparse GCN route (sga_gcn_sp_dinv, sga_gcn_sp_aggregate)
 extern "C" int sga_device_cus(void) { return sga_num_cus(); }

@@ -311,6 +311,16 @@ class SparseGraph:
         _lib.check(L.sga_gat_sp_cols(_p(skeys_t), _p(order_t), cap, T, _p(self.col_ptr), _p(self.tgt), _p(self.perm), s), 'sga_gat_sp_cols')
         _ev_stop(ev, 'gat_sp_build', (T, E))
 
+    def dinv(self):
+        """deg^-1/2 per node [T] for the GCN over this structure (csrc/gcn_sparse.hip: deg = the row's multiplicities summed, the self loop
+        counting 1; correctly rounded).  Computed at the first call and kept: a GAT batch never pays for it."""
+        d = self.__dict__.get('_dinv')
+        if d is None:
+            d = torch.empty((self.T,), device=self.row_ptr.device, dtype=torch.float32)
+            _lib.check(_lib.lib().sga_gcn_sp_dinv(_p(self.row_ptr), _p(self.mult), self.T, self.cap, _p(d), _stream()), 'sga_gcn_sp_dinv')
+            self._dinv = d
+        return d
+
 
 def _sp_workspace(sp, heads, channels, bwd, dev):
     n = _lib.lib().sga_gat_sp_workspace_bytes(sp.T, sp.cap, heads, channels, int(bwd))

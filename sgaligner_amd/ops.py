@@ -516,7 +516,7 @@ _REEXPORT = {
     'gat_ops': ('GraphBatch', '_attn_fwd', '_attn_bwd', '_elu', 'MultiGATFn', 'multi_gat', 'gat_lds_nodes', '_attn_fwd_hc', '_attn_bwd_hc',
                 'GATLayerFn', 'EluFn', 'multi_gat_layers', 'SparseGraph', '_attn_fwd_sp', '_attn_bwd_sp', 'GATLayerSparseFn',
                 'resolve_route'),
-    'gcn_ops': ('gcn_aggregate', 'MultiGCNFn', 'multi_gcn'),
+    'gcn_ops': ('gcn_aggregate', 'MultiGCNFn', 'multi_gcn', 'GCNLayerFn', 'multi_gcn_layers'),
     'nca_ops': ('NCAFn', 'nca_loss'),
     'rank_ops': ('PairLayout', 'QueryBlocks', 'simrank', 'pair_metrics'),
 }

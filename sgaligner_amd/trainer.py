@@ -186,15 +186,15 @@ class AlignerSteps:
 
 class EVASteps:
     """trainval_eva.py:16-62: the EVA model, OverallNCALoss, Adam over the model parameters (the loss has none), and the step hooks.
-    Single device: the NCA loss is not sharded."""
+    Single device: the NCA loss is not sharded.  gcn_route: EVA's ('dense' | 'sparse' | 'auto': scenes of more than 256 objects)."""
 
-    def __init__(self, modules, rel_dim=41, attr_dim=164, device='cuda', seed=42, lr=1e-3, weight_decay=0.0):
+    def __init__(self, modules, rel_dim=41, attr_dim=164, device='cuda', seed=42, lr=1e-3, weight_decay=0.0, gcn_route='dense'):
         if not torch.cuda.is_available() and str(device).startswith('cuda'):
             raise RuntimeError('sgaligner_amd.EVASteps: no HIP device; the product path has no CPU fallback')
         self.modules = list(modules)
         self.device = torch.device(device)
         torch.manual_seed(seed)
-        self.model = EVA(modules=self.modules, rel_dim=rel_dim, attr_dim=attr_dim).to(self.device)       # :48-52
+        self.model = EVA(modules=self.modules, rel_dim=rel_dim, attr_dim=attr_dim, gcn_route=gcn_route).to(self.device)       # :48-52
         self.loss_func = OverallNCALoss(modules=self.modules, device=self.device)                       # :40
         self.params = list(self.model.parameters())                                                      # :41
         self.optimizer = torch.optim.Adam([{'params': self.params}], lr=lr, weight_decay=weight_decay)   # :44
