@@ -198,8 +198,8 @@ class ContrastiveTermsFn(torch.autograd.Function):
             evb = _ev_start() if all(zh is not None for zh in zhs) else None
             if all16:
                 ws = torch.empty((int(L.sga_loss_anchor_f16_ws_bytes(nt, A, cmax)),), device=dev, dtype=torch.uint8)
-                if any(zh is not None for zh in zhs):
-                    ws16 = torch.empty((int(L.sga_loss_stash_grad_f16_bytes(A, cmax)),), device=dev, dtype=torch.uint8)
+            if any(zh is not None for zh in zhs):      # (a wide table beside narrow ones has its fp16 copy too: all16 is not the condition)
+                ws16 = torch.empty((int(L.sga_loss_stash_grad_f16_bytes(A, cmax)),), device=dev, dtype=torch.uint8)
             for lo, hi in chunks:          # bounded stash: one anchor-row block at a time
                 _lib.check(L.sga_loss_anchor_bwd_f16(_ptr_array(zs), _ptr_array(zhs), dparr, nt, A, _p(sums), ctx.alpha, TAU_ICL, TAU_IAL, _p(coef),
                                                      _ptr_array(m1), _p(gsc), lo, hi, _p(ws) if all16 else None, ws.numel() if all16 else 0, st),

@@ -32,6 +32,11 @@ Gate.  gemm_gate.gate_ok (FLOOR_U and its rms floor unchanged) at r per (stage o
 rms or max, measured on the MI355X over the gate cases): profiles/loss_accuracy_vs_fp32.json, written by tools/loss_accuracy.py;
 test_loss_gate_cpu.py keeps R and the profile together and asserts that the seeded defects FAIL at the r in use.
 
+Tier 'f16' (mode 'f16', tables wider than 128 columns: csrc/wide16.hip, the Zh forms of csrc/loss_pertable.hip's A x A kernels).  The stages
+read fp16 copies of the unit rows: sga_wide16_prepare is pinned bit for bit (prepare_ref), the references are the fp64 stages on zh.double(),
+and the yardstick restates the kernels' arithmetic in float32 torch -- fp32-chunked products of zh.float(), coefficients divided by their
+family's bound and rounded to fp16, the stash scaled by a power of two and rounded to fp16 (the section at the end of this module).
+
 Census.  Rows 2^s e_k: anchors take their class k from the low half of the columns, negatives from the high half, in every table.  Every
 anchor x negative similarity -- fp32 MFMA, three bf16 planes, lite, fp16, and the derived joint -- is exactly 0, every term of the 8 NT global
 sums is exp2(0) = 1 and every sum is the integer (anchors of the shard) x J: torch.equal is legitimate.  With at most CENSUS_COUNT = 8 rows per
@@ -64,7 +69,8 @@ SCALARS = ('sums', 'terms', 'gs', 'gamma', 'gamma_neg', 'head', 'dterms', 'dlv')
 # r per 'stage.output|tier': ceil(2 x the worst measured kernel / yardstick ratio) over the gate cases of profiles/loss_accuracy_vs_fp32.json,
 # at least 1 (the scalar head computes in fp64 and measures 0).
 # Tiers: 'f32' (gather, scatter, the A x A kernels, the head: one arithmetic), and for the sweeps and stash products 'plain' (fp32 MFMA on the
-# plain tables), 'centred' (fp32 MFMA on centred tables), 'planes' (three exact bf16 planes).
+# plain tables), 'centred' (fp32 MFMA on centred tables), 'planes' (three exact bf16 planes); 'f16' (mode 'f16', tables wider than 128 columns:
+# fp16 inputs, fp32 accumulation -- csrc/wide16.hip and the Zh forms of the per-table A x A kernels, against a yardstick in the same arithmetic).
 R = {
     'neg_grad.dZ|centred': 14, 'neg_grad.gamma_neg|centred': 2, 'neg_sums.sums|centred': 5, 'scatter.dE|centred': 3, 'stash_grad.dZ|centred': 9,
     'anchor_coef.dS|f32': 35, 'anchor_coef.gamma|f32': 1, 'anchor_coef.gs|f32': 3, 'anchor_terms.terms|f32': 6, 'gather.Z|f32': 3,
@@ -73,6 +79,7 @@ R = {
     'neg_sums.sums|pertable': 8, 'neg_grad.dZ|plain': 19, 'neg_grad.gamma_neg|plain': 2, 'neg_sums.sums|plain': 5, 'stash_grad.dZ|plain': 31,
     'neg_grad.dZ|planes': 6, 'neg_grad.gamma_neg|planes': 1, 'neg_sums.sums|planes': 4, 'scatter.dE|planes': 3, 'stash_grad.dZ|planes': 3,
     'group.dE|valu': 4, 'group.gamma|valu': 1, 'group.terms|valu': 3, 'neg_grad.dZ|wide': 5,
+    'anchor_coef.dS|f16': 10, 'anchor_coef.gs|f16': 2, 'anchor_terms.terms|f16': 4, 'neg_grad.dZ|f16': 3, 'neg_sums.sums|f16': 2, 'stash_grad.dZ|f16': 3,
 }
 
 
@@ -80,12 +87,16 @@ R = {
 # (test_loss_gate_cpu.py emulates it for every gate case).  Where it cannot -- the coefficients' own float32 error, exp(S / 0.1) amplifying the
 # rounding of S, already sits within r of what the forgotten product adds -- the output is left ungated at that case and listed here;
 # the census and the other cases still cover the kernel.  'output|tier' -> names of the gate cases left out.
+# The tier 'f16' the same way: the three emulated wide16 defects of test_loss_gate_cpu.py (a lost K group in the sums; a lost anchor row and an
+# un-zeroed straddling K group in the negatives' gradient) must fail at every gate case, or the case is listed.
 UNGATED = {
     'neg_grad.dZ|planes': ('cluster-A1-1-1-D37-M4', 'cluster-A31-33-1-D37-M3', 'parallel-A31-33-1-D8-M4', 'parallel-A32-32-32-D8-M3',
                            'cluster-A33-31-65-D97-M4', 'cluster-A63-64-129-D97-M3', 'parallel-A63-64-129-D96-M4',
                            'cluster-A129-21-75-D37-M4', 'cluster-A33-31-65-D8-M2', 'cluster-A257-40-9-D100-M3',
                            'onehot-A65-127-63-D64-M3',),
     'stash_grad.dZ|planes': (),
+    'neg_sums.sums|f16': (),
+    'neg_grad.dZ|f16': ('f16-cluster-A2305-17-0-D136',),      # (one un-zeroed pad column among 2305 anchors; the census runs this shape too)
 }
 
 
@@ -362,14 +373,21 @@ def head(terms, lv_ial, lv_icl, A, z_ial, alpha, zoom, dt=torch.float64):
 
 
 # ------------------------------------------------------------------------------------------------ the stages chained: the whole loss
-def chain_terms(E, beta, idx, A, J1, J2, coef, dt=torch.float64, envelopes=False):
+def chain_terms(E, beta, idx, A, J1, J2, coef, dt=torch.float64, envelopes=False, f16=None):
     """gather -> sums -> A x A terms and coefficients -> stash products -> negatives' gradient -> scatter in `dt` for tables E (beta given:
     the fused form, the joint derived; None: the tables as they are, the last one in the joint's place) and coef = dL/d(terms).  Returns
-    terms, dE per table, gamma = dL/dbeta (fused); envelopes (fp64): every stage's envelope carried into the next one's input error."""
+    terms, dE per table, gamma = dL/dbeta (fused); envelopes (fp64): every stage's envelope carried into the next one's input error.
+    f16 (the float32 yardstick of mode 'f16', per-table form): one flag per table -- a flagged table takes the arithmetic of the tier 'f16':
+    similarities and gradient products from the fp16 rounding of its unit rows, coefficients as f16_coefs, the stash as f16_stash_operand;
+    its scatter reads the float32 rows, as the kernel's does."""
     T = E[0].shape[0]
     n = len(E)
     E = [e.to(dt) for e in E]
     Z, nrm = zip(*[gather(e, idx, dt) for e in E])
+    f16 = list(f16) if f16 is not None else [False] * n
+    assert not any(f16) or (dt == torch.float32 and beta is None and not envelopes)
+    rows = Z                                               # the float32 rows (scatter); Z: what the products read
+    Z = [z.to(torch.float16).to(dt) if h else z for z, h in zip(Z, f16)]
     bt = None if beta is None else beta.to(dt)
     blocks = with_joint([neg_blocks(z, z, A, J1, J2) for z in Z], bt)
     sums = neg_sums(blocks, 0, A)
@@ -385,15 +403,20 @@ def chain_terms(E, beta, idx, A, J1, J2, coef, dt=torch.float64, envelopes=False
     cm, cj, em, ej = neg_coefs(blocks, gs, bt, 0, A, eb, env_gs)
     dE, env_dE = [], []
     for m in range(n):
-        dz = neg_grad_rows(cm[m], Z[m], A, J1, J2)
-        dz[:A] += mm(an['dS'][m], Z[m][A:2 * A].t())
-        dz[A:2 * A] += mm(an['dS'][m].t(), Z[m][:A].t())
+        if f16[m]:
+            bounds = f16_bounds(gs[m])
+            dz = f16_grad_rows(f16_coefs(cm[m], bounds), bounds, Z[m], A, J1, J2)
+            dz[:2 * A] += f16_stash_rows(an['dS'][m], Z[m], A, 0, A, dt)
+        else:
+            dz = neg_grad_rows(cm[m], Z[m], A, J1, J2)
+            dz[:A] += mm(an['dS'][m], Z[m][A:2 * A].t())
+            dz[A:2 * A] += mm(an['dS'][m].t(), Z[m][:A].t())
         env_in = None
         if envelopes:
             env_in = neg_grad_rows(em[m], Z[m], A, J1, J2, True)
             env_in[:A] += an['env_dS'][m] @ Z[m][A:2 * A].abs()
             env_in[A:2 * A] += an['env_dS'][m].t() @ Z[m][:A].abs()
-        de, ee = scatter(dz, None, Z[m], nrm[m], idx, T, dt=dt, env_in=env_in)
+        de, ee = scatter(dz, None, rows[m], nrm[m], idx, T, dt=dt, env_in=env_in)
         dE.append(de)
         env_dE.append(ee)
     res = dict(terms=an['terms_rows'].sum(1), dE=dE)
@@ -569,6 +592,12 @@ def plain_cases():
 def shards3(A):
     """[0, A) in three shards cut off the 32-row grid (fewer for tiny A)."""
     cuts = sorted({0, A} | {c for c in (A // 3 + 1, 2 * A // 3 + 3) if 0 < c < A})
+    return list(zip(cuts[:-1], cuts[1:]))
+
+
+def shards8(A):
+    """shards3 with the cuts moved down to multiples of 8 anchors: where a shard of the wide fp16 kernels may start."""
+    cuts = sorted({0, A} | {lo // 8 * 8 for lo, _ in shards3(A) if 0 < lo // 8 * 8 < A})
     return list(zip(cuts[:-1], cuts[1:]))
 
 
@@ -1254,3 +1283,379 @@ def measure_wide(name):
         stash = torch.full((floats,), NAN, device='cuda')
         lib.check(L.sga_loss_neg_grad_wide(p(z), dp, A, J1, J2, TAU[0], TAU[1], p(g), p(dz), p(stash), floats, st), 'sga_loss_neg_grad_wide')
         yield _row('neg_grad.dZ', 'wide', dz.cpu(), *w['dZ'])
+
+
+# ------------------------------------------------------------------------------------------------ tier 'f16': csrc/wide16.hip and the Zh forms of the per-table A x A kernels
+# Reference: the fp64 stage on what the kernel gets -- zh.double(), the tables AFTER the fp16 rounding (sga_wide16_prepare is pinned bit
+# for bit on its own), the fp32 M1.  Yardstick: float32 torch restating the arithmetic csrc/wide16.hip's header states: fp32-chunked products of
+# zh.float(); coefficients divided by the family's bound and rounded to fp16; M1 scaled by a power of two into [2^13, 2^14) and rounded to
+# fp16.  (Against a plain-fp32 yardstick every ratio would be about 2^13 and gate nothing: hence a tier of its own.)
+# (A, J1, J2, Dp) from the 256 x 256 tile, the 8-row-tile groups of the tile remap, K chunks of 64 and 16-byte K groups, 128-row anchor blocks.
+F16_SHAPES = [
+    dict(A=33, J1=31, J2=65, Dp=136, shards=((0, 8), (8, 24), (24, 33))),     # two K chunks, the second holding one group; shards3 moved to the 8-grid
+    dict(A=129, J1=21, J2=75, Dp=192),                                        # K exactly three chunks; the wave-row split at 128
+    dict(A=257, J1=40, J2=9, Dp=200, forms=('four', 'one', 'rows128', 'one128')),   # row tile edge 256 / 257; the stash-limited forms of the gradient
+    dict(A=65, J1=520, J2=63, Dp=136),                                        # K = J1 > 512 in the anchors' GEMM: a K split is possible
+    dict(A=24, J1=2305, J2=40, Dp=264),                                       # negatives' GEMM: 10 row tiles (groups of 8 and 2) x 2 column tiles, batched with one tile
+    dict(A=2305, J1=17, J2=0, Dp=136, anchors=False),                         # S / COEF passes with 10 row tiles in ONE column of tiles; J2 = 0; no A x A epilogue (2305^2 fp64 autograd)
+    dict(A=2305, J1=257, J2=0, Dp=136, anchors=False),                        # the same with two column tiles: the short group of the remap is a 2 x 2 patch
+    dict(A=40, J1=33, J2=31, Dp=136, shards=((40, 40), (8, 40))),             # an empty shard at a_lo == A, and one that starts off the 32-grid
+]
+F16_ALL_WIDE = (200, 264)                       # the case's own table first: NT = 3, every table with a copy
+F16_MIXED = (100, 136, 64, 264)                 # Zh = (NULL, zh, NULL, zh)
+
+
+def f16_cases():
+    C = []
+    for i, s in enumerate(F16_SHAPES):
+        for kind in ('gauss', 'cluster'):
+            c = dict(s, kind=kind, seed=300 + 10 * i + (kind == 'cluster'))
+            c['name'] = f"f16-{kind}-A{c['A']}-{c['J1']}-{c['J2']}-D{c['Dp']}"
+            C.append(c)
+    return C
+
+
+def f16_case(name):
+    return {c['name']: c for c in f16_cases()}[name]
+
+
+def f16_runs(c):
+    """The anchor ranges a case runs on: whole, then the shards it names."""
+    return [(0, c['A'])] + list(c.get('shards', ()))
+
+
+def f16_partition(c):
+    """The shards a case names, completed to a partition of [0, A) (the A x A terms and dL/d(sums) are judged by the shards' sum)."""
+    out, at = [], 0
+    for lo, hi in sorted(c.get('shards', ())):
+        if lo > at:
+            out.append((at, lo))
+        out.append((lo, hi))
+        at = max(at, hi)
+    return out + ([(at, c['A'])] if at < c['A'] else [])
+
+
+def pad8(n):
+    return (n + 7) // 8 * 8
+
+
+def seg_cols(A, J1, J2):
+    """First padded column of the segments X1 | X2 | N1 | N2 in ZhT and its pitch (csrc/wide16.hip, seg_cols)."""
+    x2 = pad8(A)
+    n1 = x2 + pad8(A)
+    n2 = n1 + pad8(J1)
+    return (0, x2, n1, n2), max(n2 + pad8(J2), 8)
+
+
+def prepare_ref(z, A, J1, J2):
+    """What sga_wide16_prepare makes of z [R, Dp] float32: Zh = fp16(z), round to nearest even, subnormals kept; ZhT [Dp, ldt] its transpose with
+    every segment starting at a multiple of 8 columns and zeros everywhere else."""
+    zh = z.to(torch.float16)
+    starts, ldt = seg_cols(A, J1, J2)
+    zt = torch.zeros(z.shape[1], ldt, dtype=torch.float16)
+    for s0, n, c0 in zip((0, A, 2 * A, 2 * A + J1), (A, A, J1, J2), starts):
+        zt[:, c0:c0 + n] = zh[s0:s0 + n].t()
+    return zh, zt
+
+
+def f16_bounds(gs_row):
+    """The coefficient bound of each sum family, float32: 1.02 (|g0| / tau0 e^(1 / tau0) + |g1| / tau1 e^(1 / tau1))."""
+    g = gs_row.double()
+    e = [torch.exp(torch.tensor(1.0 / t, dtype=torch.float32)) for t in TAU]
+    return [(1.02 * ((g[2 * f] / TAU[0]).float().abs() * e[0] + (g[2 * f + 1] / TAU[1]).float().abs() * e[1])).clamp_min(1e-30) for f in range(4)]
+
+
+def f16_coefs(c32, bounds):
+    """The four families' float32 coefficients as the matrix cores get them: c / bound rounded to fp16."""
+    return [(c / b).to(torch.float16).float() for c, b in zip(c32, bounds)]
+
+
+def f16_grad_rows(ch, bounds, V, A, J1, J2):
+    """neg_grad_rows on the fp16 coefficients, every family's product scaled back by its bound."""
+    x1, x2, n1, n2 = segments(V, A, J1, J2)
+    c11, c12, c22, c21 = ch
+    b11, b12, b22, b21 = bounds
+    return torch.cat([b11 * mm(c11, n1.t()) + b12 * mm(c12, n2.t()), b22 * mm(c22, n2.t()) + b21 * mm(c21, n1.t()),
+                      b11 * mm(c11.t(), x1.t()) + b21 * mm(c21.t(), x2.t()), b12 * mm(c12.t(), x1.t()) + b22 * mm(c22.t(), x2.t())])
+
+
+def f16_stash_operand(m1):
+    """(fp16(2^e M1) as float32, 2^-e): 2^e the power of two that puts the block's largest magnitude into [2^13, 2^14)."""
+    amax = float(m1.abs().max()) if m1.numel() else 0.0
+    if amax == 0.0:
+        return m1.clone(), 1.0
+    ex = math.frexp(amax)[1]
+    return (m1 * 2.0 ** (14 - ex)).to(torch.float16).float(), 2.0 ** (ex - 14)
+
+
+def f16_stash_rows(ds_block, zq, A, lo, hi, dt):
+    """The stash products of the anchor rows [lo, hi): dX1[lo:hi] = dS[lo:hi] X2, dX2 = dS[lo:hi]^T X1[lo:hi] -> [2A, Dp] in dt; float32: on the fp16
+    operand of f16_stash_operand, K walked in chunks of 32."""
+    out = torch.zeros(2 * A, zq.shape[1], dtype=dt)
+    x1, x2 = zq[lo:hi].to(dt), zq[A:2 * A].to(dt)
+    if dt == torch.float64:
+        out[lo:hi] = ds_block.double() @ x2
+        out[A:] = ds_block.double().t() @ x1
+    else:
+        mh, back = f16_stash_operand(ds_block)
+        out[lo:hi] = G.yardstick(mh, x2.t().contiguous()) * back
+        out[A:] = G.yardstick(mh.t().contiguous(), x1.t().contiguous()) * back
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def f16_inputs(name):
+    c = f16_case(name)
+    A, J1, J2, Dp = c['A'], c['J1'], c['J2'], c['Dp']
+    idx, T = index_sets(A, J1, J2, c['seed'])
+    z = gather(tables(c['kind'], T, Dp, 1, c['seed'])[0], idx)[0].float()
+    zh, zt = prepare_ref(z, A, J1, J2)
+    g = torch.Generator().manual_seed(c['seed'])
+    gs = (torch.rand(1, 8, generator=g, dtype=torch.float64) + 0.5) * 1e-3
+    return dict(c, idx=idx, T=T, z=z, zh=zh, zt=zt, gs=gs, R=2 * A + J1 + J2)
+
+
+@functools.lru_cache(maxsize=None)
+def f16_anchor_refs(name, mixed):
+    """The A x A stage of a case's anchors on NT tables: all wide (the case's own table and two more, every one with a copy) or the mixed set
+    (Zh = (NULL, zh, NULL, zh)).  S of a table with a copy is formed from its fp16 rounding, of the others from the float32 rows."""
+    c = f16_inputs(name)
+    A, J1, J2 = c['A'], c['J1'], c['J2']
+    if mixed:
+        widths, Z = F16_MIXED, []
+    else:
+        widths, Z = F16_ALL_WIDE, [c['z']]
+    for k, w in enumerate(widths):
+        Z.append(gather(tables(c['kind'], c['T'], w, 1, c['seed'] + 40 * (k + 1) + int(mixed))[0], c['idx'])[0].float())
+    copy = [z.shape[1] > 128 for z in Z]
+    Zq = [z.to(torch.float16).float() if h else z for z, h in zip(Z, copy)]
+    nt = len(Z)
+    coef = ((torch.rand(nt + 2 * (nt - 1), generator=torch.Generator().manual_seed(c['seed'] + 1)) + 0.5) * 1e-2).float()
+    bl = [neg_blocks(z.double(), z.double(), A, J1, J2) for z in Zq]
+    eb = [neg_blocks(z.double().abs(), z.double().abs(), A, J1, J2) for z in Zq]
+    sums, esum = neg_sums(bl, 0, A), neg_sums_envelope(bl, eb, 0, A)
+    sums = sums.clamp_min(1.0)                             # (J2 == 0 never gets here; any positive numbers of the right size would do)
+    S64 = [mm(z[:A].double(), z[A:2 * A].double()) for z in Zq]
+    eS = [mm(z[:A].double().abs(), z[A:2 * A].double().abs()) for z in Zq]
+    ref = anchor_stage(S64, None, sums, ALPHA, coef, eS=eS, esum=esum)
+    yard = anchor_stage([mm(z[:A], z[A:2 * A]) for z in Zq], None, sums, ALPHA, coef, dt=torch.float32)
+    return dict(Z=Z, copy=copy, coef=coef, sums=sums, ref=ref, yard=yard)
+
+
+def f16_m1(name):
+    """dL/dS [A, A] float32 the stash products are handed: the A x A reference's for the case's own table; without an A x A stage a matrix of the
+    same make, signed coefficients exp(S / tau0) of the case's own similarities."""
+    c = f16_inputs(name)
+    A = c['A']
+    if c.get('anchors', True):
+        return f16_anchor_refs(name, False)['ref']['dS'][0].float()
+    zq = c['zh'].float()
+    sgn = torch.randint(0, 2, (A, A), generator=torch.Generator().manual_seed(c['seed'] + 2)).float() * 2.0 - 1.0
+    return 1e-4 * sgn * torch.exp(mm(zq[:A], zq[A:2 * A]) / TAU[0])
+
+
+@functools.lru_cache(maxsize=None)
+def f16_refs(name):
+    """Sums, negatives' gradient and stash products of a case, per anchor range: (fp64 reference, envelope, float32 yardstick)."""
+    c = f16_inputs(name)
+    A, J1, J2 = c['A'], c['J1'], c['J2']
+    zq = c['zh'].float()
+    z64 = zq.double()
+    bl = {dt: [neg_blocks(zq.to(dt), zq.to(dt), A, J1, J2)] for dt in (torch.float64, torch.float32)}
+    eb = [neg_blocks(z64.abs(), z64.abs(), A, J1, J2)]
+    bounds = f16_bounds(c['gs'][0])
+    m1 = f16_m1(name)
+    out = dict(m1=m1, bounds=bounds)
+    for lo, hi in f16_runs(c):
+        r = {}
+        r['sums'] = (neg_sums(bl[torch.float64], lo, hi)[0], neg_sums_envelope(bl[torch.float64], eb, lo, hi)[0], neg_sums(bl[torch.float32], lo, hi)[0])
+        c64, _, e64, _ = neg_coefs(bl[torch.float64], c['gs'], None, lo, hi, eb)
+        c32, _, _, _ = neg_coefs(bl[torch.float32], c['gs'], None, lo, hi)
+        r['c32'] = c32[0]
+        r['dZ'] = (neg_grad_rows(c64[0], z64, A, J1, J2), neg_grad_rows(e64[0], z64, A, J1, J2, True),
+                   f16_grad_rows(f16_coefs(c32[0], bounds), bounds, zq, A, J1, J2))
+        blk = m1[lo:hi]
+        env = torch.zeros(2 * A, zq.shape[1], dtype=torch.float64)
+        env[lo:hi] = blk.double().abs() @ z64[A:2 * A].abs()
+        env[A:] = blk.double().abs().t() @ z64[lo:hi].abs()
+        r['stash'] = (f16_stash_rows(blk, zq, A, lo, hi, torch.float64), env, f16_stash_rows(blk, zq, A, lo, hi, torch.float32))
+        out[(lo, hi)] = r
+    return out
+
+
+def f16_defect(name, defect):
+    """A CPU emulation of a wide16 kernel with a seeded defect, on the whole anchor range: (output key, out, ref, env, yard), or None where the
+    defect has nothing to act on.
+    'k_group'   S without the last 8-column K group of the table (columns 128 .. 135 of 136), in the sums;
+    'last_row'  the negatives' gradient without the last anchor row of the row block (the C^T products lose their last K index);
+    'straddle'  the straddling K group of the C^T products not zeroed: the column behind the block's last anchor holds a copy of that anchor's
+                coefficients and meets the next packed row of the table (A % 8 == 0: no group straddles)."""
+    c, fr = f16_inputs(name), f16_refs(name)
+    A, J1, J2, Dp = c['A'], c['J1'], c['J2'], c['Dp']
+    r = fr[(0, A)]
+    zq = c['zh'].float()
+    if defect == 'k_group':
+        cut = zq[:, :Dp - 8]
+        return ('neg_sums.sums|f16', neg_sums([neg_blocks(cut, cut, A, J1, J2)], 0, A)[0]) + r['sums']
+    ch = f16_coefs(r['c32'], fr['bounds'])
+    ref, env, yard = r['dZ']
+    bad = yard.clone()
+    b11, b12, b22, b21 = fr['bounds']
+    c11, c12, c22, c21 = ch
+    x1, x2, _, _ = segments(zq, A, J1, J2)
+    if defect == 'last_row':
+        sign, row1, row2 = -1.0, x1[A - 1], x2[A - 1]
+    else:
+        if A % 8 == 0:
+            return None
+        sign, row1, row2 = 1.0, zq[A], zq[2 * A]           # the packed rows behind the last X1 / X2 anchor
+    n1, n2 = slice(2 * A, 2 * A + J1), slice(2 * A + J1, 2 * A + J1 + J2)
+    bad[n1] += sign * (b11 * c11[A - 1][:, None] * row1[None, :] + b21 * c21[A - 1][:, None] * row2[None, :])
+    bad[n2] += sign * (b12 * c12[A - 1][:, None] * row1[None, :] + b22 * c22[A - 1][:, None] * row2[None, :])
+    return 'neg_grad.dZ|f16', bad, ref, env, yard
+
+
+# ---- launches (GPU)
+def run_prepare(z, A, J1, J2):
+    """sga_wide16_prepare on z [R, Dp] float32: (Zh, ZhT) on the device, both pre-filled with NaN."""
+    lib, L, p, _, st = _abi()
+    zc = z.cuda().contiguous()
+    R, Dp = zc.shape
+    ldt = int(L.sga_wide16_ldt(A, J1, J2))
+    zh = torch.full((max(R, 1), Dp), NAN, device='cuda', dtype=torch.float16)
+    zt = torch.full((Dp, ldt), NAN, device='cuda', dtype=torch.float16)
+    lib.check(L.sga_wide16_prepare(p(zc), Dp, A, J1, J2, p(zh), p(zt), st), 'sga_wide16_prepare')
+    return zh, zt
+
+
+@functools.lru_cache(maxsize=2)
+def f16_device(name):
+    """A case's fp16 operands as the library makes them -- and they are prepare_ref's, bit for bit: the references stand on zh.double()."""
+    c = f16_inputs(name)
+    zh, zt = run_prepare(c['z'], c['A'], c['J1'], c['J2'])
+    assert torch.equal(zh.cpu(), c['zh']) and torch.equal(zt.cpu(), c['zt']), 'sga_wide16_prepare differs from prepare_ref'
+    return zh, zt
+
+
+def f16_stash_forms(c):
+    """(label, bytes) of the coefficient stash sga_loss_neg_grad_f16 is given: 'four' holds four stash pairs of all anchors (the families share
+    their launches); 'one' a single pair of all anchors (family by family); 'rows128' four pairs of 128 rows and 'one128' one pair of 128 rows
+    (several anchor-row blocks)."""
+    L = _abi()[1]
+    need = lambda r: int(L.sga_loss_neg_grad_f16_bytes(r, c['J1'], c['J2'])) // 4
+    size = {'four': 4 * need(c['A']), 'one': need(c['A']), 'rows128': 4 * need(128), 'one128': need(128)}
+    return [(f, size[f]) for f in c.get('forms', ('four',))]
+
+
+def _outside_zero(out, A, lo, hi, what):
+    """Anchor rows of X1 / X2 outside the shard hold no gradient of it."""
+    for s0 in (0, A):
+        rows = torch.cat([out[s0:s0 + lo], out[s0 + hi:s0 + A]])
+        assert not rows.any(), f'{what}: anchor rows outside [{lo}, {hi}) written'
+
+
+def measure_f16_sums(name):
+    lib, L, p, _, st = _abi()
+    c, fr = f16_inputs(name), f16_refs(name)
+    zh, _ = f16_device(name)
+    for lo, hi in f16_runs(c):
+        buf = torch.full((_slots() * 8,), NAN, device='cuda', dtype=torch.float64)
+        lib.check(L.sga_loss_neg_sums_f16(p(zh), c['Dp'], c['A'], c['J1'], c['J2'], TAU[0], TAU[1], p(buf), lo, hi, st), 'sga_loss_neg_sums_f16')
+        out = buf[:8].cpu()
+        if hi == lo:
+            assert torch.equal(out, torch.zeros(8, dtype=torch.float64)), 'sums of an empty shard'
+        yield _row('neg_sums.sums', 'f16', out, *fr[(lo, hi)]['sums'])
+
+
+def measure_f16_grad(name):
+    lib, L, p, _, st = _abi()
+    c, fr = f16_inputs(name), f16_refs(name)
+    zh, zt = f16_device(name)
+    A, R, Dp = c['A'], c['R'], c['Dp']
+    g = c['gs'].cuda().contiguous()
+    for form, nbytes in f16_stash_forms(c):
+        for lo, hi in f16_runs(c):
+            dz = torch.zeros(R, Dp, device='cuda')
+            stash = torch.full((nbytes,), 255, device='cuda', dtype=torch.uint8)          # (0xffff: an fp16 NaN)
+            lib.check(L.sga_loss_neg_grad_f16(p(zh), p(zt), Dp, A, c['J1'], c['J2'], TAU[0], TAU[1], p(g), p(dz), p(stash), nbytes, lo, hi, st),
+                      'sga_loss_neg_grad_f16')
+            out = dz.cpu()
+            _outside_zero(out, A, lo, hi, f'{name} {form}')
+            if hi == lo:
+                assert not out.any(), 'gradient of an empty shard'
+            yield _row('neg_grad.dZ', 'f16', out, *fr[(lo, hi)]['dZ'])
+
+
+def measure_f16_stash(name):
+    lib, L, p, _, st = _abi()
+    c, fr = f16_inputs(name), f16_refs(name)
+    _, zt = f16_device(name)
+    A, R, Dp = c['A'], c['R'], c['Dp']
+    for lo, hi in f16_runs(c):
+        dz = torch.zeros(R, Dp, device='cuda')
+        m1 = fr['m1'][lo:hi].t().contiguous().cuda() if hi > lo else torch.zeros(4, device='cuda')
+        nbytes = int(L.sga_loss_stash_grad_f16_bytes(A, hi - lo))
+        ws = torch.full((nbytes,), 255, device='cuda', dtype=torch.uint8)
+        lib.check(L.sga_loss_stash_grad_f16(p(m1), p(zt), Dp, A, c['J1'], c['J2'], p(dz), lo, hi, p(ws), nbytes, st), 'sga_loss_stash_grad_f16')
+        out = dz.cpu()
+        assert not out[2 * A:].any(), 'stash products in the negatives\' rows'
+        assert not out[:lo].any() and not out[hi:A].any(), 'stash products in X1 rows outside the shard'       # (every X2 row is written)
+        if hi == lo:
+            assert not out.any(), 'stash products of an empty shard'
+        yield _row('stash_grad.dZ', 'f16', out[:2 * A], *fr[(lo, hi)]['stash'])
+
+
+def measure_f16_anchor(name, mixed, use_ws):
+    """sga_loss_anchor_fwd_f16 / _bwd_f16 with fp16 copies: the K-loop form (ws = NULL) or the workspace form (similarity blocks first), on
+    the all-wide or the mixed table set, per anchor range."""
+    import ctypes
+    lib, L, p, pa, st = _abi()
+    c, ar = f16_inputs(name), f16_anchor_refs(name, mixed)
+    A, R = c['A'], c['R']
+    nt = len(ar['Z'])
+    n = nt + 2 * (nt - 1)
+    dps = [pad8(z.shape[1]) for z in ar['Z']]
+    zs, zhs = [], []
+    for z, dp, h in zip(ar['Z'], dps, ar['copy']):
+        t = torch.zeros(R + 32, dp)
+        t[:R, :z.shape[1]] = z
+        zs.append(t.cuda())
+        zhs.append(run_prepare(t[:R], A, c['J1'], c['J2'])[0] if h else None)
+    dparr = (ctypes.c_int * nt)(*dps)
+    sums, cf = ar['sums'].cuda().contiguous(), ar['coef'].cuda()
+    ref, yard = ar['ref'], ar['yard']
+    tot = lambda key, d: d[key].sum(-1)
+    for parts in [[(0, A)]] + ([f16_partition(c)] if c.get('shards') else []):
+        terms, gs = torch.zeros(n, dtype=torch.float64), torch.zeros(nt, 8, dtype=torch.float64)
+        for lo, hi in parts:
+            ns = hi - lo
+            nbytes = int(L.sga_loss_anchor_f16_ws_bytes(nt, A, max(ns, 1))) if use_ws else 0
+            ws = torch.full((nbytes,), 255, device='cuda', dtype=torch.uint8) if use_ws else None
+            out = torch.full((_slots() * n,), NAN, device='cuda', dtype=torch.float64)
+            lib.check(L.sga_loss_anchor_fwd_f16(pa(zs), pa(zhs), dparr, nt, A, p(sums), ALPHA, TAU[0], TAU[1], p(out), lo, hi, p(ws), nbytes, st), 'sga_loss_anchor_fwd_f16')
+            m1 = [torch.full((A * max(ns, 1),), NAN, device='cuda') for _ in range(nt)]
+            gsc = torch.full((_slots() + 1, nt, 8), NAN, device='cuda', dtype=torch.float64)
+            lib.check(L.sga_loss_anchor_bwd_f16(pa(zs), pa(zhs), dparr, nt, A, p(sums), ALPHA, TAU[0], TAU[1], p(cf), pa(m1), p(gsc), lo, hi, p(ws), nbytes, st),
+                      'sga_loss_anchor_bwd_f16')
+            if ns == 0:
+                assert not out[:n].any() and not gsc[0].any(), 'terms or dL/d(sums) of an empty shard'
+                assert all(bool(torch.isnan(m).all()) for m in m1), 'a stash written by an empty shard'
+            terms += out[:n].cpu()
+            gs += gsc[0].cpu()
+            for k in range(nt if ns else 0):
+                yield _row('anchor_coef.dS', 'f16', m1[k].view(A, ns).t().cpu(), ref['dS'][k][lo:hi], ref['env_dS'][k][lo:hi], yard['dS'][k][lo:hi])
+        # (a shard's share of a term or of dL/d(sums) is the kernel's own split -- the B direction rides with S[i, j], not with row i -- and
+        # is all-reduced: the shards are judged by their sum)
+        yield _row('anchor_terms.terms', 'f16', terms, tot('terms_rows', ref), tot('env_terms_rows', ref), tot('terms_rows', yard))
+        yield _row('anchor_coef.gs', 'f16', gs, tot('gs_rows', ref), tot('env_gs_rows', ref), tot('gs_rows', yard))
+
+
+def measure_f16(name):
+    """Every gated stage of a case in the tier 'f16'."""
+    yield from measure_f16_sums(name)
+    yield from measure_f16_grad(name)
+    yield from measure_f16_stash(name)
+    if f16_case(name).get('anchors', True):
+        for mixed in (False, True):
+            for use_ws in (False, True):
+                yield from measure_f16_anchor(name, mixed, use_ws)

@@ -80,6 +80,7 @@ def test_gate_ratios_are_the_measured_ones():
     want |= {'scatter.dE|centred', 'scatter.dE|planes'}
     want |= {f'{o}|pertable' for o in ('neg_sums.sums', 'anchor_terms.terms', 'anchor_coef.dS', 'anchor_coef.gs', 'neg_grad.dZ')}
     want |= {f'group.{o}|{t}' for o in ('terms', 'dE', 'gamma') for t in ('mfma', 'valu')} | {'neg_grad.dZ|wide'}
+    want |= {f'{o}|f16' for o in ('neg_sums.sums', 'neg_grad.dZ', 'stash_grad.dZ', 'anchor_terms.terms', 'anchor_coef.dS', 'anchor_coef.gs')}
     assert set(LG.R) == want
 
 
@@ -199,6 +200,67 @@ def test_gate_catches_a_dropped_plane_product(name, which):
     assert five_ok == listed, f'five products {"pass" if five_ok else "fail"} the gate here, but the case is {"" if listed else "not "}listed in UNGATED'
 
 
+# ------------------------------------------------------------------------------------------------ the tier 'f16'
+F16_CASES = [c['name'] for c in LG.f16_cases()]
+F16_DEFECTS = {'neg_sums.sums|f16': ('k_group',), 'neg_grad.dZ|f16': ('last_row', 'straddle')}
+
+
+def f16_defect_verdicts(name, key):
+    """(the clean yardstick passes its own gate, SOME seeded defect of this output passes too) at the r in use."""
+    clean_ok, slipped = True, []
+    for defect in F16_DEFECTS[key]:
+        v = LG.f16_defect(name, defect)
+        if v is None:                                       # no K group straddles the end of a block of A % 8 == 0 anchors
+            assert defect == 'straddle' and LG.f16_case(name)['A'] % 8 == 0
+            continue
+        k, bad, ref, env, yard = v
+        assert k == key
+        clean_ok &= _passes(key, yard, ref, env, yard)[0]
+        ok, ke, ye = _passes(key, bad, ref, env, yard)
+        if ok:
+            slipped.append((defect, ke, ye))
+    return clean_ok, slipped
+
+
+@pytest.mark.parametrize('key', sorted(F16_DEFECTS))
+@pytest.mark.parametrize('name', F16_CASES)
+def test_f16_gate_catches_the_seeded_defects(name, key):
+    """Three emulated wide16 kernels, at every gate case of the tier 'f16': (a) S without the last 8-column K group of the table (columns
+    128 .. 135 of 136) in the sums; (b) the negatives' gradient without the last anchor row of the row block; (c) the straddling K group of
+    the C^T product not zeroed -- a copy of the last anchor's coefficients meets the next packed row.  The clean arithmetic passes; each
+    defect FAILS at the r in use -- or the case is listed in loss_gate.UNGATED for that output, and only then."""
+    clean_ok, slipped = f16_defect_verdicts(name, key)
+    listed = name in LG.UNGATED.get(key, ())
+    assert clean_ok, 'the clean yardstick misses its own gate'
+    assert bool(slipped) == listed, f'{slipped or "every defect fails the gate"}, but the case is {"" if listed else "not "}listed in UNGATED'
+
+
+def test_f16_ungated_cases_are_few():
+    """At most one third of the gate cases of an output may go ungated; the census covers the rest."""
+    for key in F16_DEFECTS:
+        listed = LG.UNGATED.get(key, ())
+        assert set(listed) <= set(F16_CASES) and 3 * len(listed) <= len(F16_CASES), key
+
+
+def test_f16_yardstick_operands():
+    """The float32 restatement of csrc/wide16.hip's operands: ZhT keeps every segment on the 8-column grid with zeros between them; the
+    stash operand's largest magnitude lies in [2^13, 2^14) and the scaling is undone exactly; the coefficients are at most 1 in magnitude."""
+    c = LG.f16_inputs('f16-cluster-A33-31-65-D136')
+    A, J1, J2 = c['A'], c['J1'], c['J2']
+    starts, ldt = LG.seg_cols(A, J1, J2)
+    assert starts == (0, 40, 80, 112) and ldt == 184 and tuple(c['zt'].shape) == (136, ldt)
+    used = torch.zeros(ldt, dtype=torch.bool)
+    for s0, n in zip(starts, (A, A, J1, J2)):
+        used[s0:s0 + n] = True
+    assert not c['zt'][:, ~used].any() and torch.equal(c['zt'][:, :A].t(), c['zh'][:A]) and torch.equal(c['zt'][:, 112:112 + J2].t(), c['zh'][2 * A + J1:])
+    m1 = LG.f16_m1(c['name'])
+    mh, back = LG.f16_stash_operand(m1)
+    assert 2.0 ** 13 <= float(mh.abs().max()) < 2.0 ** 14 + 8 and back == 2.0 ** round(np.log2(back))
+    fr = LG.f16_refs(c['name'])
+    ch = LG.f16_coefs(fr[(0, A)]['c32'], fr['bounds'])
+    assert all(float(x.abs().max()) <= 1.0 for x in ch) and any(float(x.abs().max()) > 0 for x in ch)
+
+
 # ------------------------------------------------------------------------------------------------ the census
 CENSUS_SHAPES = [(33, 31, 65, 37), (129, 21, 75, 64), (65, 127, 63, 97), (257, 40, 9, 100), (333, 17, 50, 100), (32, 32, 32, 104), (63, 64, 129, 101)]
 
@@ -220,6 +282,21 @@ def test_census_conditions_and_integer_sums(A, J1, J2, D, M):
             assert torch.equal(LG.neg_sums(bl, lo, hi), LG.census_sums(hi - lo, J1, J2, M + 1))
     if D <= 100:
         assert not LG.centre_image(Z[0].float(), D)[2]
+
+
+@pytest.mark.parametrize('A,J1,J2', [(33, 31, 65), (129, 21, 75), (65, 127, 63), (257, 40, 9), (333, 17, 50), (63, 64, 129), (24, 2305, 40), (2305, 17, 0), (2305, 257, 0)])
+def test_census_of_136_columns_for_the_fp16_kernels(A, J1, J2):
+    """The 136-column census of the wide fp16 kernels: one-hot rows are their own fp16 rounding, the sums are the integers in whole and in
+    shards on the 8-anchor grid, and where the segments are short enough the counts stay <= 8 in every such shard (J2 = 0 included)."""
+    limited = max(A, J1) <= 400
+    tabs, idx, _, _ = LG.census(A, J1, J2, 136, 1, seed=A + 1, count_limit=limited, shards=[(0, A)] + LG.shards8(A))
+    z = LG.gather(tabs[0], idx)[0]
+    assert torch.equal(z.to(torch.float16).double(), z) and torch.equal(LG.prepare_ref(z.float(), A, J1, J2)[0].double(), z)
+    bl = [LG.neg_blocks(z, z, A, J1, J2)]
+    sh = LG.shards8(A)
+    assert sh[0][0] == 0 and sh[-1][1] == A and all(lo % 8 == 0 and lo < hi for lo, hi in sh) and all(a[1] == b[0] for a, b in zip(sh, sh[1:]))
+    for lo, hi in [(0, A)] + sh:
+        assert torch.equal(LG.neg_sums(bl, lo, hi), LG.census_sums(hi - lo, J1, J2, 1))
 
 
 def test_census_of_the_work_unit_shape_has_integer_sums_only():

@@ -1,7 +1,9 @@
 """GPU: the loss kernels at the C ABI against the fp64 stage references of tests/loss_gate.py -- every stage output of the fused path gated
 at r x the float32 yardstick's envelope-relative error (gate), and the census: exact inputs on which every global sum is an integer and
 every entry of the negatives' gradient a small count times one constant, so that one lost, doubled or misplaced pair shows.  Shapes sit on
-the tile geometry's edges (loss_gate.gate_cases); outputs a kernel must write are pre-filled with NaN."""
+the tile geometry's edges (loss_gate.gate_cases); outputs a kernel must write are pre-filled with NaN.  The wide fp16 kernels (mode 'f16':
+csrc/wide16.hip and the Zh forms of the per-table A x A kernels) have a tier of their own, 'f16' (loss_gate.f16_cases), their operands
+pinned bit for bit, and their routes through ops.contrastive_terms pinned end to end, a batch in shards included."""
 import pytest
 import torch
 
@@ -85,6 +87,63 @@ def test_wide_neg_grad_gate(name):
     LG.assert_gate(LG.measure_wide(name), name)
 
 
+# ------------------------------------------------------------------------------------------------ the wide fp16 kernels (tier 'f16')
+PREPARE_SHAPES = [(1, 1, 1, 136), (33, 31, 65, 136), (63, 64, 129, 200), (65, 0, 7, 264)]
+
+
+@pytest.mark.parametrize('A,J1,J2,Dp', PREPARE_SHAPES)
+def test_wide16_prepare_is_exact(A, J1, J2, Dp):
+    """sga_wide16_prepare, bit for bit: Zh = fp16(z) rounded to nearest even -- ties, values below 2^-14 (fp16 subnormals, kept, not flushed) and
+    below 2^-25 (zero) among the entries --, ZhT[d, r + shift of r's segment] = Zh[r, d] with every segment starting at a multiple of 8 columns,
+    and every other column of ZhT zero (both outputs pre-filled with NaN)."""
+    R = 2 * A + J1 + J2
+    g = torch.Generator().manual_seed(A + Dp)
+    z = torch.randn(R, Dp, generator=g) * torch.ldexp(torch.ones(R, Dp), torch.randint(-27, 1, (R, Dp), generator=g))
+    special = torch.tensor([1.0 + 2.0 ** -11, 1.0 + 3.0 * 2.0 ** -11, -(1.0 + 2.0 ** -11), 2.0 ** -14, 2.0 ** -15, 2.0 ** -24, 2.0 ** -25, 1.5 * 2.0 ** -25,
+                            3.0 * 2.0 ** -25, 2.0 ** -14 - 2.0 ** -25, -(2.0 ** -24), 0.0, -0.0, 1.0, 65504.0, 2.0 ** -26])
+    z.view(-1)[:special.numel()] = special[:z.numel()]
+    z.view(-1)[-special.numel():] = special[:z.numel()].flip(0)
+    zh, zt = LG.run_prepare(z, A, J1, J2)
+    want_h, want_t = LG.prepare_ref(z, A, J1, J2)
+    assert int(((want_h != 0) & (want_h.abs() < 2.0 ** -14)).sum()) >= 3, 'no fp16 subnormal among the expected values'
+    assert tuple(zt.shape) == tuple(want_t.shape)
+    assert torch.equal(zh.cpu().view(torch.int16), want_h.view(torch.int16)), 'Zh is not the round-to-nearest-even fp16 of z'
+    assert torch.equal(zt.cpu().view(torch.int16), want_t.view(torch.int16)), 'ZhT: a transposed entry misplaced, or padding not zero'
+
+
+F16_NAMES = [c['name'] for c in LG.f16_cases()]
+F16_ANCHORED = [c['name'] for c in LG.f16_cases() if c.get('anchors', True)]
+
+
+@pytest.mark.parametrize('name', F16_NAMES)
+def test_f16_neg_sums_gate(name):
+    """sga_loss_neg_sums_f16, whole and per shard; an empty shard returns exact zeros."""
+    LG.assert_gate(LG.measure_f16_sums(name), name, case=name)
+
+
+@pytest.mark.parametrize('name', F16_NAMES)
+def test_f16_neg_grad_gate(name):
+    """sga_loss_neg_grad_f16 per anchor range into a zeroed buffer, with a coefficient stash that holds four pairs -- and at A = 257 one pair
+    (family by family) and 128-row blocks, batched and family by family: anchor rows outside the shard stay zero, an empty shard writes nothing."""
+    LG.assert_gate(LG.measure_f16_grad(name), name, case=name)
+
+
+@pytest.mark.parametrize('name', F16_NAMES)
+def test_f16_stash_grad_gate(name):
+    """sga_loss_stash_grad_f16 per anchor range: the fp32 M1 against zh.double()."""
+    LG.assert_gate(LG.measure_f16_stash(name), name, case=name)
+
+
+@pytest.mark.parametrize('name', F16_ANCHORED)
+@pytest.mark.parametrize('mixed', [False, True])
+@pytest.mark.parametrize('use_ws', [False, True])
+def test_f16_anchor_gate(name, mixed, use_ws):
+    """sga_loss_anchor_fwd_f16 / _bwd_f16 with fp16 copies, in the K-loop form (ws = NULL) and the workspace form, NT = 3 all wide and the
+    mixed set Zh = (NULL, zh, NULL, zh) on widths (100, 136, 64, 264): every element of dL/dS per anchor range; the terms and dL/d(sums) whole
+    and as the sum over the case's shards; an empty shard adds exact zeros and writes no stash."""
+    LG.assert_gate(LG.measure_f16_anchor(name, mixed, use_ws), f'{name} mixed={mixed} ws={use_ws}', case=name)
+
+
 @pytest.mark.parametrize('M,A,seed', LG.HEAD_CASES)
 @pytest.mark.parametrize('f64', [1, 0])
 def test_head_gate(M, A, seed, f64):
@@ -147,22 +206,30 @@ def test_census_sums_per_table(shape):
         assert torch.equal(buf[:8].cpu(), LG.census_sums(hi - lo, J1, J2, 1)[0]), (lo, hi)
 
 
-@pytest.mark.parametrize('shape', CENSUS[:3])
+CENSUS_F16 = CENSUS + [(2305, 17, 0, 136, 1), (2305, 257, 0, 136, 1)]             # S pass of 10 row tiles (a full group of 8 and a short one) x 1 and x 2 column tiles; J2 = 0
+
+
+@pytest.mark.parametrize('shape', CENSUS_F16)
 def test_census_sums_fp16(shape):
-    """sga_loss_neg_sums_f16 (mode 'f16', tables wider than 128 columns): one-hot rows are exact in fp16 too, the sums are the integers."""
+    """sga_loss_neg_sums_f16 (mode 'f16', tables wider than 128 columns): one-hot rows are exact in fp16 too, the sums are the integers --
+    whole, in three shards cut anywhere and in shards on the 8-anchor grid, which add up to the unsharded integers."""
     A, J1, J2, _, M = shape
     D = 136
     lib, L, p, _, st = LG._abi()
-    tabs, idx, _, _ = LG.census(A, J1, J2, D, 1, seed=A + M)
+    tabs, idx, _, _ = LG.census(A, J1, J2, D, 1, seed=A + M, count_limit=A <= 400)          # (2305 anchors over 68 classes: integer sums only)
     R = 2 * A + J1 + J2
     z = LG.gather(tabs[0], idx)[0].float().cuda().contiguous()
     zh = torch.zeros(R, D, device='cuda', dtype=torch.float16)
     zt = torch.zeros(D, int(L.sga_wide16_ldt(A, J1, J2)), device='cuda', dtype=torch.float16)
     lib.check(L.sga_wide16_prepare(p(z), D, A, J1, J2, p(zh), p(zt), st), 'sga_wide16_prepare')
-    for lo, hi in [(0, A)] + LG.shards3(A):
-        buf = torch.full((LG._slots() * 8,), LG.NAN, device='cuda', dtype=torch.float64)
-        lib.check(L.sga_loss_neg_sums_f16(p(zh), D, A, J1, J2, LG.TAU[0], LG.TAU[1], p(buf), lo, hi, st), 'sga_loss_neg_sums_f16')
-        assert torch.equal(buf[:8].cpu(), LG.census_sums(hi - lo, J1, J2, 1)[0]), (lo, hi)
+    for parts in ([(0, A)], LG.shards3(A), LG.shards8(A)):
+        tot = torch.zeros(8, dtype=torch.float64)
+        for lo, hi in parts:
+            buf = torch.full((LG._slots() * 8,), LG.NAN, device='cuda', dtype=torch.float64)
+            lib.check(L.sga_loss_neg_sums_f16(p(zh), D, A, J1, J2, LG.TAU[0], LG.TAU[1], p(buf), lo, hi, st), 'sga_loss_neg_sums_f16')
+            assert torch.equal(buf[:8].cpu(), LG.census_sums(hi - lo, J1, J2, 1)[0]), (lo, hi)
+            tot += buf[:8].cpu()
+        assert torch.equal(tot, LG.census_sums(A, J1, J2, 1)[0]), parts
 
 
 @pytest.mark.parametrize('shape', CENSUS[:4])
@@ -199,6 +266,55 @@ def test_census_gradient_counts_per_table(shape, wide):
         print(f'[census] per-table {shape} wide={wide} shards={len(parts)}: max {e[0]:.3f} u')
         assert e[0] <= LG.CENSUS_U, e
         assert torch.equal(out != 0, ref != 0)
+
+
+@pytest.mark.parametrize('shape', CENSUS[:4] + [(24, 2305, 40, 136, 1), (2305, 17, 0, 136, 1), (2305, 257, 0, 136, 1)])
+def test_census_gradient_counts_fp16(shape):
+    """The third form of test_census_gradient_counts_per_table: sga_loss_neg_grad_f16 on 136-column census tables, unsharded and as shards on
+    the 8-anchor grid replayed into the same buffer ((24, 2305, 40): the negatives' GEMM of 10 row tiles, and (2305, 17, 0), (2305, 257, 0): the coefficient
+    pass of 10 row tiles by one and by two column tiles, J2 = 0; their counts exceed 8, which the fp32 accumulation of equal fp16 terms still holds exactly).  dL/d(sums) is non-zero for ONE sum family at a time, so every non-zero entry is
+    n x c: an integer count n (the fp64 reference's) times one constant c for the whole family.  The zero pattern is the reference's; all
+    entries agree on c to CENSUS_U = 4 u; c is within one fp16 step (2^-10) of gs[f,0] / tau0 + gs[f,1] / tau1 -- the coefficient enters the
+    matrix cores rounded to fp16.  A lost or doubled pair moves an entry by at least 1/8 of itself (1/n of it where the counts are not limited)."""
+    A, J1, J2, _, M = shape
+    D = 136
+    lib, L, p, _, st = LG._abi()
+    limited = max(A, J1) <= 400
+    tabs, idx, _, _ = LG.census(A, J1, J2, D, 1, seed=A + M, count_limit=limited, shards=[(0, A)] + LG.shards8(A))
+    R = 2 * A + J1 + J2
+    z64 = LG.gather(tabs[0], idx)[0]
+    zh, zt = LG.run_prepare(z64.float(), A, J1, J2)
+    assert torch.equal(zh.cpu().double(), z64)
+    nbytes = int(L.sga_loss_neg_grad_f16_bytes(A, J1, J2))
+    bl = [LG.neg_blocks(z64, z64, A, J1, J2)]
+    g0 = (torch.rand(4, 2, generator=torch.Generator().manual_seed(A), dtype=torch.float64) + 0.5) * 1e-3
+    for f in range(4):
+        gs = torch.zeros(1, 8, dtype=torch.float64)
+        gs[0, 2 * f:2 * f + 2] = g0[f] * (-1.0 if f % 2 else 1.0)
+        c_exact = float(gs[0, 2 * f] / LG.TAU[0] + gs[0, 2 * f + 1] / LG.TAU[1])
+        cm, _, _, _ = LG.neg_coefs(bl, gs, None, 0, A)
+        ref = LG.neg_grad_rows(cm[0], z64, A, J1, J2)
+        count = torch.round(ref / c_exact)
+        assert torch.equal(count * c_exact != 0, ref != 0) and float((ref - count * c_exact).abs().max()) <= 1e-12 * abs(c_exact) * float(count.max())
+        g = gs.cuda().contiguous()
+        for parts in ([(0, A)], LG.shards8(A)):
+            dz = torch.zeros(R, D, device='cuda')
+            for lo, hi in parts:
+                stash = torch.full((nbytes,), 255, device='cuda', dtype=torch.uint8)
+                lib.check(L.sga_loss_neg_grad_f16(p(zh), p(zt), D, A, J1, J2, LG.TAU[0], LG.TAU[1], p(g), p(dz), p(stash), nbytes, lo, hi, st), 'sga_loss_neg_grad_f16')
+            out = dz.cpu().double()
+            assert torch.isfinite(out).all()
+            assert torch.equal(out != 0, ref != 0), (f, parts)
+            nz = ref != 0
+            if not nz.any():                               # (a family without negatives: J2 = 0)
+                continue
+            c = out[nz] / count[nz]
+            mid = float(c.median())
+            spread = float((c - mid).abs().max()) / abs(mid) / G.U
+            step = abs(mid - c_exact) / abs(c_exact) * 2.0 ** 10
+            print(f'[census] fp16 {shape} family {f} shards={len(parts)}: c spread {spread:.3f} u, c off the exact constant by {step:.3f} fp16 steps, max count {int(count.max())}')
+            assert spread <= LG.CENSUS_U, (f, parts, spread)
+            assert step <= 1.0, (f, parts, step)
 
 
 @pytest.mark.parametrize('shape,tier', [(s, t) for s in CENSUS for t in ('plain', 'centred', 'planes')] + [(s, 'plain') for s in CENSUS_PLAIN])
@@ -346,6 +462,8 @@ def test_overall_loss_end_to_end(route):
     assert not bad, bad
 
 
+F16_MIXED_ENTRIES = {'sga_loss_gather', 'sga_loss_neg_sums_shard', 'sga_loss_neg_sums_f16', 'sga_loss_anchor_fwd_f16', 'sga_loss_anchor_bwd_f16', 'sga_loss_stash_grad',
+                     'sga_loss_stash_grad_f16', 'sga_loss_neg_grad_shard', 'sga_loss_neg_grad_f16', 'sga_loss_scatter'}
 PER_TABLE_ROUTES = {
     # name: (table widths, the last standing for the joint; ops.WIDE_STASH; the loss entry points that must run -- exactly)
     'narrow': ((100, 37, 64, 120), True, {'sga_loss_gather', 'sga_loss_neg_sums_shard', 'sga_loss_anchor_fwd_f16', 'sga_loss_anchor_bwd_f16', 'sga_loss_stash_grad',
@@ -354,17 +472,48 @@ PER_TABLE_ROUTES = {
                                     'sga_loss_neg_grad_shard', 'sga_loss_neg_grad_wide', 'sga_loss_scatter'}),
     'wide-multipass': ((100, 97, 300), False, {'sga_loss_gather', 'sga_loss_neg_sums_shard', 'sga_loss_anchor_fwd_f16', 'sga_loss_anchor_bwd_f16',
                                                'sga_loss_stash_grad', 'sga_loss_neg_grad_shard', 'sga_loss_scatter'}),
+    # mode 'f16' (a fourth entry: the mfma mode): tables wider than 128 columns take their fp16 copies through csrc/wide16.hip
+    'f16-all-wide': ((136, 264, 400), True, {'sga_loss_gather', 'sga_loss_neg_sums_f16', 'sga_loss_anchor_fwd_f16', 'sga_loss_anchor_bwd_f16', 'sga_loss_stash_grad_f16',
+                                             'sga_loss_neg_grad_f16', 'sga_loss_scatter'}, 'f16'),
+    'f16-mixed': ((100, 120, 220), True, F16_MIXED_ENTRIES, 'f16'),                     # two narrow tables and their wide joint
+    'f16-mixed-first-wide': ((264, 100, 364), True, F16_MIXED_ENTRIES, 'f16'),
 }
+F16_KEYS = ('anchor_terms.terms|f16', 'neg_sums.sums|f16', 'anchor_coef.dS|f16', 'anchor_coef.gs|f16', 'neg_grad.dZ|f16', 'stash_grad.dZ|f16')
+
+
+def _route_gates(f16):
+    """(r of the terms, r of dE): the largest r of the stages that feed each output on a per-table route."""
+    r = lambda *keys: max(LG.R[k] for k in keys)
+    r_terms = r('anchor_terms.terms|pertable', 'neg_sums.sums|pertable')
+    r_de = r('anchor_coef.dS|pertable', 'anchor_coef.gs|pertable', 'neg_grad.dZ|pertable', 'neg_grad.dZ|wide', 'stash_grad.dZ|plain', 'scatter.dE|f32', 'gather.Z|f32',
+             'neg_sums.sums|pertable')
+    if f16:
+        r_terms = max(r_terms, r(*F16_KEYS[:2]))
+        r_de = max(r_de, r(*F16_KEYS[1:]))
+    return r_terms, r_de
+
+
+def _gate_rows(what, rows):
+    bad = []
+    for name, got, rf, env, yd, rr, scalar in rows:
+        ke, ye = LG.errors(got, rf, env), LG.errors(yd, rf, env)
+        print(f'[loss gate] per-table {what} {name}: kernel max {ke[0]:.3f} u rms {ke[1]:.4f} u | fp32 yardstick max {ye[0]:.3f} u rms {ye[1]:.4f} u | r = {rr}')
+        if not LG.gate_ok(ke, ye, rr, scalar):
+            bad.append((name, ke[:2], ye[:2], rr))
+    assert not bad, bad
 
 
 @pytest.mark.parametrize('route', sorted(PER_TABLE_ROUTES))
 def test_contrastive_terms_end_to_end(route):
-    """ops.contrastive_terms (any joint table) on the narrow route, the wide one (coefficient stash + GEMMs) and the wide multi-pass sweep:
-    the raw terms and dE of every table against the fp64 chain of the per-table stages, at the largest r of the stages that feed them."""
+    """ops.contrastive_terms (any joint table) on the narrow route, the wide one (coefficient stash + GEMMs), the wide multi-pass sweep and,
+    in mode 'f16', all tables wide and the two mixed sets (a narrow table beside a wide one: fp16 copies for some tables only): the raw terms
+    and dE of every table against the fp64 chain of the per-table stages, at the largest r of the stages that feed them.  The yardstick of a
+    table with an fp16 copy is the float32 chain in the arithmetic of the tier 'f16'."""
     import numpy as np
     from sgaligner_amd import _lib, ops
     from sgaligner_amd.synthetic import make_batch
-    widths, wide_stash, expect = PER_TABLE_ROUTES[route]
+    widths, wide_stash, expect, *mode = PER_TABLE_ROUTES[route]
+    mode = mode[0] if mode else ops.get_mfma_mode()
     dd = make_batch(6, 30, 1, seed=4, ragged=True)
     idx = torch.cat([torch.as_tensor(np.asarray(dd[k]), dtype=torch.int32) for k in ('e1i', 'e2i', 'e1j', 'e2j')])
     A, J1, J2 = len(dd['e1i']), len(dd['e1j']), len(dd['e2j'])
@@ -373,32 +522,101 @@ def test_contrastive_terms_end_to_end(route):
     E = [torch.randn(T, d, generator=g) for d in widths]
     nt = len(E)
     coef = (torch.rand(nt + 2 * (nt - 1), generator=g) + 0.5) * 1e-2
+    copies = [mode == 'f16' and d > 128 for d in widths]
     ref = LG.chain_terms(E, None, idx, A, J1, J2, coef, envelopes=True)
-    yard = LG.chain_terms(E, None, idx, A, J1, J2, coef, dt=torch.float32)
+    yard = LG.chain_terms(E, None, idx, A, J1, J2, coef, dt=torch.float32, f16=copies)
     tabs = [e.cuda().requires_grad_(True) for e in E]
-    keep, real = ops.WIDE_STASH, _lib.lib()
+    keep, keep_mode, real = ops.WIDE_STASH, ops.get_mfma_mode(), _lib.lib()
     rec = _Recorder(real)
     try:
         ops.WIDE_STASH = wide_stash
+        ops.set_mfma_mode(mode)
         _lib._lib = rec
         out, _ = ops.contrastive_terms(tabs, dd)
         (out * coef.cuda()).sum().backward()
         torch.cuda.synchronize()
     finally:
         _lib._lib = real
+        ops.set_mfma_mode(keep_mode)
         ops.WIDE_STASH = keep
     ran = {n for n in rec.called if n.startswith('sga_loss_') and not n.endswith(('_slots', '_bytes', '_floats'))}
     assert ran == expect, (sorted(ran - expect), sorted(expect - ran))
-    r = lambda *keys: max(LG.R[k] for k in keys)
-    r_terms = r('anchor_terms.terms|pertable', 'neg_sums.sums|pertable')
-    r_de = r('anchor_coef.dS|pertable', 'anchor_coef.gs|pertable', 'neg_grad.dZ|pertable', 'neg_grad.dZ|wide', 'stash_grad.dZ|plain', 'scatter.dE|f32', 'gather.Z|f32',
-             'neg_sums.sums|pertable')
+    r_terms, r_de = _route_gates(any(copies))
     rows = [('e2e.terms', out.detach().double().cpu(), ref['terms'], ref['env_terms'], yard['terms'], r_terms, True)]
     rows += [(f'e2e.dE[{k}]', tabs[k].grad, ref['dE'][k], ref['env_dE'][k], yard['dE'][k], r_de, False) for k in range(nt)]
-    bad = []
-    for what, got, rf, env, yd, rr, scalar in rows:
-        ke, ye = LG.errors(got, rf, env), LG.errors(yd, rf, env)
-        print(f'[loss gate] per-table {route} {what}: kernel max {ke[0]:.3f} u rms {ke[1]:.4f} u | fp32 yardstick max {ye[0]:.3f} u rms {ye[1]:.4f} u | r = {rr}')
-        if not LG.gate_ok(ke, ye, rr, scalar):
-            bad.append((what, ke[:2], ye[:2], rr))
-    assert not bad, bad
+    _gate_rows(route, rows)
+
+
+def test_contrastive_terms_f16_mixed_in_shards():
+    """The route 'f16-mixed' with the anchors of a batch (A = 55: not a multiple of 8) in three shards, (0, 32), (32, A) and the empty (A, A)
+    -- the few-anchors case of the trainer's shard cuts --, the all-reduce emulated by evaluating the shards one after another with the
+    totals of the earlier passes: the shares of the terms add up to the unsharded terms and the table gradients to the unsharded
+    gradients, within the route's gate against the fp64 chain; the empty shard's shares are exact zeros; a wide table with a non-empty
+    shard that starts off the 8-anchor grid raises."""
+    import numpy as np
+    from sgaligner_amd import ops
+    from sgaligner_amd.synthetic import make_batch
+    widths = PER_TABLE_ROUTES['f16-mixed'][0]
+    dd = make_batch(5, 40, 1, seed=4, ragged=True)
+    idx = torch.cat([torch.as_tensor(np.asarray(dd[k]), dtype=torch.int32) for k in ('e1i', 'e2i', 'e1j', 'e2j')])
+    A, J1, J2 = len(dd['e1i']), len(dd['e1j']), len(dd['e2j'])
+    assert A > 32 and A % 8
+    T = int(np.asarray(dd['tot_obj_count']).sum())
+    g = torch.Generator().manual_seed(55)
+    E = [torch.randn(T, d, generator=g) for d in widths]
+    nt = len(E)
+    coef = (torch.rand(nt + 2 * (nt - 1), generator=g) + 0.5) * 1e-2
+    copies = [d > 128 for d in widths]
+    ref = LG.chain_terms(E, None, idx, A, J1, J2, coef, envelopes=True)
+    yard = LG.chain_terms(E, None, idx, A, J1, J2, coef, dt=torch.float32, f16=copies)
+    shards = [(0, 32), (32, A), (A, A)]
+
+    def run(shard, reduce):
+        tabs = [e.cuda().requires_grad_(True) for e in E]
+        out, _ = ops.contrastive_terms(tabs, dd, shard=shard, reduce=reduce)
+        (out * coef.cuda()).sum().backward()
+        torch.cuda.synchronize()
+        return out.detach().double().cpu(), [t.grad.cpu() for t in tabs]
+
+    keep_mode = ops.get_mfma_mode()
+    try:
+        ops.set_mfma_mode('f16')
+        whole = run(None, None)
+        # the in-place SUM all-reduce of three ranks, one rank after another: pass p knows the totals of the reductions before the p-th
+        # (forward: the sums, the terms; backward: dL/d(sums)) and collects the ranks' shares of the p-th
+        totals, shares = [], []
+        for _ in range(4):
+            pending, results = [], []
+            for rank, shard in enumerate(shards):
+                calls = [0]
+
+                def reduce(t, rank=rank, calls=calls):
+                    k = calls[0]
+                    calls[0] += 1
+                    if k == len(totals):
+                        pending.append(t.detach().clone())
+                    if k < len(totals):
+                        t.copy_(totals[k])
+                results.append(run(shard, reduce))
+            if pending:
+                assert len(pending) == len(shards)
+                shares.append(pending)
+                totals.append(sum(pending))
+        assert len(totals) == 3, 'contrastive_terms reduces the sums, the terms and dL/d(sums)'
+        with pytest.raises(RuntimeError, match='multiple of 8'):
+            run((5, A), None)
+    finally:
+        ops.set_mfma_mode(keep_mode)
+    r_terms, r_de = _route_gates(True)
+    n = nt + 2 * (nt - 1)
+    terms = totals[1][:n].double().cpu()
+    dE = [sum(res[1][k] for res in results) for k in range(nt)]
+    rows = [('whole.terms', whole[0], ref['terms'], ref['env_terms'], yard['terms'], r_terms, True), ('shards.terms', terms, ref['terms'], ref['env_terms'], yard['terms'], r_terms, True)]
+    rows += [(f'whole.dE[{k}]', whole[1][k], ref['dE'][k], ref['env_dE'][k], yard['dE'][k], r_de, False) for k in range(nt)]
+    rows += [(f'shards.dE[{k}]', dE[k], ref['dE'][k], ref['env_dE'][k], yard['dE'][k], r_de, False) for k in range(nt)]
+    _gate_rows('f16-mixed in shards', rows)
+    for res in results:                                    # every rank returns the all-reduced terms
+        assert torch.equal(res[0], results[0][0])
+    empty = len(shards) - 1
+    assert all(not share[empty].any() for share in shares), 'the empty shard adds to a global sum, a term or dL/d(sums)'
+    assert all(not d.any() for d in results[empty][1]), 'the empty shard has a table gradient'
