@@ -506,6 +506,27 @@ int sga_pct_attention(const float* Q, long ldq, const float* V, long ldv, int T,
 /* backward of sga_pct_attention (autograd of pct.py:211-222): stats as left by the forward, work = T*N floats */
 int sga_pct_attention_bwd(const float* Q, long ldq, const float* V, long ldv, const float* dXs, long ldd, int T, int N,
                           const float* stats, float* work, float* dQ, long ldo, float* dV, long ldw, void* stream);
+/* Offset attention, OA.forward (pct.py:261-269), for T objects of N >= 1 points each (T = 0: nothing is done).  Against sga_pct_attention:
+ * no 1/sqrt(32), and the row softmax is L1-normalised over its COLUMNS before it is applied:
+ *   E = Q Q^T,  P[i,j] = exp(E[i,j] - m_i) / l_i,  d_j = 1e-9f + sum_i P[i,j],  Xr[j,:] = (sum_i P[i,j] V[i,:]) / d_j.
+ * The same kernels as sga_pct_attention (csrc/pct.hip, templated on the variant): the row-statistics pass, then the apply pass, whose lane
+ * owns output row j, also adds up its column of P in-lane and divides at the end.  Exact fp32 MFMA, no atomics: an object's outputs have
+ * the same bits alone and in a batch.
+ *   Q [T*N,32], V [T*N,128], Xr [T*N,128] with their row strides (Q and V rows 16-byte aligned);  stats: 3*T*N floats, m | l | d;
+ *   X (nullable) [T*N,128]: the layer's input;  Diff (nullable, needs X): X - Xr, the operand of trans_conv (pct.py:270).
+ * sga_pct_offset_attention_bwd, with G = gsign * (the caller's gradient) = dL/dXr (gsign = -1 for a caller that holds dL/dDiff):
+ *   Gh[j] = G[j] / d_j,  kappa_j = -<G[j], Xr[j]> / d_j,  dV[i] = sum_j P[i,j] Gh[j],  dP[i,j] = <V[i], Gh[j]> + kappa_j,
+ *   delta_i = <V[i], dV[i]> + sum_j P[i,j] kappa_j,  dE = P (dP - delta_i),  dQ[i] = sum_j (dE[i,j] + dE[j,i]) Q[j].
+ *   stats as left by the forward;  work: exactly T*N*130 floats, 16-byte aligned (Gh [T*N,128] | kappa [T*N] | delta [T*N]).
+ * sga_segment_mean: G[t,c] = mean over the N points of object t (SPCT's x_mean, pct.py:349) in a fixed order -- four row walkers
+ *   (rows n, n+4, ...) folded 0,1,2,3 -- and sga_segment_mean_bwd: dY[t*N + n, c] = dG[t,c] / N. */
+int sga_pct_offset_attention(const float* Q, long ldq, const float* V, long ldv, const float* X, long ldxi, int T, int N, float* stats,
+                             float* Xr, long ldx, float* Diff, long ldf, void* stream);
+int sga_pct_offset_attention_bwd(const float* Q, long ldq, const float* V, long ldv, const float* Xr, long ldx, const float* G, long ldg,
+                                 float gsign, int T, int N, const float* stats, float* work, float* dQ, long ldo, float* dV, long ldw,
+                                 void* stream);
+int sga_segment_mean(const float* Y, long ldy, int T, int N, int C, float* G, void* stream);
+int sga_segment_mean_bwd(const float* dG, int T, int N, int C, float* dY, long ldd, void* stream);
 int sga_segment_max(const float* Y, long ldy, int T, int N, int C, float* G, int32_t* argmax, void* stream);
 int sga_segment_max_bwd(const float* dG, const int32_t* argmax, int T, int N, int C, float* dY, long ldd, void* stream);
 /* Backward of conv(512->1024, no bias) + BatchNorm + LeakyReLU(slope) + max over an object's points (pct.py:282-286,306-308) without the

@@ -62,6 +62,10 @@ SIGNATURES = {
     'sga_gemm_ex': (I, [I, I, I, I, I, P, c_long, P, c_long, P, c_long, P, I, P, c_long, P]),
     'sga_pct_attention': (I, [P, c_long, P, c_long, I, I, P, P, c_long, P]),
     'sga_pct_attention_bwd': (I, [P, c_long, P, c_long, P, c_long, I, I, P, P, P, c_long, P, c_long, P]),
+    'sga_pct_offset_attention': (I, [P, c_long, P, c_long, P, c_long, I, I, P, P, c_long, P, c_long, P]),
+    'sga_pct_offset_attention_bwd': (I, [P, c_long, P, c_long, P, c_long, P, c_long, c_float, I, I, P, P, P, c_long, P, c_long, P]),
+    'sga_segment_mean': (I, [P, c_long, I, I, I, P, P]),
+    'sga_segment_mean_bwd': (I, [P, I, I, I, P, c_long, P]),
     'sga_segment_max': (I, [P, c_long, I, I, I, P, P, P]),
     'sga_segment_max_bwd': (I, [P, P, I, I, I, P, c_long, P]),
     'sga_pct_head_prep': (I, [P, P, P, P, P, I, I, c_long, I, c_float, P, P, P]),

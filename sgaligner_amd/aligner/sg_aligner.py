@@ -58,10 +58,11 @@ class MultiModalEncoder(nn.Module):
     with the reference's name -- it shadows nn.Module.modules(), exactly as in the reference (:41)."""
 
     def __init__(self, modules, rel_dim, attr_dim, hidden_units=[3, 128, 128], heads=[2, 2], emb_dim=100,
-                 pt_out_dim=256, dropout=0.0, attn_dropout=0.0, instance_norm=False, gat_route='dense'):
+                 pt_out_dim=256, dropout=0.0, attn_dropout=0.0, instance_norm=False, gat_route='dense', pct_attention='sa'):
         super().__init__()
         self.modules = modules
         self.gat_route = gat_route          # MultiGAT's route: 'dense' | 'sparse' | 'auto' (graphs of more than 256 nodes need the sparse one)
+        self.pct_attention = pct_attention  # NaivePCT's attention: 'sa' (the reference's) | 'oa' (offset attention, the trunk of SPCT)
         self.pt_out_dim = pt_out_dim
         self.rel_dim = rel_dim
         self.emb_dim = emb_dim
@@ -79,7 +80,7 @@ class MultiModalEncoder(nn.Module):
             self.object_encoder = PointNetfeat(global_feat=True, batch_norm=True, point_size=3, input_transform=False,
                                                feature_transform=False, out_size=self.pt_out_dim)
         elif 'pct' in self.modules:
-            self.object_encoder = NaivePCT()                             # sg_aligner.py:59-60 (eval and training: pct_ops.py)
+            self.object_encoder = NaivePCT(attention=pct_attention)    # sg_aligner.py:59-60 (eval and training: pct_ops.py)
         else:
             raise NotImplementedError                                   # sg_aligner.py:61-62
         self.object_embedding = _Linear(self.pt_out_dim, self.emb_dim)

@@ -85,16 +85,29 @@ __global__ __launch_bounds__(PA_THREADS) void attn_stats_kernel(const float* __r
 // ---- pass 2: Xs[j, :] = sum_i exp(scale (E[i,j] - m_i)) / l_i * V[i, :]
 constexpr int QS = 36;                 // LDS row strides (floats): 16-byte aligned, spread over the banks
 constexpr int VS = DV + 4;
-constexpr int BUF_F = 32 * QS + 32 * VS + 64;       // Q tile, V tile, m[32], 1/l[32]
+constexpr int buf_f(bool oa) { return 32 * QS + 32 * VS + 64 + (oa ? 32 : 0); }      // Q tile, V tile, m[32], 1/l[32] (+ kappa[32])
+constexpr float OA_EPS = 1e-9f;        // pct.py:267: the Python float 1e-9 added to a float32 tensor
+
+// What offset attention (OA, pct.py:261-269: no 1/sqrt(da), and the softmax L1-normalised over its COLUMNS afterwards) adds to a launch
+// of the kernels below; the SA instantiations never read it.
+struct OaArgs {
+    const float* kappa;                // backward: kappa_j = dL/dc_j                                                     [T*N]
+    float* aux;                        // forward: d_j = eps + sum_i P[i,j] out;  backward own-row pass: sum_j P[i,j] kappa_j out  [T*N]
+    const float* X; long ldxi;         // forward, nullable: the layer input, for Diff
+    float* Diff; long ldf;             // forward, nullable: X - Xr
+};
 
 // OWN == false (forward):  out[own j, :] = sum_{tile i} exp(s (E[i,j] - m_i)) / l_i * V[i, :]          (tile-row statistics)
 // OWN == true  (backward):  out[own i, :] = sum_{tile j} exp(s (E[i,j] - m_i)) / l_i * dXs[j, :] = dV[i]  (own-row statistics)
-template <bool OWN>
+// OA, forward: the lane also adds up its column of p, c_j, and the rows leave divided by d_j = eps + c_j (and subtracted from X);
+// OA, own-row pass: the lane also accumulates sum_j p[i,j] kappa_j, the second term of the softmax backward's delta_i.
+template <bool OWN, bool OA>
 __global__ __launch_bounds__(PA_THREADS) void attn_apply_kernel(const float* __restrict__ Q, long ldq,
                                                                 const float* __restrict__ V, long ldv, int T, int N,
                                                                 float scale, const float* __restrict__ mstat,
                                                                 const float* __restrict__ lstat,
-                                                                float* __restrict__ Xs, long ldx) {
+                                                                float* __restrict__ Xs, long ldx, OaArgs oa) {
+    constexpr int BUF_F = buf_f(OA);
     __shared__ __attribute__((aligned(16))) float lds[2 * BUF_F];
     const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, l31 = lane & 31;
     const int j0 = (blockIdx.y * 4 + wave) * 32;                // this wave's 32 output rows (may be past N: idle wave)
@@ -110,6 +123,7 @@ __global__ __launch_bounds__(PA_THREADS) void attn_apply_kernel(const float* __r
     const float rl_own = OWN ? 1.f / lt[min(j0 + l31, N - 1)] : 0.f;
     f32x16 out[4];
     zero_acc<4>(out);
+    float colacc = 0.f;                                         // OA: c_j (forward) / sum_j p[i,j] kappa_j (own-row pass), this half's share
 
     auto stage = [&](int i0, float* buf) {                      // rows [i0, i0+32) of Q, V and the row statistics
         {
@@ -129,6 +143,7 @@ __global__ __launch_bounds__(PA_THREADS) void attn_apply_kernel(const float* __r
             // clamped row overflows to inf, and inf * 0 is NaN)
             buf[32 * QS + 32 * VS + tid] = ok ? mt[i0 + tid] : INFINITY;
             buf[32 * QS + 32 * VS + 32 + tid] = ok ? (OWN ? 1.f : 1.f / lt[i0 + tid]) : 0.f;
+            if constexpr (OA && OWN) buf[32 * QS + 32 * VS + 64 + tid] = ok ? oa.kappa[(size_t)t * N + i0 + tid] : 0.f;
         }
     };
 
@@ -158,6 +173,14 @@ __global__ __launch_bounds__(PA_THREADS) void attn_apply_kernel(const float* __r
             for (int u = 0; u < 4; ++u)
                 acc[4 * g + u] = OWN ? __builtin_amdgcn_exp2f((acc[4 * g + u] - m_own) * c) * (rl_own * r4[u])
                                      : __builtin_amdgcn_exp2f((acc[4 * g + u] - m4[u]) * c) * r4[u];
+            if constexpr (OA && OWN) {
+                const f32x4 k4 = *reinterpret_cast<const f32x4*>(ms + 64 + 8 * g + 4 * h);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) colacc += acc[4 * g + u] * k4[u];
+            } else if constexpr (OA) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) colacc += acc[4 * g + u];
+            }
         }
         // Xs[j, :] += sum_i p[i,j] V[i, :]   (A = p from the accumulators, B = V rows from LDS)
         const float* vs = buf + 32 * QS + l31;
@@ -170,6 +193,30 @@ __global__ __launch_bounds__(PA_THREADS) void attn_apply_kernel(const float* __r
     }
     if (j0 >= N) return;
     float* xo = Xs + (size_t)t * N * ldx;
+    if constexpr (OA) {
+        colacc += __shfl_xor(colacc, 32, 64);                   // the two halves hold disjoint tile rows of the same own row
+        if constexpr (!OWN) colacc = OA_EPS + colacc;           // d_j, a float32 add as in the reference
+        if (h == 0 && j0 + l31 < N) oa.aux[(size_t)t * N + j0 + l31] = colacc;
+    }
+    if constexpr (OA && !OWN) {
+        // the lane holds d of row j0 + l31, its registers rows j0 + mfma32_row(r, h): one cross-lane read per register
+        const float* xi = oa.X ? oa.X + (size_t)t * N * oa.ldxi : nullptr;
+        float* df = oa.Diff ? oa.Diff + (size_t)t * N * oa.ldf : nullptr;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float dj = __shfl(colacc, mfma32_row(r, h), 64);
+            const int j = j0 + mfma32_row(r, h);
+            if (j < N) {
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct) {
+                    const float xr = out[ct][r] / dj;
+                    xo[(size_t)j * ldx + ct * 32 + l31] = xr;
+                    if (df) df[(size_t)j * oa.ldf + ct * 32 + l31] = xi[(size_t)j * oa.ldxi + ct * 32 + l31] - xr;
+                }
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
@@ -180,6 +227,8 @@ __global__ __launch_bounds__(PA_THREADS) void attn_apply_kernel(const float* __r
 }
 
 // ---- delta_i = <V[i, :], dV[i, :]>   (= sum_j P[i,j] dP[i,j], the softmax-backward row term)
+// ADD (OA): out[r] already holds sum_j P[r,j] kappa_j, the term the column normalisation adds to delta
+template <bool ADD>
 __global__ void rowdot_kernel(const float* __restrict__ A, long lda, const float* __restrict__ B, long ldb, size_t R,
                               float* __restrict__ out) {
     const int lane = threadIdx.x & 63;
@@ -188,22 +237,41 @@ __global__ void rowdot_kernel(const float* __restrict__ A, long lda, const float
     float s = A[r * lda + lane] * B[r * ldb + lane] + A[r * lda + 64 + lane] * B[r * ldb + 64 + lane];
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) out[r] = s;
+    if (lane == 0) out[r] = ADD ? s + out[r] : s;
+}
+
+// ---- OA backward, per row j:  Gh[j, :] = gsign G[j, :] / d_j,   kappa_j = -gsign <G[j, :], Xr[j, :]> / d_j   (= dL/dc_j)
+__global__ void oa_prep_kernel(const float* __restrict__ G, long ldg, const float* __restrict__ Xr, long ldx, const float* __restrict__ dstat,
+                               float gsign, size_t R, float* __restrict__ Gh, float* __restrict__ kappa) {
+    const int lane = threadIdx.x & 63;
+    const size_t r = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (r >= R) return;
+    const float d = dstat[r];
+    const float g0 = gsign * G[r * ldg + lane], g1 = gsign * G[r * ldg + 64 + lane];
+    float s = g0 * Xr[r * ldx + lane] + g1 * Xr[r * ldx + 64 + lane];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+    Gh[r * DV + lane] = g0 / d;
+    Gh[r * DV + 64 + lane] = g1 / d;
+    if (lane == 0) kappa[r] = -s / d;
 }
 
 // ---- backward, dQ:  dQ[i, :] = s * sum_j ( P[i,j] (dP[i,j] - delta_i) + P[j,i] (dP[j,i] - delta_j) ) Q[j, :]
 // with dP[i,j] = V[i] . dXs[j] (the energy uses ONE shared Q, so both the "query" and the "key" role of row i collect
 // here).  A wave owns 32 rows i; per 32-row tile j: E (16 MFMAs), dP[i,j] and dP[j,i] (64 + 64, K = 128), then the
 // 32x32 coefficient tile -- lane = i, registers = j, the A-operand layout -- feeds dQ += G Q[j] (16 MFMAs).
-constexpr int DQ_BUF_F = 32 * QS + 2 * 32 * VS + 4 * 32;      // Q, V, dXs tiles + m, 1/l, delta, valid of the tile rows
+constexpr int dq_buf_f(bool oa) { return 32 * QS + 2 * 32 * VS + (oa ? 5 : 4) * 32; }      // Q, V, dXs tiles + m, 1/l, delta, valid (+ kappa) of the tile rows
 
+// OA: dXs is Gh, and dP[i,j] = <V[i], Gh[j]> + kappa_j -- kappa of the tile row on one tile, of the own row on the other.
+template <bool OA>
 __global__ __launch_bounds__(PA_THREADS) void attn_bwd_dq_kernel(const float* __restrict__ Q, long ldq,
                                                                  const float* __restrict__ V, long ldv,
                                                                  const float* __restrict__ dXs, long ldd, int T, int N,
                                                                  float scale, const float* __restrict__ mstat,
                                                                  const float* __restrict__ lstat,
                                                                  const float* __restrict__ delta,
-                                                                 float* __restrict__ dQ, long ldo) {
+                                                                 float* __restrict__ dQ, long ldo, const float* __restrict__ kappa) {
+    constexpr int DQ_BUF_F = dq_buf_f(OA);
     extern __shared__ __attribute__((aligned(16))) float dlds[];       // [2][DQ_BUF_F]
     const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, l31 = lane & 31;
     const int i0 = (blockIdx.y * 4 + wave) * 32;
@@ -224,6 +292,7 @@ __global__ __launch_bounds__(PA_THREADS) void attn_bwd_dq_kernel(const float* __
         bd[4 * v] = b[0]; bd[4 * v + 1] = b[1]; bd[4 * v + 2] = b[2]; bd[4 * v + 3] = b[3];
     }
     const float m_i = mstat[base + my_i], rl_i = 1.f / lstat[base + my_i], dl_i = delta[base + my_i];
+    const float kp_i = OA ? kappa[base + my_i] : 0.f;
     f32x16 dq;
 #pragma unroll
     for (int r = 0; r < 16; ++r) dq[r] = 0.f;
@@ -248,6 +317,7 @@ __global__ __launch_bounds__(PA_THREADS) void attn_bwd_dq_kernel(const float* __
             st[32 + tid] = ok ? 1.f / lstat[base + j0 + tid] : 0.f;
             st[64 + tid] = ok ? delta[base + j0 + tid] : 0.f;
             st[96 + tid] = ok ? 1.f : 0.f;
+            if constexpr (OA) st[128 + tid] = ok ? kappa[base + j0 + tid] : 0.f;
         }
     };
 
@@ -290,6 +360,11 @@ __global__ __launch_bounds__(PA_THREADS) void attn_bwd_dq_kernel(const float* __
             const f32x4 r4 = *reinterpret_cast<const f32x4*>(st + 32 + 8 * g + 4 * h);
             const f32x4 d4 = *reinterpret_cast<const f32x4*>(st + 64 + 8 * g + 4 * h);
             const f32x4 ok4 = *reinterpret_cast<const f32x4*>(st + 96 + 8 * g + 4 * h);
+            if constexpr (OA) {
+                const f32x4 k4 = *reinterpret_cast<const f32x4*>(st + 128 + 8 * g + 4 * h);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { p1[4 * g + u] += k4[u]; p2[4 * g + u] += kp_i; }
+            }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int r = 4 * g + u;
@@ -481,6 +556,30 @@ __global__ __launch_bounds__(256) void head_scatter_kernel(const float* __restri
     }
 }
 
+// ---- G[t, c] = mean_n Y[t*N + n, c]   (pct.py:349): four row walkers (rows n = rw, rw + 4, ...) folded 0,1,2,3 -- a fixed order
+__global__ void segment_mean_kernel(const float* __restrict__ Y, long ldy, int T, int N, int C, float* __restrict__ G) {
+    const int t = blockIdx.x, c = blockIdx.y * 64 + (threadIdx.x & 63), rw = threadIdx.x >> 6;
+    __shared__ float red[4][64];
+    float s = 0.f;
+    if (c < C)
+        for (int n = rw; n < N; n += 4) s += Y[((size_t)t * N + n) * ldy + c];
+    red[rw][threadIdx.x & 63] = s;
+    __syncthreads();
+    if (rw == 0 && c < C) {
+        const int k = threadIdx.x;
+        G[(size_t)t * C + c] = (((red[0][k] + red[1][k]) + red[2][k]) + red[3][k]) / (float)N;
+    }
+}
+
+// its backward: dY[t*N + n, c] = dG[t, c] / N
+__global__ void segment_mean_bwd_kernel(const float* __restrict__ dG, int T, int N, int C, float* __restrict__ dY, long ldd) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (size_t)T * N * C) return;
+    const size_t row = e / C;
+    const int c = (int)(e % C);
+    dY[row * ldd + c] = dG[(row / N) * C + c] / (float)N;
+}
+
 }  // namespace
 
 extern "C" int sga_pct_attention(const float* Q, long ldq, const float* V, long ldv, int T, int N, float* stats,
@@ -496,7 +595,7 @@ extern "C" int sga_pct_attention(const float* Q, long ldq, const float* V, long 
     float* lstat = stats + (size_t)T * N;
     dim3 grid(T, (N + 127) / 128);
     hipLaunchKernelGGL(attn_stats_kernel, grid, dim3(PA_THREADS), 0, s, Q, ldq, T, N, scale, mstat, lstat);
-    hipLaunchKernelGGL(attn_apply_kernel<false>, grid, dim3(PA_THREADS), 0, s, Q, ldq, V, ldv, T, N, scale, mstat, lstat, Xs, ldx);
+    hipLaunchKernelGGL((attn_apply_kernel<false, false>), grid, dim3(PA_THREADS), 0, s, Q, ldq, V, ldv, T, N, scale, mstat, lstat, Xs, ldx, OaArgs{});
     SGA_CHECK_LAUNCH("sga_pct_attention");
     return SGA_OK;
 }
@@ -517,13 +616,86 @@ extern "C" int sga_pct_attention_bwd(const float* Q, long ldq, const float* V, l
     const float* lstat = stats + (size_t)T * N;
     dim3 grid(T, (N + 127) / 128);
     // dV[i] = sum_j P[i,j] dXs[j]: the forward kernel with own-row statistics and dXs as the second tile
-    hipLaunchKernelGGL(attn_apply_kernel<true>, grid, dim3(PA_THREADS), 0, s, Q, ldq, dXs, ldd, T, N, scale, mstat, lstat, dV, ldw);
+    hipLaunchKernelGGL((attn_apply_kernel<true, false>), grid, dim3(PA_THREADS), 0, s, Q, ldq, dXs, ldd, T, N, scale, mstat, lstat, dV, ldw, OaArgs{});
     const size_t R = (size_t)T * N;
-    hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, V, ldv, dV, ldw, R, work);
-    const size_t lds = (size_t)2 * DQ_BUF_F * sizeof(float);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, dim3(PA_THREADS), lds, s, Q, ldq, V, ldv, dXs, ldd, T, N, scale, mstat, lstat, work, dQ, ldo);
+    hipLaunchKernelGGL(rowdot_kernel<false>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, V, ldv, dV, ldw, R, work);
+    const size_t lds = (size_t)2 * dq_buf_f(false) * sizeof(float);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, grid, dim3(PA_THREADS), lds, s, Q, ldq, V, ldv, dXs, ldd, T, N, scale, mstat, lstat, work, dQ, ldo,
+                       static_cast<const float*>(nullptr));
     SGA_CHECK_LAUNCH("sga_pct_attention_bwd");
+    return SGA_OK;
+}
+
+// ---- offset attention (OA.forward, pct.py:261-269): the SA kernels with scale 1 and the column normalisation.
+// stats: m | l | d, T*N floats each.
+extern "C" int sga_pct_offset_attention(const float* Q, long ldq, const float* V, long ldv, const float* X, long ldxi, int T, int N,
+                                        float* stats, float* Xr, long ldx, float* Diff, long ldf, void* stream) {
+    SGA_CHECK_ARG(Q && V && stats && Xr, "sga_pct_offset_attention: null pointer");
+    SGA_CHECK_ARG(T >= 0 && N >= 1 && ldq >= DA && ldv >= DV && ldx >= DV, "sga_pct_offset_attention: bad sizes");
+    SGA_CHECK_ARG(!Diff || (X && ldxi >= DV && ldf >= DV), "sga_pct_offset_attention: Diff needs X, and row strides of at least 128");
+    SGA_CHECK_ARG(ldq % 4 == 0 && ldv % 4 == 0 && reinterpret_cast<uintptr_t>(Q) % 16 == 0 && reinterpret_cast<uintptr_t>(V) % 16 == 0,
+                  "sga_pct_offset_attention: Q / V rows must be 16-byte aligned");
+    if (T == 0) return SGA_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t R = (size_t)T * N;
+    float* mstat = stats;
+    float* lstat = stats + R;
+    dim3 grid(T, (N + 127) / 128);
+    hipLaunchKernelGGL(attn_stats_kernel, grid, dim3(PA_THREADS), 0, s, Q, ldq, T, N, 1.0f, mstat, lstat);
+    hipLaunchKernelGGL((attn_apply_kernel<false, true>), grid, dim3(PA_THREADS), 0, s, Q, ldq, V, ldv, T, N, 1.0f, mstat, lstat, Xr, ldx,
+                       OaArgs{nullptr, stats + 2 * R, X, ldxi, Diff, ldf});
+    SGA_CHECK_LAUNCH("sga_pct_offset_attention");
+    return SGA_OK;
+}
+
+// backward of sga_pct_offset_attention.  G = gsign * (the caller's gradient): gsign = -1 when the caller holds dL/dDiff.
+// work: T*N*130 floats, 16-byte aligned: Gh [T*N,128] | kappa [T*N] | delta [T*N].
+extern "C" int sga_pct_offset_attention_bwd(const float* Q, long ldq, const float* V, long ldv, const float* Xr, long ldx, const float* G,
+                                            long ldg, float gsign, int T, int N, const float* stats, float* work, float* dQ, long ldo,
+                                            float* dV, long ldw, void* stream) {
+    SGA_CHECK_ARG(Q && V && Xr && G && stats && work && dQ && dV, "sga_pct_offset_attention_bwd: null pointer");
+    SGA_CHECK_ARG(T >= 0 && N >= 1 && ldq >= DA && ldv >= DV && ldx >= DV && ldg >= DV && ldo >= DA && ldw >= DV,
+                  "sga_pct_offset_attention_bwd: bad sizes");
+    SGA_CHECK_ARG(ldq % 4 == 0 && ldv % 4 == 0 && reinterpret_cast<uintptr_t>(Q) % 16 == 0 && reinterpret_cast<uintptr_t>(V) % 16 == 0 &&
+                      reinterpret_cast<uintptr_t>(work) % 16 == 0,
+                  "sga_pct_offset_attention_bwd: Q / V rows and work must be 16-byte aligned");
+    if (T == 0) return SGA_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t R = (size_t)T * N;
+    const float* mstat = stats;
+    const float* lstat = stats + R;
+    float* Gh = work;
+    float* kappa = work + R * DV;
+    float* delta = kappa + R;
+    dim3 grid(T, (N + 127) / 128);
+    hipLaunchKernelGGL(oa_prep_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, G, ldg, Xr, ldx, stats + 2 * R, gsign, R, Gh, kappa);
+    // dV[i] = sum_j P[i,j] Gh[j], and delta_i's second term sum_j P[i,j] kappa_j into `delta`
+    hipLaunchKernelGGL((attn_apply_kernel<true, true>), grid, dim3(PA_THREADS), 0, s, Q, ldq, Gh, (long)DV, T, N, 1.0f, mstat, lstat, dV, ldw,
+                       OaArgs{kappa, delta, nullptr, 0, nullptr, 0});
+    hipLaunchKernelGGL(rowdot_kernel<true>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, V, ldv, dV, ldw, R, delta);
+    const size_t lds = (size_t)2 * dq_buf_f(true) * sizeof(float);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, grid, dim3(PA_THREADS), lds, s, Q, ldq, V, ldv, Gh, (long)DV, T, N, 1.0f, mstat, lstat, delta, dQ,
+                       ldo, kappa);
+    SGA_CHECK_LAUNCH("sga_pct_offset_attention_bwd");
+    return SGA_OK;
+}
+
+extern "C" int sga_segment_mean(const float* Y, long ldy, int T, int N, int C, float* G, void* stream) {
+    SGA_CHECK_ARG(Y && G && T >= 0 && N >= 1 && C >= 1 && ldy >= C, "sga_segment_mean: bad argument");
+    if (T == 0) return SGA_OK;
+    hipLaunchKernelGGL(segment_mean_kernel, dim3(T, (C + 63) / 64), dim3(256), 0, static_cast<hipStream_t>(stream), Y, ldy, T, N, C, G);
+    SGA_CHECK_LAUNCH("sga_segment_mean");
+    return SGA_OK;
+}
+
+extern "C" int sga_segment_mean_bwd(const float* dG, int T, int N, int C, float* dY, long ldd, void* stream) {
+    SGA_CHECK_ARG(dG && dY && T >= 0 && N >= 1 && C >= 1 && ldd >= C, "sga_segment_mean_bwd: bad argument");
+    if (T == 0) return SGA_OK;
+    const size_t n = (size_t)T * N * C;
+    hipLaunchKernelGGL(segment_mean_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), dG, T, N, C, dY, ldd);
+    SGA_CHECK_LAUNCH("sga_segment_mean_bwd");
     return SGA_OK;
 }
 

@@ -145,6 +145,100 @@ def pct_attention(q, v, n_obj, n_pts):
     return PCTAttentionFn.apply(q, v, n_obj, n_pts)
 
 
+def _offset_attention_fwd(q, v, x, n_obj, n_pts):
+    """sga_pct_offset_attention: (stats, xr, x - xr or None)."""
+    rows, dev = n_obj * n_pts, q.device
+    stats = torch.empty((3 * rows,), device=dev, dtype=torch.float32)
+    xr = torch.empty((rows, 128), device=dev, dtype=torch.float32)
+    diff = torch.empty((rows, 128), device=dev, dtype=torch.float32) if x is not None else None
+    _chk(_lib.lib().sga_pct_offset_attention(_p(q), q.stride(0), _p(v), v.stride(0), _p(x), x.stride(0) if x is not None else 0, n_obj, n_pts,
+                                             _p(stats), _p(xr), xr.stride(0), _p(diff), diff.stride(0) if diff is not None else 0, _stream()),
+         'sga_pct_offset_attention')
+    return stats, xr, diff
+
+
+def _offset_attention_bwd(q, v, xr, g, gsign, n_obj, n_pts, stats, dq, dv):
+    g = g if g.stride(1) == 1 else g.contiguous()
+    work = torch.empty((n_obj * n_pts * 130,), device=q.device, dtype=torch.float32)
+    _chk(_lib.lib().sga_pct_offset_attention_bwd(_p(q), q.stride(0), _p(v), v.stride(0), _p(xr), xr.stride(0), _p(g), g.stride(0), gsign, n_obj,
+                                                 n_pts, _p(stats), _p(work), _p(dq), dq.stride(0), _p(dv), dv.stride(0), _stream()),
+         'sga_pct_offset_attention_bwd')
+
+
+class PCTOffsetAttentionFn(torch.autograd.Function):
+    """Offset attention of OA.forward (pct.py:261-269, shared q/k weight) per object: with P = softmax_rows(q q^T) (no 1/sqrt(32)) and
+    d_j = 1e-9 + sum_i P[i,j],  xr[j] = sum_i P[i,j] v[i] / d_j.  q [T*N, 32], v [T*N, 128] point-major (column slices allowed).  Without x
+    the result is xr; with x [T*N, 128] it is x - xr, the operand of trans_conv (pct.py:270), written by the same kernel."""
+
+    @staticmethod
+    def forward(ctx, q, v, x, n_obj, n_pts):
+        stats, xr, diff = _offset_attention_fwd(q, v, x, n_obj, n_pts)
+        ctx.save_for_backward(q, v, xr, stats)
+        ctx.dims = (n_obj, n_pts, x is not None)
+        return xr if x is None else diff
+
+    @staticmethod
+    def backward(ctx, g):
+        q, v, xr, stats = ctx.saved_tensors
+        n_obj, n_pts, with_x = ctx.dims
+        dq = torch.empty((n_obj * n_pts, 32), device=q.device, dtype=torch.float32)
+        dv = torch.empty((n_obj * n_pts, 128), device=q.device, dtype=torch.float32)
+        _offset_attention_bwd(q, v, xr, g, -1.0 if with_x else 1.0, n_obj, n_pts, stats, dq, dv)
+        return dq, dv, (g if with_x else None), None, None
+
+
+class PCTOffsetAttentionQVFn(torch.autograd.Function):
+    """PCTOffsetAttentionFn on ONE [T*N, 160] tensor holding q (columns 0..31) and v (32..159), as PCTAttentionQVFn."""
+
+    @staticmethod
+    def forward(ctx, qv, x, n_obj, n_pts):
+        qv = qv if qv.is_contiguous() else qv.contiguous()
+        stats, xr, diff = _offset_attention_fwd(qv[:, :32], qv[:, 32:], x, n_obj, n_pts)
+        ctx.save_for_backward(qv, xr, stats)
+        ctx.dims = (n_obj, n_pts, x is not None)
+        return xr if x is None else diff
+
+    @staticmethod
+    def backward(ctx, g):
+        qv, xr, stats = ctx.saved_tensors
+        n_obj, n_pts, with_x = ctx.dims
+        dqv = torch.empty_like(qv)
+        _offset_attention_bwd(qv[:, :32], qv[:, 32:], xr, g, -1.0 if with_x else 1.0, n_obj, n_pts, stats, dqv[:, :32], dqv[:, 32:])
+        return dqv, (g if with_x else None), None, None
+
+
+def pct_offset_attention(q, v, n_obj, n_pts, x=None):
+    return PCTOffsetAttentionFn.apply(q, v, x, n_obj, n_pts)
+
+
+def pct_offset_attention_qv(qv, n_obj, n_pts, x=None):
+    return PCTOffsetAttentionQVFn.apply(qv, x, n_obj, n_pts)
+
+
+class SegmentMeanFn(torch.autograd.Function):
+    """g[t, c] = mean over the n_pts rows of object t (pct.py:349), summed in a fixed order (csrc/pct.hip segment_mean_kernel)."""
+
+    @staticmethod
+    def forward(ctx, y, n_obj, n_pts):
+        C = y.shape[1]
+        g = torch.empty((n_obj, C), device=y.device, dtype=torch.float32)
+        _chk(_lib.lib().sga_segment_mean(_p(y), y.stride(0), n_obj, n_pts, C, _p(g), _stream()), 'sga_segment_mean')
+        ctx.dims = (n_obj, n_pts, C)
+        return g
+
+    @staticmethod
+    def backward(ctx, dg):
+        n_obj, n_pts, C = ctx.dims
+        dg = dg.contiguous()
+        dy = torch.empty((n_obj * n_pts, C), device=dg.device, dtype=torch.float32)
+        _chk(_lib.lib().sga_segment_mean_bwd(_p(dg), n_obj, n_pts, C, _p(dy), dy.stride(0), _stream()), 'sga_segment_mean_bwd')
+        return dy, None, None
+
+
+def segment_mean(y, n_obj, n_pts):
+    return SegmentMeanFn.apply(y, n_obj, n_pts)
+
+
 class SegmentMaxFn(torch.autograd.Function):
     """g[t, c] = max over the n_pts rows of object t (pct.py:308); backward routes to the first arg-max row."""
 
