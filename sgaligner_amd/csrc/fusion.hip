@@ -194,7 +194,10 @@ extern "C" int sga_fusion_bwd(const float* const* embs, int M, const float* weig
     hipStream_t s = static_cast<hipStream_t>(stream);
     FusionPtrs p{};
     FusionOutPtrs q{};
-    for (int m = 0; m < M; ++m) { p.p[m] = embs[m]; q.p[m] = gembs[m]; }
+    for (int m = 0; m < M; ++m) {
+        SGA_CHECK_ARG(T == 0 || (embs[m] && gembs[m]), "sga_fusion_bwd: null table %d", m);
+        p.p[m] = embs[m]; q.p[m] = gembs[m];
+    }
     double* acc = static_cast<double*>(workspace);
     if (hipMemsetAsync(acc, 0, sizeof(double) * M, s) != hipSuccess) { sga_set_error("sga_fusion_bwd: memset failed"); return SGA_ERR_HIP; }
     if (T > 0) hipLaunchKernelGGL(fusion_bwd_kernel, dim3(grid_for_rows(T, 4)), dim3(256), 0, s, p, weight, gjoint, q, acc, T, D, M);

@@ -337,7 +337,10 @@ __global__ void elu_fwd_kernel(const float* __restrict__ x, float* __restrict__ 
 __global__ void elu_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gy, float* __restrict__ gx, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const float v = x[i];
-        gx[i] = v > 0.f ? gy[i] : gy[i] * expf(v);
+        // exp in fp64, rounded once.  Not expf: under -ffp-contract=fast the compiler's float expansion of it, 2^((p - rint(p)) + p_lo) with
+        // p = fl(v log2e), has p - rint(p) fused into fma(v, log2e, -rint(p)) and then adds the product's rounding error p_lo a second time --
+        // up to 40 ulp for v in [-90, -2.5] (tests/test_elementwise_gpu.py holds this kernel to 4 ulp).
+        gx[i] = v > 0.f ? gy[i] : gy[i] * (float)exp((double)v);
     }
 }
 

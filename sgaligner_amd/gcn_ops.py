@@ -108,6 +108,7 @@ def multi_gcn(gb, x, layer0, layer1):
 
 # ------------------------------------------------------------------------------------------ GCN, any stack, both routes
 def _relu_bwd(y, gy):
+    y, gy = y.contiguous(), gy.contiguous()               # the kernel walks memory: a strided view would be read as if it were dense
     gx = torch.empty_like(y)
     _lib.check(_lib.lib().sga_relu_bwd(_p(y), _p(gy), _p(gx), y.numel(), _stream()), 'sga_relu_bwd')
     return gx

@@ -75,15 +75,12 @@ def test_fusion_golden(m):
 
 
 def test_fusion_zero_row_and_large():
+    import fusion_gate as FG
     from oracle import sga_oracle as O
     from sgaligner_amd import ops
-    torch.manual_seed(0)
-    embs = [torch.randn(5000, 100) for _ in range(3)]
-    embs[1][17] = 0.0                                    # F.normalize eps branch
-    w = torch.tensor([[0.3], [1.2], [-0.4]])
+    w, embs, cot = FG.large_inputs()                     # 3 tables of 5000 x 100, row 17 of table 1 all zero (F.normalize eps branch)
     er = [e.clone().requires_grad_(True) for e in embs]
     wr = w.clone().requires_grad_(True)
-    cot = torch.randn(5000, 300)
     (O.fusion(er, wr) * cot).sum().backward()
     ed = [e.cuda().requires_grad_(True) for e in embs]
     wd = w.cuda().requires_grad_(True)
@@ -96,3 +93,6 @@ def test_fusion_zero_row_and_large():
         # the all-zero row takes F.normalize's eps branch: gradient = w * g / 1e-12 (huge) -> relative check
         err = (a.grad.cpu() - b.grad).abs() / b.grad.abs().clamp_min(1.0)
         assert err.max() < 1e-4
+    # ... and the fp32-faithful gate of tests/fusion_gate.py on the same outputs (the all-zero row left out)
+    got = (j.detach().cpu(), torch.cat([e.grad.cpu() for e in ed], dim=1), wd.grad.reshape(-1).cpu())
+    FG.assert_gate(FG.measure(got, w, embs, cot), 'test_fusion_zero_row_and_large')
