@@ -160,8 +160,9 @@ int sga_fusion_var_bwd(const float* const* embs, int M, const int32_t* widths, c
 /* ---- GAT structure encoder --------------------------------------------------------------------------
  * replaces torch_geometric.nn.GATConv (2.2.0, un-vendored) as used by src/aligner/networks/gat.py:36-37,44,
  * for ALL graphs of a batch in one launch (sg_aligner.py:86-110 issues 2B sequential calls):
- * H [T,256] = x W^T (2 heads x 128), att_src/att_dst/bias [256]; edges [sumE,2] int64 graph-local (col 0 source,
- * col 1 target); node_off/edge_off [G+1] int32 prefix sums; nmax = max nodes per graph (<= 256; up to 128 the features stay in LDS).
+ * any GATConv(in, channels, heads) the reference's MultiGAT can stack (gat.py:35-37): heads >= 1 heads of 1 <= channels <= 256 channels each.
+ * H [T, heads*channels] = x W^T head-major (as out / dO / dH), att_src / att_dst / bias / d_att_src / d_att_dst [heads*channels]; edges
+ * [sumE,2] int64 graph-local (col 0 source, col 1 target); node_off/edge_off [G+1] int32 prefix sums; nmax = max nodes per graph (<= 256).
  * out[i] = sum_j softmax_j(leaky_relu(a_s[j]+a_d[i], 0.2)) H[j] + bias, self loops normalised as PyG does.
  * Limits the CALLER must respect (the Python wrapper checks the first two on the host once per batch): node ids are
  * graph-local in [0, nodes of that graph) -- an endpoint outside that range is DROPPED by the kernels, where PyG would raise;
@@ -175,19 +176,11 @@ int sga_fusion_var_bwd(const float* const* embs, int M, const int32_t* widths, c
  * multiplicities are all 1 and the kernels do not read its edges at all (16 B per edge: 2.13 GB at configs[2], eight times per step).
  * sga_gat_complete_flags fills the array from the edge lists themselves (order-independent: an N x N bitmap per graph), once per batch. */
 int sga_gat_complete_flags(const int64_t* edges, const int32_t* node_off, const int32_t* edge_off, int G, uint8_t* flags, void* stream);
-int sga_gat_attn_fwd(const float* H, const float* att_src, const float* att_dst, const float* bias,
-                     const int64_t* edges, const int32_t* node_off, const int32_t* edge_off, int G, int nmax,
-                     float* out, int32_t* status, const uint8_t* complete, void* stream);
-int sga_gat_attn_bwd(const float* H, const float* dO, const float* att_src, const float* att_dst, const int64_t* edges,
-                     const int32_t* node_off, const int32_t* edge_off, int G, int nmax, float* dH, float* d_att_src,
-                     float* d_att_dst, const uint8_t* complete, void* stream);
-/* The same two for any GATConv(in, channels, heads) the reference's MultiGAT can stack (gat.py:35-37): heads >= 1 heads of 1 <= channels <= 256
- * channels each.  H / dO / out / dH [T, heads*channels] head-major, att_src / att_dst / bias / d_att_src / d_att_dst [heads*channels];
- * everything else -- edges, offsets, nmax <= 256, status, complete, the arithmetic and its order, the limits above -- as for sga_gat_attn_fwd /
- * sga_gat_attn_bwd, which remain the route of the 2 x 128 layers.  One workgroup per (graph, head); lanes span the channels in
- * ceil(channels / 64) slots, the last one masked.  A head's features [N, channels] (and, backward, their gradient's) are kept in LDS, row stride
- * channels | 1, while they fit the 160 KiB of a CU beside the multiplicity matrix: sga_gat_lds_nodes(channels, bwd) is the largest nmax for which
- * they do (bwd != 0: the backward kernel's two copies); above it the rows are read from global memory.
+/* One workgroup per (graph, head); lanes span the channels in ceil(channels / 64) slots, the last one masked.  A head's features
+ * [N, channels] (and, backward, their gradient's) are kept in LDS, row stride channels | 1, while they fit the 160 KiB of a CU beside the
+ * multiplicity matrix: sga_gat_lds_nodes(channels, bwd) is the largest nmax for which they do (bwd != 0: the backward kernel's two copies);
+ * above it the rows are read from global memory.  heads == 2 with channels == 128, the reference model's layers, launches kernels of its own
+ * with those two numbers literal (the same algorithm; features in LDS up to 128 nodes, from global memory above).
  * heads < 1, channels < 1 or channels > 256 is SGA_ERR_ARG (sga_gat_lds_nodes: -1), before any device call. */
 int sga_gat_attn_fwd_hc(const float* H, int heads, int channels, const float* att_src, const float* att_dst, const float* bias,
                         const int64_t* edges, const int32_t* node_off, const int32_t* edge_off, int G, int nmax,
@@ -195,6 +188,8 @@ int sga_gat_attn_fwd_hc(const float* H, int heads, int channels, const float* at
 int sga_gat_attn_bwd_hc(const float* H, const float* dO, int heads, int channels, const float* att_src, const float* att_dst,
                         const int64_t* edges, const int32_t* node_off, const int32_t* edge_off, int G, int nmax, float* dH,
                         float* d_att_src, float* d_att_dst, const uint8_t* complete, void* stream);
+/* The general kernels' residency boundary.  It has no head count: at channels == 128 it answers for every heads != 2 (215 forward, 135
+ * backward); the launch at heads == 2, channels == 128 keeps features in LDS up to 128 nodes in both directions, whatever this returns. */
 int sga_gat_lds_nodes(int channels, int bwd);
 /* The SPARSE route: the same attention over a compressed edge list instead of a dense matrix in LDS -- graphs of ANY size, multiplicities of
  * 32 bits (no saturation, no status word), no atomics: every sum's order is fixed by the structure alone, so the outputs are bitwise

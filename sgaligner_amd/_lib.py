@@ -39,8 +39,6 @@ SIGNATURES = {
     'sga_pointnet_fwd_lg_ws_bytes': (c_size_t, []),
     'sga_pointnet_plan': (I, [I, I, I, I, I, c_size_t, I, P]),
     'sga_gat_complete_flags': (I, [P, P, P, I, P, P]),
-    'sga_gat_attn_fwd': (I, [P, P, P, P, P, P, P, I, I, P, P, P, P]),
-    'sga_gat_attn_bwd': (I, [P, P, P, P, P, P, P, I, I, P, P, P, P, P]),
     'sga_gat_attn_fwd_hc': (I, [P, I, I, P, P, P, P, P, P, I, I, P, P, P, P]),
     'sga_gat_attn_bwd_hc': (I, [P, P, I, I, P, P, P, P, P, I, I, P, P, P, P, P]),
     'sga_gat_lds_nodes': (I, [I, I]),

@@ -33,8 +33,8 @@ class GATConv(nn.Module):
 
 class MultiGAT(nn.Module):
     """gat.py:27-48: GATConv layers of any depth, head count and width (at most MAX_CHANNELS channels per head), dropout on every layer's
-    input, ELU between layers.  The reference's own model -- n_units=[F,128,128], n_heads=[2,2], no dropout -- runs on the kernels
-    specialised for it; every other stack on the general ones (ops.multi_gat_layers).
+    input, ELU between layers.  Every stack runs on ops.multi_gat_layers; at the reference's own shape, 2 heads of 128 channels, the C
+    entry points launch the attention kernels written for it.
     route: 'dense' (default; a graph holds at most 256 nodes), 'sparse' (the CSR attention kernels: graphs of any size, no atomics -- every
     model, the 2 x 128 one included) or 'auto' (per batch: sparse exactly when its largest graph has more than 256 nodes)."""
     MAX_CHANNELS = 256
@@ -60,17 +60,12 @@ class MultiGAT(nn.Module):
             in_c = n_units[i] * n_heads[i - 1] if i else n_units[i]
             layers.append(GATConv(in_c, n_units[i + 1], n_heads[i]))
         self.layer_stack = nn.ModuleList(layers)
-        self._canonical = self.num_layers == 2 and list(n_units[1:]) == [128, 128] and list(n_heads) == [2, 2]
 
     def forward_batched(self, x, graph_batch, masks=None):
         """All graphs of a batch in one launch per layer (x [T,F], graph_batch: ops.GraphBatch).  masks: one [T, in_width] tensor per layer,
         already scaled by 1 / (1 - p), used INSTEAD of drawing (parity with a recorded run); without them F.dropout draws in train mode."""
-        drop = self.training and self.dropout > 0.0
-        route = ops.resolve_route(self.route, graph_batch)
-        if route == 'dense' and self._canonical and masks is None and not drop:
-            return ops.multi_gat(graph_batch, x, self.layer_stack[0].params(), self.layer_stack[1].params())
         return ops.multi_gat_layers(graph_batch, x, [l.params() for l in self.layer_stack], p=self.dropout, training=self.training, masks=masks,
-                                    route=route)
+                                    route=ops.resolve_route(self.route, graph_batch))
 
     def forward(self, x, edges):
         """Reference signature (gat.py:40): one graph, x [N,F], edges [2,E] (row 0 source, row 1 target)."""
@@ -96,8 +91,8 @@ class GCNConv(nn.Module):
 
 class MultiGCN(nn.Module):
     """gat.py:6-25: GCNConv layers of any depth (len(n_units) - 1 of them) and width, ReLU between layers and none after the last.  Dropout is
-    out of scope: the reference's default is 0 (eva.py:10), anything else raises NotImplementedError.  The two-layer model on the dense route
-    runs on ops.multi_gcn; every other stack on ops.multi_gcn_layers.
+    out of scope: the reference's default is 0 (eva.py:10), anything else raises NotImplementedError.  Every stack runs on
+    ops.multi_gcn_layers.
     route: 'dense' (default; a graph holds at most 256 nodes, a pair at most 255 copies), 'sparse' (the CSR aggregation kernels: graphs of any
     size -- the same bits as 'dense' wherever that route can run) or 'auto' (per batch: sparse exactly when its largest graph has more than
     256 nodes)."""
@@ -118,10 +113,7 @@ class MultiGCN(nn.Module):
 
     def forward_batched(self, x, graph_batch):
         """All graphs of a batch in one launch per layer and direction (x [T,F], graph_batch: ops.GraphBatch)."""
-        route = ops.resolve_route(self.route, graph_batch)
-        if route == 'dense' and self.num_layers == 2:
-            return ops.multi_gcn(graph_batch, x, self.layer_stack[0].params(), self.layer_stack[1].params())
-        return ops.multi_gcn_layers(graph_batch, x, [l.params() for l in self.layer_stack], route=route)
+        return ops.multi_gcn_layers(graph_batch, x, [l.params() for l in self.layer_stack], route=ops.resolve_route(self.route, graph_batch))
 
     def forward(self, x, edges):
         """Reference signature (gat.py:17): one graph, x [N,F], edges [2,E] (row 0 source, row 1 target)."""

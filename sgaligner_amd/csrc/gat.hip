@@ -15,6 +15,10 @@
 // alpha broadcast by v_readlane for the aggregate.  All 2B graphs of a batch go in ONE launch
 // (the reference issues 2B sequential GATConv calls).  Graph traffic is byte-bound: 16 B/edge (int64
 // pairs, read once per head) + 512 B/node/head in, 512 B/node/head out.
+//
+// Two kernel families, one pair of entry points (sga_gat_attn_fwd_hc / _bwd_hc).  First in the file, and described above, the kernels of
+// 2 heads x 128 channels -- the reference model's layers -- with those two numbers literal; further down the general ones (any head count,
+// 1 .. 256 channels, both run-time values).  The entry points launch the first family at exactly 2 x 128 and the second everywhere else.
 #include "sga_common.h"
 
 namespace {
@@ -28,6 +32,8 @@ constexpr int GAT_THREADS = 256;
 constexpr int GAT_TB = 8;             // targets (fwd) / sources (bwd) a wave processes together: LDS reads per FMA / 8
 constexpr float GAT_SLOPE = 0.2f;
 
+// The kernels of 2 heads x 128 channels, the reference model's layers; sga_gat_attn_fwd_hc / _bwd_hc launch them at that shape (they measured
+// faster there than the general kernels below, also with the width fixed at compile time: profiles/gat_unify_bench.json).
 // Two instantiations of every kernel: <NJ = 2, LDSF = true> for graphs of up to 128 nodes (every real 3RScan sub-scan:
 // the head's features [N,128] live in LDS) and <NJ = 4, LDSF = false> for up to 256 nodes, where only the multiplicity
 // matrix and the per-node scalars stay in LDS and feature rows are read from global memory (L2-resident: 128 KiB per
@@ -353,62 +359,26 @@ int check_common(int G, int nmax, const char* who) {
     return SGA_OK;
 }
 
+// the launches of the 2 x 128 kernels: features LDS-resident exactly up to GAT_MAXN nodes
+void launch_fwd_2x128(int G, hipStream_t s, const float* H, const float* att_s, const float* att_d, const float* bias, const long long* edges,
+                      const int* node_off, const int* edge_off, float* out, int nmax, int* status, const unsigned char* complete) {
+    const bool small = nmax <= GAT_MAXN;
+    const size_t lds = gat_lds_bytes(nmax, false, small ? 2 : 4, small);
+    auto k = small ? gat_attn_fwd_kernel<2, true> : gat_attn_fwd_kernel<4, false>;      // 129..256 nodes: features from global memory
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k, dim3(G, GAT_H), dim3(GAT_THREADS), lds, s, H, att_s, att_d, bias, edges, node_off, edge_off, out, nmax, status, complete);
+}
+
+void launch_bwd_2x128(int G, hipStream_t s, const float* H, const float* dO, const float* att_s, const float* att_d, const long long* edges,
+                      const int* node_off, const int* edge_off, float* dH, float* d_att_s, float* d_att_d, int nmax, const unsigned char* complete) {
+    const bool small = nmax <= GAT_MAXN;
+    const size_t lds = gat_lds_bytes(nmax, true, small ? 2 : 4, small);
+    auto k = small ? gat_attn_bwd_kernel<2, true> : gat_attn_bwd_kernel<4, false>;
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k, dim3(G, GAT_H), dim3(GAT_THREADS), lds, s, H, dO, att_s, att_d, edges, node_off, edge_off, dH, d_att_s, d_att_d, nmax, complete);
+}
+
 }  // namespace
-
-extern "C" int sga_gat_attn_fwd(const float* H, const float* att_src, const float* att_dst, const float* bias,
-                                const int64_t* edges, const int32_t* node_off, const int32_t* edge_off, int G,
-                                int nmax, float* out, int32_t* status, const uint8_t* complete, void* stream) {
-    int rc = check_common(G, nmax, "sga_gat_attn_fwd");
-    if (rc) return rc;
-    if (G == 0 || nmax == 0) return SGA_OK;
-    SGA_CHECK_ARG(H && att_src && att_dst && bias && node_off && edge_off && out, "sga_gat_attn_fwd: null pointer");
-    if (nmax <= GAT_MAXN) {
-        const size_t lds = gat_lds_bytes(nmax, false, 2, true);
-        auto k = gat_attn_fwd_kernel<2, true>;
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k, dim3(G, GAT_H), dim3(GAT_THREADS), lds, static_cast<hipStream_t>(stream), H, att_src,
-                           att_dst, bias, reinterpret_cast<const long long*>(edges), node_off, edge_off, out, nmax, status, complete);
-    } else {                                              // 129..256 nodes: features from global memory
-        const size_t lds = gat_lds_bytes(nmax, false, 4, false);
-        auto k = gat_attn_fwd_kernel<4, false>;
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k, dim3(G, GAT_H), dim3(GAT_THREADS), lds, static_cast<hipStream_t>(stream), H, att_src,
-                           att_dst, bias, reinterpret_cast<const long long*>(edges), node_off, edge_off, out, nmax, status, complete);
-    }
-    SGA_CHECK_LAUNCH("sga_gat_attn_fwd");
-    return SGA_OK;
-}
-
-extern "C" int sga_gat_attn_bwd(const float* H, const float* dO, const float* att_src, const float* att_dst,
-                                const int64_t* edges, const int32_t* node_off, const int32_t* edge_off, int G,
-                                int nmax, float* dH, float* d_att_src, float* d_att_dst, const uint8_t* complete, void* stream) {
-    int rc = check_common(G, nmax, "sga_gat_attn_bwd");
-    if (rc) return rc;
-    SGA_CHECK_ARG(((G == 0 || nmax == 0) || (H && dO && node_off && edge_off && dH)) && att_src && att_dst && d_att_src && d_att_dst, "sga_gat_attn_bwd: null pointer");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (d_att_dst == d_att_src + GAT_H * GAT_C) {                     // one flat buffer (ops.py): one launch
-        hipMemsetAsync(d_att_src, 0, 2 * GAT_H * GAT_C * sizeof(float), s);
-    } else {
-        hipMemsetAsync(d_att_src, 0, GAT_H * GAT_C * sizeof(float), s);
-        hipMemsetAsync(d_att_dst, 0, GAT_H * GAT_C * sizeof(float), s);
-    }
-    if (G == 0 || nmax == 0) return SGA_OK;
-    if (nmax <= GAT_MAXN) {
-        const size_t lds = gat_lds_bytes(nmax, true, 2, true);
-        auto k = gat_attn_bwd_kernel<2, true>;
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k, dim3(G, GAT_H), dim3(GAT_THREADS), lds, s, H, dO, att_src, att_dst,
-                           reinterpret_cast<const long long*>(edges), node_off, edge_off, dH, d_att_src, d_att_dst, nmax, complete);
-    } else {
-        const size_t lds = gat_lds_bytes(nmax, true, 4, false);
-        auto k = gat_attn_bwd_kernel<4, false>;
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k, dim3(G, GAT_H), dim3(GAT_THREADS), lds, s, H, dO, att_src, att_dst,
-                           reinterpret_cast<const long long*>(edges), node_off, edge_off, dH, d_att_src, d_att_dst, nmax, complete);
-    }
-    SGA_CHECK_LAUNCH("sga_gat_attn_bwd");
-    return SGA_OK;
-}
 
 // flags[g] = 1 iff graph g lists every ordered pair i != j exactly once and nothing else (E = N (N - 1), every edge in range, no self
 // loop, no duplicate -- an N x N bitmap in LDS catches duplicates whatever the ORDER of the list: preprocess.py writes the annotated
@@ -460,7 +430,7 @@ extern "C" int sga_elu_bwd(const float* x, const float* gy, float* gx, size_t n,
 }
 
 // ---- the general form: GATConv(in, C, heads) for any heads >= 1 and 1 <= C <= 256 (every stack reference gat.py:34-37 can build) ----
-// Same algorithm, arithmetic and order as the kernels above, which remain the route of the 2 x 128 layers.  heads and C are run-time values
+// Same algorithm, arithmetic and order as the kernels above, which the entry points launch at 2 x 128.  heads and C are run-time values
 // (grid y, row stride heads * C); lanes span the channels in CJ = ceil(C / 64) slots (channel c = lane + 64 k), a template parameter.  Only
 // the LAST slot can be ragged: its lanes past C read channel C - 1 again (a valid address, no branch in the inner loops), enter every dot
 // product with weight 0 and are never written.  The LDS row stride is C | 1: odd for every C, so lanes walking down a column (backward
@@ -807,6 +777,7 @@ void launch_bwd_hc(size_t lds, int G, int heads, hipStream_t s, const float* H, 
 
 }  // namespace
 
+// the GENERAL kernels' boundary: the 2 x 128 launch (launch_fwd_2x128 / launch_bwd_2x128) has its own, GAT_MAXN nodes in both directions
 extern "C" int sga_gat_lds_nodes(int channels, int bwd) {
     if (channels < 1 || channels > GAT_CMAX) {
         sga_set_error("sga_gat_lds_nodes: channels %d outside 1 .. %d per head", channels, GAT_CMAX);
@@ -826,11 +797,16 @@ extern "C" int sga_gat_attn_fwd_hc(const float* H, int heads, int channels, cons
     if (rc) return rc;
     if (G == 0 || nmax == 0) return SGA_OK;
     SGA_CHECK_ARG(H && att_src && att_dst && bias && node_off && edge_off && out, "sga_gat_attn_fwd_hc: null pointer");
-    const int nj = gat_nj(nmax), cj = (channels + 63) / 64;
-    const bool ldsf = gat_fits_lds(nmax, false, channels);
-    const size_t lds = gat_lds_bytes_hc(nmax, false, channels, ldsf);
-    GAT_HC_DISPATCH(launch_fwd_hc, lds, G, heads, static_cast<hipStream_t>(stream), H, att_src, att_dst, bias,
-                    reinterpret_cast<const long long*>(edges), node_off, edge_off, out, nmax, channels, status, complete);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long long* e = reinterpret_cast<const long long*>(edges);
+    if (heads == GAT_H && channels == GAT_C) {
+        launch_fwd_2x128(G, s, H, att_src, att_dst, bias, e, node_off, edge_off, out, nmax, status, complete);
+    } else {
+        const int nj = gat_nj(nmax), cj = (channels + 63) / 64;
+        const bool ldsf = gat_fits_lds(nmax, false, channels);
+        const size_t lds = gat_lds_bytes_hc(nmax, false, channels, ldsf);
+        GAT_HC_DISPATCH(launch_fwd_hc, lds, G, heads, s, H, att_src, att_dst, bias, e, node_off, edge_off, out, nmax, channels, status, complete);
+    }
     SGA_CHECK_LAUNCH("sga_gat_attn_fwd_hc");
     return SGA_OK;
 }
@@ -852,11 +828,15 @@ extern "C" int sga_gat_attn_bwd_hc(const float* H, const float* dO, int heads, i
         hipMemsetAsync(d_att_dst, 0, hc * sizeof(float), s);
     }
     if (G == 0 || nmax == 0) return SGA_OK;
-    const int nj = gat_nj(nmax), cj = (channels + 63) / 64;
-    const bool ldsf = gat_fits_lds(nmax, true, channels);
-    const size_t lds = gat_lds_bytes_hc(nmax, true, channels, ldsf);
-    GAT_HC_DISPATCH(launch_bwd_hc, lds, G, heads, s, H, dO, att_src, att_dst, reinterpret_cast<const long long*>(edges), node_off, edge_off,
-                    dH, d_att_src, d_att_dst, nmax, channels, complete);
+    const long long* e = reinterpret_cast<const long long*>(edges);
+    if (heads == GAT_H && channels == GAT_C) {
+        launch_bwd_2x128(G, s, H, dO, att_src, att_dst, e, node_off, edge_off, dH, d_att_src, d_att_dst, nmax, complete);
+    } else {
+        const int nj = gat_nj(nmax), cj = (channels + 63) / 64;
+        const bool ldsf = gat_fits_lds(nmax, true, channels);
+        const size_t lds = gat_lds_bytes_hc(nmax, true, channels, ldsf);
+        GAT_HC_DISPATCH(launch_bwd_hc, lds, G, heads, s, H, dO, att_src, att_dst, e, node_off, edge_off, dH, d_att_src, d_att_dst, nmax, channels, complete);
+    }
     SGA_CHECK_LAUNCH("sga_gat_attn_bwd_hc");
     return SGA_OK;
 }

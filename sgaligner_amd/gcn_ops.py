@@ -57,55 +57,6 @@ def _gcn_aggregate_sp(h, gb, bias, transpose, relu):
     return out
 
 
-class MultiGCNFn(torch.autograd.Function):
-    """MultiGCN.forward over ALL graphs of a batch (reference gat.py:17-25 x eva.py:44-72): GCNConv, ReLU, GCNConv."""
-
-    @staticmethod
-    def forward(ctx, gb, x, w0, b0, w1, b1):
-        if not x.is_cuda:
-            raise RuntimeError('sgaligner_amd.MultiGCNFn: HIP device tensor required; there is no CPU path')
-        if x.dtype not in (torch.float32, torch.float64):
-            raise RuntimeError(f'sgaligner_amd.MultiGCNFn: tot_rel_pose must be float32 or float64, got {x.dtype}')
-        x32 = cast_f32(x.contiguous())
-        w0, b0, w1, b1 = [_req(t.contiguous(), n) for t, n in ((w0, 'gcn0.lin.weight'), (b0, 'gcn0.bias'), (w1, 'gcn1.lin.weight'), (b1, 'gcn1.bias'))]
-        t, f = x32.shape
-        c0, c1 = w0.shape[0], w1.shape[0]
-        if t != gb.T:
-            raise RuntimeError(f'sgaligner_amd: tot_rel_pose has {t} rows but the graphs hold {gb.T} nodes')
-        if w0.shape[1] != f or w1.shape[1] != c0 or b0.shape != (c0,) or b1.shape != (c1,):
-            raise RuntimeError('sgaligner_amd.MultiGCNFn: layer shapes do not chain')
-        h0 = gemm(x32, w0, False, True, t, c0, f)
-        x1 = gcn_aggregate(h0, gb, b0, relu=True, check_status=True)     # both layers see the same edge list: one check per batch
-        h1 = gemm(x1, w1, False, True, t, c1, c0)
-        o1 = gcn_aggregate(h1, gb, b1)
-        ctx.gb = gb
-        ctx.save_for_backward(x32, x1, w1)
-        return o1
-
-    @staticmethod
-    def backward(ctx, d_o1):
-        x32, x1, w1 = ctx.saved_tensors
-        gb = ctx.gb
-        t, f = x32.shape
-        c1, c0 = w1.shape
-        d_o1 = d_o1.contiguous()
-        db1 = colsum(d_o1)
-        dh1 = gcn_aggregate(d_o1, gb, transpose=True)
-        dw1 = gemm(dh1, x1, True, False, c1, c0, t)
-        dx1 = gemm(dh1, w1, False, False, t, c0, c1)
-        d_p0 = torch.empty_like(dx1)
-        _lib.check(_lib.lib().sga_relu_bwd(_p(x1), _p(dx1), _p(d_p0), x1.numel(), _stream()), 'sga_relu_bwd')
-        db0 = colsum(d_p0)
-        dh0 = gcn_aggregate(d_p0, gb, transpose=True)
-        dw0 = gemm(dh0, x32, True, False, c0, f, t)
-        return None, None, dw0, db0, dw1, db1
-
-
-def multi_gcn(gb, x, layer0, layer1):
-    """layer = (lin_weight [out, in], bias [out])."""
-    return MultiGCNFn.apply(gb, x, *layer0, *layer1)
-
-
 # ------------------------------------------------------------------------------------------ GCN, any stack, both routes
 def _relu_bwd(y, gy):
     y, gy = y.contiguous(), gy.contiguous()               # the kernel walks memory: a strided view would be read as if it were dense
@@ -117,8 +68,7 @@ def _relu_bwd(y, gy):
 class GCNLayerFn(torch.autograd.Function):
     """One GCNConv(in, out) over ALL graphs of a batch, with the ReLU that follows it where relu is set: the projection on the GEMM, then the
     aggregation with bias (and ReLU) on the route given ('dense' | 'sparse', already resolved).  Backward: relu_bwd, colsum, the transposed
-    aggregation and the two GEMMs -- the calls of MultiGCNFn in its order, so a two-layer stack returns MultiGCNFn's bits.  The input gets a
-    gradient only where it asks for one (not the first layer's)."""
+    aggregation and the two GEMMs.  The input gets a gradient only where it asks for one (not the first layer's)."""
 
     @staticmethod
     def forward(ctx, gb, x, w, bias, relu, route, check_status):

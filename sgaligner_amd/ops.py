@@ -513,10 +513,9 @@ _REEXPORT = {
     'loss_ops': ('_anchor_chunks', '_sym_chunks', '_sym_jobs', 'SWEEP_GRAD_INFO', 'SWEEP_SUMS_INFO', 'TAU_ICL', 'TAU_IAL', 'ALPHA', 'ContrastiveTermsFn',
                  'contrastive_terms', 'LossHeadFn', 'LossGroups', 'GroupedContrastiveFn', 'grouped_contrastive_terms', 'group_data_dicts',
                  '_allreduce_sum', 'FusedContrastiveFn', 'fused_contrastive_terms'),
-    'gat_ops': ('GraphBatch', '_attn_fwd', '_attn_bwd', '_elu', 'MultiGATFn', 'multi_gat', 'gat_lds_nodes', '_attn_fwd_hc', '_attn_bwd_hc',
-                'GATLayerFn', 'EluFn', 'multi_gat_layers', 'SparseGraph', '_attn_fwd_sp', '_attn_bwd_sp', 'GATLayerSparseFn',
-                'resolve_route'),
-    'gcn_ops': ('gcn_aggregate', 'MultiGCNFn', 'multi_gcn', 'GCNLayerFn', 'multi_gcn_layers'),
+    'gat_ops': ('GraphBatch', '_elu', 'gat_lds_nodes', '_attn_fwd_hc', '_attn_bwd_hc', 'GATLayerFn', 'EluFn', 'multi_gat_layers', 'SparseGraph',
+                '_attn_fwd_sp', '_attn_bwd_sp', 'GATLayerSparseFn', 'resolve_route'),
+    'gcn_ops': ('gcn_aggregate', 'GCNLayerFn', 'multi_gcn_layers'),
     'nca_ops': ('NCAFn', 'nca_loss'),
     'rank_ops': ('PairLayout', 'QueryBlocks', 'simrank', 'pair_metrics'),
 }

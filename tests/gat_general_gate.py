@@ -39,7 +39,7 @@ KERNEL_CASES = ((1, 1), (1, 64), (2, 65), (3, 100), (1, 129), (8, 32), (2, 200),
 KERNEL_SIZES = (1, 2, 3, 64, 65, 128, 129, 256)
 STACKS = (((17, 128, 100), (2, 2)), ((3, 48, 100, 32), (3, 1, 8)), ((3, 1), (1,)), ((5, 256), (8,)), ((3, 65, 129), (2, 1)))
 STACK_SIZES = (1, 2, 7, 33, 64, 129, 200)          # 7: no edges; 33: duplicates and explicit self loops; 64: complete; others 4 n random pairs
-# the shapes of tests/test_gat_gpu.py::test_multigat_fwd_bwd (general against specialised kernel at 2 x 128)
+# the shapes of tests/test_gat_gpu.py::test_multigat_fwd_bwd (the attention kernels at 2 x 128)
 CANON_SHAPES = (((5, 7), True), ((64, 64, 33, 1, 2, 128), False), ((9, 17, 100, 3), True), ((129, 40), True), ((256, 3, 200), True),
                 ((130, 255, 64), False))
 KERNEL_OUTPUTS = ('out', 'dw', 'das', 'dad')       # 'dw' of a kernel alone: dH (the projection is the identity)
@@ -247,8 +247,8 @@ def kernel_subset(case, cap):
     return idx, rows, _collect(case['ref'], idx), _collect(case['yard'], idx)
 
 
-def kernel_run(case, idx, rows, general=True):
-    """The attention kernel, forward and backward, on the card; general=False: the kernels specialised for 2 x 128."""
+def kernel_run(case, idx, rows):
+    """The attention kernel, forward and backward, on the card."""
     from sgaligner_amd import ops
     heads, channels = case['heads'], case['channels']
     graphs = [case['graphs'][i] for i in idx]
@@ -258,13 +258,8 @@ def kernel_run(case, idx, rows, general=True):
         assert all(f == int(g[2]) for f, g in zip(got, graphs) if g[0] > 2), (got, [g[2] for g in graphs])
     dev = lambda t: t.float().cuda().contiguous()
     H, a_s, a_d, b, cot = dev(case['H'][rows]), dev(case['att_s']), dev(case['att_d']), dev(case['bias']), dev(case['cot'][rows])
-    if general:
-        out = ops._attn_fwd_hc(H, heads, channels, a_s, a_d, b, gb, check_status=True)
-        dh, das, dad = ops._attn_bwd_hc(H, cot, heads, channels, a_s, a_d, gb)
-    else:
-        assert (heads, channels) == (2, 128)
-        out = ops._attn_fwd(H, a_s, a_d, b, gb, check_status=True)
-        dh, das, dad = ops._attn_bwd(H, cot, a_s, a_d, gb)
+    out = ops._attn_fwd_hc(H, heads, channels, a_s, a_d, b, gb, check_status=True)
+    dh, das, dad = ops._attn_bwd_hc(H, cot, heads, channels, a_s, a_d, gb)
     torch.cuda.synchronize()
     ops.DEFERRED_CHECKS.flush()
     return dict(out=out, dw=dh, das=das, dad=dad)
@@ -281,7 +276,7 @@ def measure_kernel(heads, channels):
     return res
 
 
-# 2 x 128 on the shapes of test_multigat_fwd_bwd: the general kernel and the specialised one against one reference
+# 2 x 128 (the kernels of that shape) on the shapes of test_multigat_fwd_bwd
 @functools.lru_cache(maxsize=8)
 def canon_case(which):
     sizes, dups = CANON_SHAPES[which]
@@ -313,10 +308,10 @@ def find_canon_seed(which):
     return seed
 
 
-def measure_canon(which, general=True):
+def measure_canon(which):
     case = canon_case(which)
     idx, rows, ref, yard = kernel_subset(case, 256)
-    ke, ye = errors(kernel_run(case, idx, rows, general), ref), errors(yard, ref)
+    ke, ye = errors(kernel_run(case, idx, rows), ref), errors(yard, ref)
     return {k: (ke[k], ye[k]) for k in KERNEL_OUTPUTS}
 
 

@@ -75,7 +75,7 @@ def test_c3_shard_gat_128_nodes_all_graphs():
     def run(g0, g1):
         gb = ops.GraphBatch(np.full(g1 - g0, NOBJ), np.full(g1 - g0, E1), edges[g0 * E1:g1 * E1])
         dl = [[l[k].detach().float().cuda().requires_grad_(True) for k in ('lin_w', 'att_src', 'att_dst', 'bias')] for l in layers]
-        out = ops.multi_gat(gb, x[g0 * NOBJ:g1 * NOBJ], dl[0], dl[1])
+        out = ops.multi_gat_layers(gb, x[g0 * NOBJ:g1 * NOBJ], dl)
         (out * cot[g0 * NOBJ:g1 * NOBJ]).sum().backward()
         return out.detach(), [t.grad for li in dl for t in li]
 

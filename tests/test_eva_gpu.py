@@ -84,7 +84,7 @@ def test_gcn_reference_signature_and_limits():
     with pytest.raises(RuntimeError, match='at most 256 per graph'):
         net.forward_batched(torch.zeros(257, 3, device='cuda'), big)
     with pytest.raises(RuntimeError, match='no CPU path'):
-        ops.multi_gcn(gb, xg.cpu(), net.layer_stack[0].params(), net.layer_stack[1].params())
+        ops.multi_gcn_layers(gb, xg.cpu(), [l.params() for l in net.layer_stack])
     # more than 255 copies of one edge: the deferred status error of the GAT path
     ops.DEFERRED_CHECKS.flush()
     many = EG.graph_batch([(2, np.tile(np.array([[0, 1]], dtype=np.int64), (300, 1)))])

@@ -53,10 +53,9 @@ def test_canonical_state_dict_is_unchanged():
     got = {k: s for k, s in _shapes(enc).items() if 'num_batches_tracked' not in k}
     assert got == want
     assert got['structure_encoder.layer_stack.0.lin_src.weight'] == (256, 3) and got['structure_encoder.layer_stack.1.att_dst'] == (1, 2, 128)
-    assert enc.structure_encoder._canonical
     # hidden_units / heads / dropout reach the structure encoder; structure_embedding stays the reference's Linear(256, emb_dim)
     enc = MultiModalEncoder(['point', 'gat'], 41, 164, hidden_units=[3, 64, 96, 64], heads=[4, 2, 4], dropout=0.25)
-    assert enc.structure_encoder.dropout == 0.25 and not enc.structure_encoder._canonical
+    assert enc.structure_encoder.dropout == 0.25
     assert tuple(enc.structure_encoder.layer_stack[2].lin_src.weight.shape) == (256, 192) and enc.structure_embedding.in_features == 256
 
 
@@ -86,9 +85,13 @@ def test_general_gat_kernels_do_not_spill():
     if not os.path.exists(_build.HIPCC):
         pytest.skip('hipcc not available')
     base, res = kr.analyse(os.path.join(_build.CSRC, 'gat.hip'))
-    for tag in ('gat_attn_fwd_hc_kernel', 'gat_attn_bwd_hc_kernel'):
+    names = kr.demangle(list(res))
+    # general kernels: NJ in {2, 4} x CJ in 1 .. 4 x LDSF; the kernels the entry points launch at 2 x 128: <NJ, LDSF> = <2, true> and <4, false>
+    for tag, count in (('gat_attn_fwd_hc_kernel', 16), ('gat_attn_bwd_hc_kernel', 16), ('gat_attn_fwd_kernel', 2), ('gat_attn_bwd_kernel', 2)):
         ks = [k for k in res if tag in k]
-        assert len(ks) == 16, (tag, sorted(res))                  # NJ in {2, 4} x CJ in 1 .. 4 x LDSF
+        assert len(ks) == count, (tag, sorted(res))
+        if count == 2:
+            assert sorted(names[k] for k in ks) == [tag + '<2, true>', tag + '<4, false>'], sorted(names.values())
         for k in ks:
             v = res[k]
             assert v['scratch'] == 0 and v['vspill'] == 0 and v['sspill'] == 0, (k, v)

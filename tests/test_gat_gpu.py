@@ -51,7 +51,7 @@ def test_multigat_fwd_bwd(sizes, dups):
 
     gb = ops.GraphBatch(np.asarray(sizes), ecnt, et.cuda())
     dl = [[l[k].detach().float().cuda().requires_grad_(True) for k in ('lin_w', 'att_src', 'att_dst', 'bias')] for l in layers]
-    out = ops.multi_gat(gb, x.cuda(), dl[0], dl[1])
+    out = ops.multi_gat_layers(gb, x.cuda(), dl)
     (out * cot.float().cuda()).sum().backward()
     torch.cuda.synchronize()
     assert (out.detach().cpu().double() - ref.detach()).abs().max() < 1e-4
@@ -68,7 +68,7 @@ def test_gat_too_many_nodes_fails_loudly():
     gb = ops.GraphBatch(np.asarray([257]), ecnt, torch.from_numpy(edges).cuda())
     h = torch.randn(257, 256, device='cuda')
     with pytest.raises(RuntimeError, match='at most 256'):
-        ops._attn_fwd(h, torch.randn(256, device='cuda'), torch.randn(256, device='cuda'), torch.zeros(256, device='cuda'), gb)
+        ops._attn_fwd_hc(h, 2, 128, torch.randn(256, device='cuda'), torch.randn(256, device='cuda'), torch.zeros(256, device='cuda'), gb)
 
 
 def test_gat_kernel_vs_hand_derived_case():
@@ -84,7 +84,7 @@ def test_gat_kernel_vs_hand_derived_case():
         ecnt = np.asarray([len(G.EDGES)] if len(sizes) == 1 else [0, len(G.EDGES), 0])
         gb = ops.GraphBatch(np.asarray(sizes), ecnt, torch.from_numpy(G.EDGES).cuda())
         f = lambda a: torch.from_numpy(a).float().cuda()
-        out = ops._attn_fwd(f(hh), f(a_s), f(a_d), f(b), gb, check_status=True)
+        out = ops._attn_fwd_hc(f(hh), 2, 128, f(a_s), f(a_d), f(b), gb, check_status=True)
         torch.cuda.synchronize()
         ops.DEFERRED_CHECKS.flush()
         got = out.cpu().double().numpy()[off:off + 3]
@@ -104,7 +104,7 @@ def test_gat_multiplicity_overflow_fails_loudly():
     for copies, ok in ((255, True), (256, False), (700, False)):
         e = np.concatenate([base, np.repeat(np.array([[4, 2]], dtype=np.int64), copies, axis=0)])
         gb = ops.GraphBatch(np.asarray([n]), np.asarray([len(e)]), torch.from_numpy(e).cuda())
-        out = ops._attn_fwd(h.cuda(), a_s.cuda(), a_d.cuda(), b.cuda(), gb, check_status=True)
+        out = ops._attn_fwd_hc(h.cuda(), 2, 128, a_s.cuda(), a_d.cuda(), b.cuda(), gb, check_status=True)
         torch.cuda.synchronize()
         if ok:
             ops.DEFERRED_CHECKS.flush()
@@ -156,7 +156,7 @@ def test_complete_graph_fast_path_flags_and_equality():
             g2 = ops.GraphBatch(np.asarray(sizes), ecnt, et)
             assert (g2.complete is None) == (not fast)
             dl = [[l[k].detach().float().cuda().requires_grad_(True) for k in ('lin_w', 'att_src', 'att_dst', 'bias')] for l in layers]
-            out = ops.multi_gat(g2, x, dl[0], dl[1])
+            out = ops.multi_gat_layers(g2, x, dl)
             (out * cot).sum().backward()
             torch.cuda.synchronize()
             return out.detach(), [t.grad for li in dl for t in li]
@@ -208,7 +208,7 @@ def test_vs_real_pyg():
                 assert (layers[li][k].grad - pg).abs().max().item() < 1e-9 * max(1.0, pg.abs().max().item()), (n, li, k)
         gb = ops.GraphBatch(np.asarray([n]), np.asarray([edges.shape[0]]), torch.from_numpy(edges).cuda())
         dl = [[l[k].detach().float().cuda().requires_grad_(True) for k in ('lin_w', 'att_src', 'att_dst', 'bias')] for l in layers]
-        out_g = ops.multi_gat(gb, x.cuda(), dl[0], dl[1])
+        out_g = ops.multi_gat_layers(gb, x.cuda(), dl)
         (out_g * cot.float().cuda()).sum().backward()
         torch.cuda.synchronize()
         assert (out_g.detach().cpu().double() - ref.detach()).abs().max().item() < 1e-4, n

@@ -212,7 +212,7 @@ def test_auto_stays_on_the_dense_kernels_for_small_graphs(monkeypatch):
     T = sum(g[0] for g in graphs)
     x = torch.randn(T, 3, generator=torch.Generator().manual_seed(4)).cuda()
     outs = {}
-    for units, heads in (([3, 128, 128], [2, 2]), ([3, 48, 100], [3, 1])):           # the specialised and the general dense kernels
+    for units, heads in (([3, 128, 128], [2, 2]), ([3, 48, 100], [3, 1])):           # the dense kernels of 2 x 128 and the general ones
         for route in ('auto', 'dense', 'sparse'):
             torch.manual_seed(5)
             net = MultiGAT(units, heads, route=route).cuda()

@@ -1,5 +1,5 @@
 """Time the sparse GAT route (csrc/gat_sparse.hip) at 2 heads x 128 channels, forward and backward, with the structure build on its own:
-  (a) BASELINE configs[1]'s graph mix, 1024 complete graphs of 64 nodes, beside the dense route (the specialised kernels) in the same
+  (a) BASELINE configs[1]'s graph mix, 1024 complete graphs of 64 nodes, beside the dense route at the same shape in the same
       process -- the ratio is reported, not gated: the default stays dense and is expected to win there;
   (b) 8 graphs of 1024 nodes with 16 n random pairs;   (c) one complete graph of 1000 nodes;
   (d) the 601-node double star 256 times (two segments of 601 entries among 1200 of 2: what one wave per destination costs under skew).
@@ -76,8 +76,8 @@ def main():
                       f'{d}_model_tb_per_s': round(model[d] / (t[0] * 1e-6) / 1e12, 3)})
         if tag == 'a':
             assert gb.complete is not None and bool(gb.complete.all())
-            df = timed(lambda: ops._attn_fwd(h, a_s, a_d, b, gb))
-            dw = timed(lambda: ops._attn_bwd(h, d_o, a_s, a_d, gb))
+            df = timed(lambda: ops._attn_fwd_hc(h, HEADS, C, a_s, a_d, b, gb))
+            dw = timed(lambda: ops._attn_bwd_hc(h, d_o, HEADS, C, a_s, a_d, gb))
             r.update(dense_fwd_us=round(df[0], 1), dense_bwd_us=round(dw[0], 1), sparse_over_dense_fwd=round(f[0] / df[0], 2),
                      sparse_over_dense_bwd=round(w[0] / dw[0], 2))
         else:

@@ -1,7 +1,8 @@
-"""Measure the general GAT path against plain fp32 arithmetic: the kernel's and the CPU yardstick's errors (tests/gat_general_gate.py: flat
-envelope, fp64 oracle reference) of every attention-kernel case at every batch cut of it, of the general kernel at 2 x 128 on the shapes of
-test_multigat_fwd_bwd beside the kernel specialised for it (the tests judge both by the same r), and of every stack (the masked one included), written to profiles/gat_general_accuracy_vs_fp32.json -- the
-measurement the gate ratios R of the tests are derived from ("measured ratio x 2, rounded up").
+"""Measure the dense GAT path against plain fp32 arithmetic: the kernel's and the CPU yardstick's errors (tests/gat_general_gate.py: flat
+envelope, fp64 oracle reference) of every attention-kernel case at every batch cut of it, of the kernels of 2 x 128 on the shapes
+of test_multigat_fwd_bwd, and of every stack (the masked one included), written to
+profiles/gat_general_accuracy_vs_fp32.json -- the measurement the gate ratios R of the tests are derived from ("measured ratio x 2,
+rounded up").
 Needs the card:  python tools/gat_general_accuracy.py [out.json]"""
 import json
 import os
@@ -30,7 +31,6 @@ def main():
             rows += [row(k, f'kernel {heads}x{channels} nmax<={cap}', ke, ye) for k, (ke, ye) in meas.items()]
     for which in range(len(GG.CANON_SHAPES)):
         rows += [row(k, f'kernel 2x128 shapes[{which}]', ke, ye) for k, (ke, ye) in GG.measure_canon(which).items()]
-        rows += [row(k, f'specialised kernel 2x128 shapes[{which}]', ke, ye) for k, (ke, ye) in GG.measure_canon(which, False).items()]
     for which, (units, heads) in enumerate(GG.STACKS):
         rows += [row(k, f'stack {list(units)}/{list(heads)}', ke, ye) for k, (ke, ye) in GG.measure_stack(which).items()]
     units, heads = GG.STACKS[GG.MASKED_STACK]
